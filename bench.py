@@ -6,15 +6,23 @@ fields, exactly what tests/dslash_test.cpp times with transfer=0 (:455-616).  `v
 reference's kernel-level flop count (1368 / checkerboard site, lib/dslash_twisted_mass.cu:144-160).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--prec 8|4|2] [--recon 18|12] [--dslash tm|tmc|wilson] [--lattice X,Y,Z,T]
+                  [--full] [--dump-outputs DIR]
 
+A plain run sets up, warms up, times the K steps and prints the line; `extra` is empty and `cpu_baseline` null.  --full adds
+the other legs:
 N > 1 (launched by torch.distributed.run): the global lattice is 4-D block-decomposed over the ranks (strong scaling: the
 global volume is fixed); the halo goes through direct peer stores over xGMI where the start-up probe and the first-use check
-allow it, else through grouped RCCL send/recv.  After the Dslash measurement the ranks run the MG-GCR half of the metric on the
-decomposed lattice (extra.mg_gcr; --no-mg skips it).  N = 1 adds the other precisions / actions, the 48^3 x 96 legs, the partitioned
+allow it, else through grouped RCCL send/recv.  With --full, after the Dslash measurement the ranks run the MG-GCR half of the metric on the
+decomposed lattice (extra.mg_gcr; --no-mg skips it).  With --full, N = 1 adds the other precisions / actions, the 48^3 x 96 legs, the partitioned
 sub-lattice kernel of an 8-GPU split, the MG-GCR legs (32^4, its critical kappa, 16^4, 48^3 x 96) and the CPU baselines under `extra`.
 
+--dump-outputs DIR: after the timed steps, the output spinor of the last timed step (what a caller of Dslash receives, host order,
+float64) goes to DIR/dslash_out.npy, whole or as a fixed seeded sample of whole sites when it exceeds 48 MB, and its squared norm over
+the whole field to DIR/dslash_out_norm2.npy (N > 1: one pair per rank, suffix _rank<r>).  The inputs are seeded: the same arguments give
+the same inputs on every run.
+
 One JSON line on stdout; `roofline` is computed from the ALGORITHMIC bytes of the stencil kernel
-divided by its average duration measured with HIP events on the stream the kernel runs on; `cpu_baseline` is
+divided by its average duration measured with HIP events on the stream the kernel runs on; `cpu_baseline` (--full) is
 the oracle (CPU restatement of the reference host path, kind "port") timed on this box's host cores.
 """
 import argparse
@@ -39,6 +47,21 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
 
 
 from synth import make_clover, make_gauge, smooth_gauge, tiled_gauge  # noqa: E402
+
+DUMP_BYTES = 48 << 20   # --dump-outputs: largest field written whole (all ranks together); a larger one is sampled by whole sites
+
+
+def dump_outputs(path, field, norm2, suffix="", budget=DUMP_BYTES, site_reals=24):
+    """--dump-outputs: `field` (host spinor, site_reals reals per site) as path/dslash_out<suffix>.npy in float64, whole if it fits in
+    `budget` bytes, else the sites of a fixed seeded sample in ascending order (the same sites on every run of the same lattice);
+    norm2 (|out|^2 over the whole field) as path/dslash_out_norm2<suffix>.npy"""
+    os.makedirs(path, exist_ok=True)
+    sites = np.asarray(field, dtype=np.float64).reshape(-1, site_reals)
+    keep = budget // (site_reals * 8)
+    if len(sites) > keep:
+        sites = sites[np.sort(np.random.default_rng(2024).choice(len(sites), keep, replace=False))]
+    np.save(os.path.join(path, "dslash_out%s.npy" % suffix), sites)
+    np.save(os.path.join(path, "dslash_out_norm2%s.npy" % suffix), np.array([norm2], dtype=np.float64))
 
 
 class _LineGuard:
@@ -360,9 +383,11 @@ def main():
     ap.add_argument("--dslash", default="tm", choices=["tm", "tmc", "wilson"])
     ap.add_argument("--lattice", default="32,32,32,32")
     ap.add_argument("--fast-gauge", action="store_true", help="links = periodic repetition of 65536 random SU(3) matrices (profiling of big lattices)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the other-precision sweep")
-    ap.add_argument("--no-mg", action="store_true", help="N > 1: skip the MG-GCR leg on the decomposed lattice")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the other-precision sweep")
+    ap.add_argument("--no-mg", action="store_true", help="--full, N > 1: skip the MG-GCR leg on the decomposed lattice")
+    ap.add_argument("--full", action="store_true", help="also run the other legs: precision / action sweep, MG-GCR, 48^3 x 96, CPU baselines (N = 1), MG-GCR on the decomposed lattice (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the output of the last timed step as DIR/*.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -398,7 +423,7 @@ def main():
     rng = np.random.default_rng(1234 + rank)
     src_h = rng.random(Vh_local * 24)
 
-    def run(prec, recon, kind, steps, warmup, prewarm=0.0):
+    def run(prec, recon, kind, steps, warmup, prewarm=0.0, keep_output=False):
         gp = qa.gauge_param(Xl, cuda_prec=prec, recon=recon)
         qa.load_gauge(gauge, gp)
         ip = qa.invert_param(kinds[kind], kappa, mu, +1, "ee", 0, cuda_prec=prec)
@@ -444,18 +469,23 @@ def main():
         flops_site = qa.lib().qudaAmdDslashFlopsPerSite(ip, 0)
         bytes_site = qa.lib().qudaAmdDslashBytesPerSite(ip, 0, 0)
         n2 = dst.norm2()
+        out_h = dst.save(ip, src_h) if keep_output else None   # the last timed step's output, downloaded after the timing
         for f in (src, dst):
             f.free()
         d.free()
-        return dict(wall=wall, sec=sec_kernel, sec_min=sec_min, flops_site=flops_site, bytes_site=bytes_site, norm2=n2, prewarm=n_prewarm)
+        return dict(wall=wall, sec=sec_kernel, sec_min=sec_min, flops_site=flops_site, bytes_site=bytes_site, norm2=n2, prewarm=n_prewarm, out=out_h)
 
-    r = run(args.prec, args.recon, args.dslash, args.steps, args.warmup, prewarm=float(os.environ.get("QUDA_AMD_BENCH_PREWARM", "0.3")))
+    r = run(args.prec, args.recon, args.dslash, args.steps, args.warmup, prewarm=float(os.environ.get("QUDA_AMD_BENCH_PREWARM", "0.3")),
+            keep_output=bool(args.dump_outputs))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r["out"], r["norm2"], "" if world == 1 else "_rank%d" % rank, DUMP_BYTES // world)
+        del r["out"]
     ms_per_step = 1e3 * r["wall"] / args.steps
     gflops = r["flops_site"] * Vh_global / (r["wall"] / args.steps) * 1e-9
     achieved = r["bytes_site"] * Vh_local / r["sec"] * 1e-9  # GB/s of ONE GPU's kernel (per launch)
 
     extra = {}
-    if not args.no_extra and rank == 0 and world == 1:
+    if args.full and not args.no_extra and rank == 0 and world == 1:
         for prec, recon, kind in ((8, 12, "tm"), (4, 18, "tm"), (4, 12, "tm"), (4, 8, "tm"), (2, 18, "tm"), (2, 8, "tm"), (8, 18, "tmc"), (4, 18, "tmc"), (2, 18, "tmc")):
             e = run(prec, recon, kind, max(20, args.steps // 2), 5)
             extra["%s_%s_r%d" % (kind, dtype_name[prec].split("+")[0], recon)] = dict(
@@ -512,7 +542,7 @@ def main():
             extra["halo_8gpu_sublattice"] = halo
 
     g16 = None
-    if not args.no_extra and rank == 0 and world == 1:
+    if args.full and not args.no_extra and rank == 0 and world == 1:
         g32 = smooth_gauge((32, 32, 32, 32), 0.35)
         extra["mg_gcr"] = run_mg(qa, (32, 32, 32, 32), gauge=g32, multi_src=12)
         # the same problem with the production action (twisted CLOVER): lockstep set-up on the clover variant of the multi-rhs stencil
@@ -560,7 +590,7 @@ def main():
         del gc5, h5
 
     cpu = None
-    if rank == 0 and not args.no_cpu:
+    if args.full and rank == 0 and not args.no_cpu:
         import oracle_api  # TEST INFRASTRUCTURE used as the reported CPU baseline ("port" of the reference host path)
         oracle = oracle_api.load()
         cores = os.cpu_count() or 1
@@ -666,7 +696,7 @@ def main():
             "cpu_baseline": cpu,
             "extra": extra,
         }
-    if world > 1 and not args.no_mg and (X == [32, 32, 32, 32] or os.environ.get("QUDA_AMD_BENCH_MG_ANY")):
+    if args.full and world > 1 and not args.no_mg and (X == [32, 32, 32, 32] or os.environ.get("QUDA_AMD_BENCH_MG_ANY")):
         # The second half of the metric on the decomposed lattice: the same 32^4 MG-GCR problem as extra.mg_gcr at N = 1, the
         # hierarchy built and the K-cycle run across the ranks (aggregates never straddle ranks, coarse halos through the same
         # transport, global sums through the collective path).  The Dslash line above is complete at this point; a guard makes sure
