@@ -3,11 +3,12 @@
  * (reference include/qudaQKXTM_Kepler.h:484-508; bodies lib/interface_quda.cpp:6018-6560, :8535-9300, :7093-8530).
  *
  * What this library runs is the SOLVE LOOP each of them opens with — sources, Dirac::prepare, even-odd GCR preconditioned by the
- * multigrid hierarchies in param->preconditioner[UP|DN], Dirac::reconstruct, normalisation.  The contractions, momentum
- * projection and HDF5 / ASCII writers that follow every solve in the reference are QKXTM's own physics code and are not part
- * of this library: instead each finished solution is handed to the sink registered with qudaAmdSetSolutionSink
- * (quda_amd_ext.h), where the driver does its contractions.  Arguments that only those later stages consume (gauge for the
- * plaquette / derivative operators, file names, NUCLEON, momenta) are accepted and ignored.
+ * multigrid hierarchies in param->preconditioner[UP|DN], Dirac::reconstruct, normalisation.  Each finished solution is handed
+ * to the sink registered with qudaAmdSetSolutionSink (quda_amd_ext.h).  With qudaAmdSetTwopOutput(1), calcMG_threepTwop_EvenOdd
+ * also computes the two-point functions of every source on the device (meson and baryon contractions, momentum projection up to
+ * info.Q_sq) and writes the reference's ASCII files named from filename_twop.  Three-point functions, loop contractions and HDF5
+ * output are not part of this library; the arguments only they consume (gauge for the plaquette / derivative operators,
+ * filename_threep, NUCLEON) are accepted and ignored.
  */
 #ifndef _QUDAQKXTM_KEPLER_H
 #define _QUDAQKXTM_KEPLER_H

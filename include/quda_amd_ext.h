@@ -143,8 +143,9 @@ double qudaAmdMultigridTimeTransfer(void *mg_instance, int level, int what, int 
  * calcMG_threepTwop_EvenOdd / calcMG_loop_wOneD_TSM_* (lib/interface_quda.cpp:6018-6531, :7093, :8535) open with the same
  * loop: for every spin-colour component of a point source, Gaussian-smear it with the APE-smeared links, solve for the up
  * quark (twist +, inv_param->preconditionerUP) and the down quark (twist -, preconditionerDN) with even-odd preconditioned
- * GCR, reconstruct, rescale by 2 kappa under mass normalisation.  The reference then contracts and writes HDF5 (out of
- * scope); these entry points hand the propagators back instead.
+ * GCR, reconstruct, rescale by 2 kappa under mass normalisation.  The reference then contracts and writes its files; these
+ * entry points hand the propagators back, and the two-point contractions below (qudaAmdContractTwop, qudaAmdSetTwopOutput)
+ * compute the correlators on the device.  Three-point functions, loop contractions and HDF5 output are not part of the library.
  * Host layouts are the QKXTM ones: sites lexicographic x fastest (LOCAL lattice of the calling rank), vectors
  * iv*24 + (spin*3 + colour)*2 + re/im in the UKQCD basis (lib/qudaQKXTM_Vector_Kepler.cpp:72-81), smearing links
  * gauge_APE[dir][iv*18 + (row*3 + col)*2 + re/im] (lib/qudaQKXTM_Gauge_Kepler.cpp:73-89, what mapEvenOddToNormalGauge
@@ -174,6 +175,35 @@ void qudaAmdCalcMGPropagators(void *h_prop_up, void *h_prop_dn, void **gauge_APE
  * reference does inside those functions.  No sink registered: the solutions are dropped after their norm has been printed. */
 typedef void (*QudaAmdSolutionSink)(void *ctx, const char *kind, int index, int twist_flavor, const double *h_source, const double *h_solution, size_t nreal);
 void qudaAmdSetSolutionSink(QudaAmdSolutionSink sink, void *ctx);
+
+/* ---- two-point correlators of the QKXTM drivers (reference lib/interface_quda.cpp:6960-7030) ----
+ * Mesons (channel order pseudoscalar, scalar, g5g1, g5g2, g5g3, g5g4, g1, g2, g3, g4) and baryons (nucl_nucl, nucl_roper,
+ * roper_nucl, roper_roper, deltapp_deltamm_11/22/33, deltap_deltaz_11/22/33) of the up / down propagators of one source, after
+ * Gaussian smearing at the sink, the rotation (1 +- i g5)/sqrt2 to the physical basis (+ up, - down) and the projection
+ * sum_x e^{-2 pi i n.(x - x0)/L} onto every momentum |n|^2 <= Q_sq.  Flavour index 0 / 1: the up / down propagator for the mesons,
+ * proton (uud) / neutron (ddu) for the baryons.  Time runs from the source (it = 0 is the source time slice: global slice
+ * (it + t0) mod T); the baryons carry the sign -1 where it + t0 >= T, as the reference's ASCII writer applies it. */
+typedef struct QudaAmdTwopParam_s {
+  int sourcePosition[4];   /* GLOBAL (x, y, z, t) */
+  int Q_sq;                /* momenta n with |n|^2 <= Q_sq, in the order of qudaAmdTwopMomenta */
+  int nsmearGauss;         /* sink smearing steps; 0: none, gauge_APE may be NULL */
+  double alphaGauss;
+} QudaAmdTwopParam;
+/* the momentum list: shells iQ = 0 .. Q_sq, inside a shell nx, ny, nz each from +iQ down to -iQ (lib/qudaQKXTM_Kepler_kernels.cu:96-114);
+ * returns Nmoms and, if moms is not NULL, fills moms[Nmoms][3] (max_moms entries available) */
+int qudaAmdTwopMomenta(int Q_sq, int *moms, int max_moms);
+/* global time extent T of the resident lattice (the first dimension of the outputs below) */
+int qudaAmdTwopTimeExtent(void);
+/* h_prop_up / h_prop_dn: 12 vectors each exactly as qudaAmdCalcMGPropagators returns them (LOCAL lattice, lexicographic, UKQCD);
+ * gauge_APE: smearing links as for qudaAmdGaussianSmear (NULL: the resident smeared field, or none with nsmearGauss = 0).
+ * h_mesons [T][Nmoms][2][10][re, im], h_baryons [T][Nmoms][2][10][4 gamma][4 gamma'][re, im], fp64, T global; every rank
+ * receives the full result (summed over the ranks' time slices and spatial sub-volumes).  Either output may be NULL. */
+void qudaAmdContractTwop(double *h_mesons, double *h_baryons, const void *h_prop_up, const void *h_prop_dn, void **gauge_APE, const QudaAmdTwopParam *p);
+/* off by default.  On: calcMG_threepTwop_EvenOdd contracts every source from the device-resident solutions (sink smearing with
+ * info.nsmearGauss / alphaGauss, momenta info.Q_sq) after its 24 solves and rank 0 writes the reference's ASCII files
+ * <filename_twop>.mesons.SS.xx.yy.zz.tt.dat and <filename_twop>.baryons.SS.xx.yy.zz.tt.dat; the solution sink is still called as
+ * before.  CorrSpace = POSITION_SPACE and HighMomForm need HDF5 and are errors; CorrFileFormat = HDF5_FORM warns and writes ASCII. */
+void qudaAmdSetTwopOutput(int enable);
 
 /* ILDG gauge configurations in LIME containers (the step in front of loadGaugeQuda in the QKXTM drivers).  qudaAmdReadLimeGauge
  * has the semantics of readLimeGauge / readLimeGaugeSmeared (qkxtm/QKXTM_read_conf.h:107-400, :819-835): every rank reads the

@@ -119,7 +119,7 @@ EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLo
                  "qudaAmdMultigridVerify", "qudaAmdMultigridCycle", "qudaAmdTimeAxpy", "qudaAmdMultigridLevels", "qudaAmdMultigridLevelInfo",
                  "qudaAmdMultigridSetHalfStorage", "qudaAmdMultigridGetNullVector", "qudaAmdMultigridGetV", "qudaAmdMultigridGetCoarseLinks", "qudaAmdMultigridApply", "qudaAmdMultigridApplyBlock",
                  "qudaAmdMultigridTimeApply", "qudaAmdMultigridTimeTransfer", "qudaAmdSetExitLine", "qudaAmdDiracPrepare", "qudaAmdDiracReconstruct", "qudaAmdSpinorRawInfo", "qudaAmdGaugeRawInfo", "qudaAmdCloverRawInfo", "qudaAmdRawDeviceCopy",
-                 "qudaAmdSetSolutionSink", "qudaAmdCommStats", "qudaAmdDescribeHaloError", "qudaAmdMultigridOrthoFallbackBlocks", "qudaAmdProfileMarker", "qudaAmdAccountStart", "qudaAmdAccountDump", "qudaAmdWriteSpinorFields", "qudaAmdReadSpinorFields", "qudaAmdMultigridRefine", "qudaAmdMultigridSetFused", "qudaAmdMultigridFusedStats", "qudaAmdMultiSrcStats"]
+                 "qudaAmdSetSolutionSink", "qudaAmdCommStats", "qudaAmdDescribeHaloError", "qudaAmdMultigridOrthoFallbackBlocks", "qudaAmdProfileMarker", "qudaAmdAccountStart", "qudaAmdAccountDump", "qudaAmdWriteSpinorFields", "qudaAmdReadSpinorFields", "qudaAmdMultigridRefine", "qudaAmdMultigridSetFused", "qudaAmdMultigridFusedStats", "qudaAmdMultiSrcStats", "qudaAmdTwopMomenta", "qudaAmdTwopTimeExtent", "qudaAmdContractTwop", "qudaAmdSetTwopOutput"]
 
 _lib = None
 
@@ -127,6 +127,11 @@ _lib = None
 class QudaAmdSourceParam(C.Structure):
     """include/quda_amd_ext.h: the source description of the QKXTM solve loop"""
     _fields_ = [("sourcePosition", C.c_int * 4), ("nsmearGauss", C.c_int), ("alphaGauss", C.c_double)]
+
+
+class QudaAmdTwopParam(C.Structure):
+    """include/quda_amd_ext.h: source and sink description of the two-point contractions"""
+    _fields_ = [("sourcePosition", C.c_int * 4), ("Q_sq", C.c_int), ("nsmearGauss", C.c_int), ("alphaGauss", C.c_double)]
 
 
 def lib():
@@ -231,6 +236,14 @@ def lib():
         L.qudaAmdSaveSmearedGauge.argtypes = [C.POINTER(_p), _i]
         L.qudaAmdGaussianSmear.argtypes = [_p, _p, C.POINTER(_p), _i, _d]
         L.qudaAmdCalcMGPropagators.argtypes = [_p, _p, C.POINTER(_p), C.POINTER(QudaInvertParam), C.POINTER(QudaAmdSourceParam)]
+        L.qudaAmdTwopMomenta.argtypes = [_i, C.POINTER(_i), _i]
+        L.qudaAmdTwopMomenta.restype = _i
+        L.qudaAmdTwopTimeExtent.argtypes = []
+        L.qudaAmdTwopTimeExtent.restype = _i
+        L.qudaAmdContractTwop.argtypes = [_p, _p, _p, _p, C.POINTER(_p), C.POINTER(QudaAmdTwopParam)]
+        L.qudaAmdContractTwop.restype = None
+        L.qudaAmdSetTwopOutput.argtypes = [_i]
+        L.qudaAmdSetTwopOutput.restype = None
         _lib = L
     return _lib
 
@@ -461,6 +474,39 @@ def calc_mg_propagators(gauge_lex, ip, source_position, nsmear, alpha, local_vol
     keep, links = _lex_links(gauge_lex)
     lib().qudaAmdCalcMGPropagators(_vp(up), _vp(dn), links, C.byref(ip), C.byref(sp))
     return up, dn
+
+
+def twop_momenta(Q_sq):
+    """qudaAmdTwopMomenta: the momenta |n|^2 <= Q_sq of the two-point functions as an (Nmoms, 3) int array, in the reference's order"""
+    n = lib().qudaAmdTwopMomenta(int(Q_sq), None, 0)
+    out = np.zeros((n, 3), dtype=np.int32)
+    lib().qudaAmdTwopMomenta(int(Q_sq), out.ctypes.data_as(C.POINTER(_i)), n)
+    return out
+
+
+def contract_twop(prop_up, prop_dn, gauge_lex, source_position, Q_sq, nsmear, alpha):
+    """qudaAmdContractTwop on two propagators as calc_mg_propagators returns them ((12, V*24) lexicographic UKQCD, local lattice):
+    returns (mesons (T, Nmoms, 2, 10), baryons (T, Nmoms, 2, 10, 4, 4)) complex128, time relative to the source"""
+    up = np.ascontiguousarray(prop_up, dtype=np.float64)
+    dn = np.ascontiguousarray(prop_dn, dtype=np.float64)
+    if up.shape != dn.shape or up.shape[0] != 12:
+        raise ValueError("prop_up / prop_dn must both be (12, V*24)")
+    p = QudaAmdTwopParam()
+    for k in range(4):
+        p.sourcePosition[k] = int(source_position[k])
+    p.Q_sq, p.nsmearGauss, p.alphaGauss = int(Q_sq), int(nsmear), float(alpha)
+    T = lib().qudaAmdTwopTimeExtent()
+    nm = lib().qudaAmdTwopMomenta(int(Q_sq), None, 0)
+    mes = np.zeros((T, nm, 2, 10, 2))
+    bar = np.zeros((T, nm, 2, 10, 4, 4, 2))
+    keep, links = _lex_links(gauge_lex)
+    lib().qudaAmdContractTwop(_vp(mes), _vp(bar), _vp(up), _vp(dn), links, C.byref(p))
+    return mes[..., 0] + 1j * mes[..., 1], bar[..., 0] + 1j * bar[..., 1]
+
+
+def set_twop_output(enable):
+    """qudaAmdSetTwopOutput: calcMG_threepTwop_EvenOdd writes the two-point ASCII files"""
+    lib().qudaAmdSetTwopOutput(int(bool(enable)))
 
 
 class Spinor:

@@ -24,6 +24,7 @@
 #include "device_io.h"
 #include "dslash.h"
 #include "interface_internal.h"
+#include "lex_index.h"
 #include "multigrid.h"
 #include "p2p.h"
 #include "quda_amd_ext.h"
@@ -34,12 +35,6 @@ namespace quda {
 void *stagingBuffer(size_t bytes);   // fields.hip
 
 // ---- site order / basis: QKXTM host vector (lexicographic sites, UKQCD spin) <-> device full field (even-odd, DeGrand-Rossi) ----
-__device__ __forceinline__ long lex_of(int idx, int parity, int Xh, int Y, int Z) {
-  int l = idx / Xh;
-  const int y = l % Y; l /= Y;
-  const int z = l % Z, t = l / Z;
-  return 2l * idx + ((y + z + t + parity) & 1);   // checkerboard index = lexicographic index / 2
-}
 
 __global__ void __launch_bounds__(256) lex_to_dev_kernel(double *dev, int stride, size_t parityDoubles, const double *lex, int Vh, int Xh, int Y, int Z, int change) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x, parity = blockIdx.y;
@@ -95,7 +90,7 @@ static void checkFullDouble(const ColorSpinorField &f) {
     errorQuda("expected a full fp64 device spinor");
 }
 
-static void lexToDevice(ColorSpinorField &dst, const double *h_lex, const LatticeGeom &g, bool ukqcd) {
+void lexToDevice(ColorSpinorField &dst, const double *h_lex, const LatticeGeom &g, bool ukqcd) {
   checkFullDouble(dst);
   const size_t bytes = (size_t)g.V * 24 * sizeof(double);
   double *stage = (double *)stagingBuffer(bytes);
@@ -119,7 +114,7 @@ static void deviceToLex(double *h_lex, const ColorSpinorField &src, const Lattic
 }
 
 // ---- the smearing links: QKXTM host layout gauge[dir][lexicographic site][3][3][2] (lib/qudaQKXTM_Gauge_Kepler.cpp:73-89) ----
-static GaugeField *loadLexGauge(void **gauge_lex, const LatticeGeom &g) {
+GaugeField *loadLexGauge(void **gauge_lex, const LatticeGeom &g) {
   // reorder to the QDP host order (even sites then odd) the loader takes; host loop, once per call
   std::vector<std::vector<double>> eo(4, std::vector<double>((size_t)g.V * 18));
   void *ptr[4];
@@ -141,7 +136,7 @@ static GaugeField *loadLexGauge(void **gauge_lex, const LatticeGeom &g) {
 }
 
 // v <- smear^n(v):  psi' = (psi + alpha sum_{i<3} [U_i(x) psi(x+i) + U_i(x-i)^dag psi(x-i)]) / (1 + 6 alpha)   (Gauss_core_Kepler.h)
-static void gaussianSmear(ColorSpinorField &v, const GaugeField &U, double alpha, int nsmear) {
+void gaussianSmear(ColorSpinorField &v, const GaugeField &U, double alpha, int nsmear) {
   checkFullDouble(v);
   ColorSpinorField tmp(v);
   ColorSpinorField *src = &v, *dst = &tmp;
@@ -199,7 +194,8 @@ namespace quda {
 // the solve loop itself; every finished propagator (isc = spin * 3 + colour of the source, flavour +1 up / -1 down) is handed to
 // `each` as a lexicographic UKQCD host vector of V * 24 doubles that is only valid during the call
 void calcMGPropagatorsEach(void **gauge_APE, QudaInvertParam *param, const QudaAmdSourceParam *src, const char *fname,
-                           void (*each)(void *ctx, int isc, int flavor, const double *h_prop, size_t nreal), void *ctx) {
+                           void (*each)(void *ctx, int isc, int flavor, const double *h_prop, size_t nreal), void *ctx,
+                           void (*eachDevice)(void *ctx, int isc, int flavor, ColorSpinorField &x, double scale) = nullptr) {
   if (!gaugePrecise) errorQuda("%s: Gauge field not allocated", fname);
   if (!cloverPrecise && param->dslash_type == QUDA_TWISTED_CLOVER_DSLASH) errorQuda("%s: Clover field not allocated", fname);
   if (!src) errorQuda("%s: source description is NULL", fname);
@@ -295,6 +291,7 @@ void calcMGPropagatorsEach(void **gauge_APE, QudaInvertParam *param, const QudaA
       for (int isc = 0; isc < 12; isc++) {
         dirac.reconstruct(*xs[isc], *bs[isc], param->solution_type);
         result = *xs[isc];
+        if (eachDevice) eachDevice(ctx, isc, fl == 0 ? +1 : -1, result, rescale ? 2.0 * param->kappa : 1.0);
         deviceToLex(h_one.data(), result, g, true, rescale ? 2.0 * param->kappa : 1.0);
         each(ctx, isc, fl == 0 ? +1 : -1, h_one.data(), vec);
       }
@@ -328,6 +325,7 @@ void calcMGPropagatorsEach(void **gauge_APE, QudaInvertParam *param, const QudaA
       dirac.reconstruct(*x, *b, param->solution_type);
       delete solve;
       result = *x;
+      if (eachDevice) eachDevice(ctx, isc, fl == 0 ? +1 : -1, result, rescale ? 2.0 * param->kappa : 1.0);
       deviceToLex(h_one.data(), result, g, true, rescale ? 2.0 * param->kappa : 1.0);
       each(ctx, isc, fl == 0 ? +1 : -1, h_one.data(), vec);
     }
@@ -521,10 +519,32 @@ static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInf
 
 extern "C" void qudaAmdSetSolutionSink(QudaAmdSolutionSink sink, void *ctx) { quda::g_sink = sink; quda::g_sinkCtx = ctx; }
 
+namespace quda {
+struct TwopProps;
+bool twopOutputEnabled();
+TwopProps *twopPropsCreate(const LatticeGeom &g);
+void twopPropsDestroy(TwopProps *p);
+void twopAbsorbColumn(TwopProps &props, int fl, int isc, ColorSpinorField &v, const LatticeGeom &g, const GaugeField *U, int nsmear, double alpha, bool deviceBasis,
+                      double scale);
+void twopContract(TwopProps &props, const LatticeGeom &g, const int src[4], int Q_sq, double *h_mes, double *h_bar);
+void twopWriteAscii(const char *fname_twop, const int src[4], int Q_sq, int T, const double *h_mes, const double *h_bar);
+}  // namespace quda
+
 void calcMG_threepTwop_EvenOdd(void **gaugeSmeared, void **gauge, QudaGaugeParam *gauge_param, QudaInvertParam *param, quda::qudaQKXTMinfo_Kepler info,
                                char *filename_twop, char *filename_threep, quda::WHICHPARTICLE NUCLEON) {
-  (void)gauge; (void)gauge_param; (void)filename_twop; (void)filename_threep; (void)NUCLEON;   // consumed by the contractions / writers only
+  (void)gauge; (void)gauge_param; (void)filename_threep; (void)NUCLEON;   // consumed by the three-point stage only
   if (info.Nsources < 0 || info.Nsources > MAX_NSOURCES) errorQuda("calcMG_threepTwop_EvenOdd: Nsources = %d", info.Nsources);
+  // two-point output (qudaAmdSetTwopOutput): contractions from the device-resident solutions, the reference's ASCII files
+  const bool twop = quda::twopOutputEnabled();
+  if (twop) {
+    if (info.CorrSpace == quda::POSITION_SPACE)
+      errorQuda("calcMG_threepTwop_EvenOdd: position-space correlators are written only as HDF5, which this library does not link; use CorrSpace = MOMENTUM_SPACE");
+    if (info.HighMomForm)
+      errorQuda("calcMG_threepTwop_EvenOdd: the high-momenta form is written only as HDF5, which this library does not link; set HighMomForm = false");
+    if (info.CorrFileFormat == quda::HDF5_FORM) warningQuda("calcMG_threepTwop_EvenOdd: HDF5 is not linked into this library; writing the two-point functions in ASCII format");
+    if (!filename_twop) errorQuda("calcMG_threepTwop_EvenOdd: filename_twop is NULL");
+    if (info.Q_sq < 0) errorQuda("calcMG_threepTwop_EvenOdd: Q_sq = %d", info.Q_sq);
+  }
   double secs = 0, gflops = 0;
   int iters = 0;
   for (int isource = 0; isource < info.Nsources; isource++) {
@@ -532,10 +552,42 @@ void calcMG_threepTwop_EvenOdd(void **gaugeSmeared, void **gauge, QudaGaugeParam
     for (int k = 0; k < 4; k++) src.sourcePosition[k] = info.sourcePosition[isource][k];
     src.nsmearGauss = info.nsmearGauss;
     src.alphaGauss = info.alphaGauss;
-    int base = 12 * isource;
-    quda::calcMGPropagatorsEach(gaugeSmeared, param, &src, "calcMG_threepTwop_EvenOdd",
-                                [](void *c, int isc, int flavor, const double *h, size_t n) { quda::toSink(flavor > 0 ? "prop_up" : "prop_dn", *(int *)c + isc, flavor, nullptr, h, n); }, &base);
+    struct Ctx {
+      int base;
+      quda::TwopProps *props;
+      quda::ColorSpinorField *work;
+      quda::GaugeField *U;
+      int nsmear;
+      double alpha;
+    } ctx = {12 * isource, nullptr, nullptr, nullptr, info.nsmearGauss, info.alphaGauss};
+    const quda::LatticeGeom &g = quda::residentGeom();
+    if (twop) {
+      if (info.nsmearGauss > 0 && !gaugeSmeared && !quda::gaugeSmeared) errorQuda("calcMG_threepTwop_EvenOdd: gaugeSmeared is NULL and no smeared field is resident (performAPEnStep)");
+      ctx.U = info.nsmearGauss > 0 ? (gaugeSmeared ? quda::loadLexGauge(gaugeSmeared, g) : quda::gaugeSmeared) : nullptr;
+      ctx.props = quda::twopPropsCreate(g);
+      quda::ColorSpinorParam cp = quda::deviceSpinorParam(QUDA_DOUBLE_PRECISION, QUDA_FULL_SITE_SUBSET, QUDA_TWIST_NO);
+      cp.create = QUDA_ZERO_FIELD_CREATE;
+      ctx.work = new quda::ColorSpinorField(cp);
+    }
+    quda::calcMGPropagatorsEach(
+        gaugeSmeared, param, &src, "calcMG_threepTwop_EvenOdd",
+        [](void *c, int isc, int flavor, const double *h, size_t n) { quda::toSink(flavor > 0 ? "prop_up" : "prop_dn", ((Ctx *)c)->base + isc, flavor, nullptr, h, n); }, &ctx,
+        twop ? +[](void *c, int isc, int flavor, quda::ColorSpinorField &x, double scale) {
+          Ctx *o = (Ctx *)c;
+          quda::blas::copy(*o->work, x);   // the solution itself still goes to the sink unsmeared
+          quda::twopAbsorbColumn(*o->props, flavor > 0 ? 0 : 1, isc, *o->work, quda::residentGeom(), o->U, o->nsmear, o->alpha, true, scale);
+        } : nullptr);
     secs += param->secs; gflops += param->gflops; iters += param->iter;
+    if (twop) {
+      const int T = g.X[3] * quda::commGrid().dims[3];
+      const int Nm = qudaAmdTwopMomenta(info.Q_sq, nullptr, 0);
+      std::vector<double> mes((size_t)T * Nm * 2 * 10 * 2), bar((size_t)T * Nm * 2 * 10 * 16 * 2);
+      quda::twopContract(*ctx.props, g, src.sourcePosition, info.Q_sq, mes.data(), bar.data());
+      quda::twopWriteAscii(filename_twop, src.sourcePosition, info.Q_sq, T, mes.data(), bar.data());
+      delete ctx.work;
+      quda::twopPropsDestroy(ctx.props);
+      if (ctx.U && gaugeSmeared) delete ctx.U;
+    }
   }
   param->secs = secs; param->gflops = gflops; param->iter = iters;
 }

@@ -1,0 +1,172 @@
+"""Two-point correlators (qudaAmdContractTwop, reference lib/interface_quda.cpp:6960-7030) against an independent numpy restatement:
+every channel built from explicit 4x4 gamma matrices of the UKQCD basis with einsum, the rotation (1 +- i g5)/sqrt2, sink smearing
+through the oracle, explicit momentum phases, source-relative time and the baryons' wrap sign."""
+import importlib
+import itertools
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+from synth import smooth_gauge  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def qa():
+    mod = importlib.import_module("quda-qkxtm-multigrid_amd")
+    mod.init(0)
+    yield mod
+    mod.end()
+
+
+def _lex_gauge(oracle, gauge, X):
+    return np.stack([oracle.eo_to_lex(np.ascontiguousarray(gauge[d]), list(X), 18) for d in range(4)])
+
+
+# ---- UKQCD gamma matrices: g_k = [[0, i s_k], [-i s_k, 0]], g4 = diag(1, 1, -1, -1), g5 = g1 g2 g3 g4 ----
+_s = [np.array([[0, 1], [1, 0]], complex), np.array([[0, -1j], [1j, 0]]), np.array([[1, 0], [0, -1]], complex)]
+_Z2 = np.zeros((2, 2))
+G = {k: np.block([[_Z2, 1j * _s[k - 1]], [-1j * _s[k - 1], _Z2]]) for k in (1, 2, 3)}
+G[4] = np.diag([1, 1, -1, -1]).astype(complex)
+G[5] = G[1] @ G[2] @ G[3] @ G[4]
+ONE = np.eye(4, dtype=complex)
+CC = G[4] @ G[2]
+EPS = np.zeros((3, 3, 3))
+for p in itertools.permutations(range(3)):
+    EPS[p] = np.linalg.det(np.eye(3)[list(p)])
+
+
+def _to_tensor(prop, V):
+    """(12, V*24) host columns (isc = nu*3 + b; site, mu*3 + a, re/im) -> P[site, mu, nu, a, b]"""
+    c = prop.reshape(12, V, 12, 2)
+    c = c[..., 0] + 1j * c[..., 1]
+    return c.reshape(4, 3, V, 4, 3).transpose(2, 3, 0, 4, 1)
+
+
+def _rotate(P, sign):
+    R = (ONE + sign * 1j * G[5]) / np.sqrt(2)
+    return np.einsum("mr,xrsab,sn->xmnab", R, P, R)
+
+
+def _mesons_site(P):
+    gams = [G[5], ONE, G[5] @ G[1], G[5] @ G[2], G[5] @ G[3], G[5] @ G[4], G[1], G[2], G[3], G[4]]
+    out = []
+    for gam in gams:
+        g = G[5] @ gam
+        out.append(np.einsum("xabij,bc,xdcij,da->x", P, g, P.conj(), g, optimize=True))   # Tr[P g P^+ g]
+    return np.stack(out, axis=1)
+
+
+def _wick(A, B, pi, Q):
+    """sum eps_abc eps_a'b'c' A_{alpha beta} B_{beta' alpha'} Q0[alpha, .] Q1[beta, .] Q2[gamma, .], sink slot s -> source slot pi[s]"""
+    sink_s, src_s, sink_c, src_c = "ijk", "lmn", "abc", "def"
+    specs = ["x" + sink_s[s] + src_s[pi[s]] + sink_c[s] + src_c[pi[s]] for s in range(3)]
+    return np.einsum("abc,def,ij,ml," + ",".join(specs) + "->xkn", EPS, EPS, A, B, *Q, optimize=True)
+
+
+def _baryons_site(U, D):
+    out = []
+    Cg5 = CC @ G[5]
+    # sink diquark A_{alpha beta}, source diquark M_{alpha' beta'} (B = M^T in _wick's B_{beta' alpha'})
+    for A, M, L, R in ((Cg5, Cg5, ONE, ONE), (Cg5, CC, ONE, G[5]), (CC, Cg5, G[5], ONE), (CC, CC, G[5], G[5])):
+        N = _wick(A, M.T, (0, 1, 2), (U, D, U)) - _wick(A, M.T, (2, 1, 0), (U, D, U))
+        out.append(np.einsum("gd,xde,ef->xgf", L, N, R))
+    deltas_iso1, deltas_iso12 = [], []
+    for k in (1, 2, 3):
+        A = CC @ G[k]
+        B = (G[4] @ A.conj().T @ G[4]).T
+        acc = 0
+        for p in itertools.permutations(range(3)):
+            acc = acc + np.linalg.det(np.eye(3)[list(p)]) * _wick(A, B, p, (U, U, U))
+        deltas_iso1.append(acc)
+        terms = [(-4, (2, 1, 0), (U, D, U)), (2, (1, 2, 0), (U, D, U)), (2, (2, 0, 1), (U, U, D)), (-2, (0, 2, 1), (U, U, D)),
+                 (-2, (0, 2, 1), (U, D, U)), (-1, (1, 0, 2), (U, U, D)), (1, (0, 1, 2), (U, U, D)), (4, (0, 1, 2), (U, D, U))]
+        deltas_iso12.append(sum(w * _wick(A, B, p, q) for w, p, q in terms) / 3.0)
+    return np.stack(out + deltas_iso1 + deltas_iso12, axis=1)   # (V, 10, 4, 4)
+
+
+def numpy_twop(prop_up, prop_dn, X, src, moms, smear=None):
+    V = int(np.prod(X))
+    if smear is not None:
+        prop_up = np.stack([smear(c) for c in prop_up])
+        prop_dn = np.stack([smear(c) for c in prop_dn])
+    U = _rotate(_to_tensor(prop_up, V), +1)
+    D = _rotate(_to_tensor(prop_dn, V), -1)
+    mes = np.stack([_mesons_site(U), _mesons_site(D)], axis=1)                 # (V, 2, 10)
+    bar = np.stack([_baryons_site(U, D), _baryons_site(D, U)], axis=1)         # (V, 2, 10, 4, 4)
+    T, Z, Y, Xx = X[3], X[2], X[1], X[0]
+    z, y, x = np.meshgrid(np.arange(Z), np.arange(Y), np.arange(Xx), indexing="ij")
+    ph = np.stack([np.exp(-2j * np.pi * (n[0] * (x - src[0]) / Xx + n[1] * (y - src[1]) / Y + n[2] * (z - src[2]) / Z)) for n in moms])   # (Nm, Z, Y, X)
+    mes = np.einsum("mzyx,tzyxfc->tmfc", ph, mes.reshape(T, Z, Y, Xx, 2, 10))
+    bar = np.einsum("mzyx,tzyxfcgh->tmfcgh", ph, bar.reshape(T, Z, Y, Xx, 2, 10, 4, 4))
+    ts = (np.arange(T) + src[3]) % T
+    sign = np.where(np.arange(T) + src[3] >= T, -1.0, 1.0)
+    return mes[ts], bar[ts] * sign[:, None, None, None, None, None]
+
+
+def _blockwise_err(got, want, axes):
+    """max |got - want| / max |want| over each (flavour, channel) block"""
+    worst = 0.0
+    g = np.moveaxis(got, axes, (0, 1)).reshape(2, 10, -1)
+    w = np.moveaxis(want, axes, (0, 1)).reshape(2, 10, -1)
+    for f in range(2):
+        for c in range(10):
+            worst = max(worst, np.max(np.abs(g[f, c] - w[f, c])) / np.max(np.abs(w[f, c])))
+    return worst
+
+
+def _momenta(Q):
+    return [(nx, ny, nz) for iQ in range(Q + 1) for nx in range(iQ, -iQ - 1, -1) for ny in range(iQ, -iQ - 1, -1) for nz in range(iQ, -iQ - 1, -1)
+            if nx * nx + ny * ny + nz * nz == iQ]
+
+
+@pytest.mark.parametrize("X,src", [((4, 4, 4, 4), (1, 2, 3, 3)), ((6, 4, 2, 8), (5, 1, 1, 6))])
+@pytest.mark.parametrize("nsmear", [0, 2])
+@pytest.mark.parametrize("mask", [0, 0b0110, 0b1010])
+def test_contractions_match_numpy(qa, oracle, X, src, nsmear, mask):
+    """random complex propagators (nothing relies on g5-hermiticity); 1e-12 relative to the largest entry of each (channel, flavour) block"""
+    gauge, _, _ = oracle.make_fields(list(X), seed=5, antiperiodic_t=False, clover=False)
+    qa.load_gauge(gauge, qa.gauge_param(X, t_boundary=qa.QUDA_PERIODIC_T))
+    g_lex = _lex_gauge(oracle, gauge, X)
+    V = int(np.prod(X))
+    rng = np.random.default_rng(11 + nsmear + mask)
+    up, dn = rng.standard_normal((12, V * 24)), rng.standard_normal((12, V * 24))
+    Q, alpha = 3, 0.7
+    qa.lib().qudaAmdSetPartitionMask(mask)
+    try:
+        mes, bar = qa.contract_twop(up, dn, g_lex if nsmear else None, src, Q, nsmear, alpha)
+    finally:
+        qa.lib().qudaAmdSetPartitionMask(0)
+    moms = _momenta(Q)
+    assert np.array_equal(qa.twop_momenta(Q), np.array(moms))
+    smear = (lambda v: oracle.gauss_smear(v, g_lex, list(X), alpha, nsmear)) if nsmear else None
+    wm, wb = numpy_twop(up, dn, X, src, moms, smear)
+    assert mes.shape == (X[3], len(moms), 2, 10) and bar.shape == (X[3], len(moms), 2, 10, 4, 4)
+    em, eb = _blockwise_err(mes, wm, (2, 3)), _blockwise_err(bar, wb, (2, 3))
+    assert em < 1e-12 and eb < 1e-12, (em, eb)
+
+
+def test_pseudoscalar_on_solved_propagators(qa, oracle):
+    """8^3 x 16 smooth gauge, solved and sink-smeared propagators: at p = 0 the pseudoscalar of each flavour is real and equals
+    +sum over the time slice of |S_smeared|^2 (G = g5 g5 = 1, and the rotation is unitary), with no gamma table involved"""
+    X, kappa, mu = (8, 8, 8, 16), 0.12, 0.05
+    gauge = smooth_gauge(X, 0.35)
+    qa.load_gauge(gauge, qa.gauge_param(X, t_boundary=qa.QUDA_PERIODIC_T))
+    g_lex = _lex_gauge(oracle, gauge, X)
+    ip = qa.invert_param(qa.QUDA_TWISTED_MASS_DSLASH, kappa, mu, +1, "ee", 0, cuda_prec=8, solution_type=qa.QUDA_MAT_SOLUTION,
+                         gamma_basis=qa.QUDA_UKQCD_GAMMA_BASIS)
+    ip.solve_type, ip.inv_type, ip.gcrNkrylov, ip.tol, ip.maxiter = qa.QUDA_DIRECT_PC_SOLVE, qa.QUDA_GCR_INVERTER, 20, 1e-10, 4000
+    ip.inv_type_precondition = qa.QUDA_INVALID_ENUM
+    ip.verbosity = qa.QUDA_SILENT
+    V = int(np.prod(X))
+    src, ns, alpha = (3, 5, 2, 11), 3, 0.5
+    up, dn = qa.calc_mg_propagators(g_lex, ip, src, ns, alpha, V)
+    mes, _ = qa.contract_twop(up, dn, g_lex, src, 0, ns, alpha)
+    T, Vs = X[3], V // X[3]
+    for f, prop in enumerate((up, dn)):
+        sm = np.stack([qa.gaussian_smear(c, g_lex, ns, alpha) for c in prop]).reshape(12, T, Vs * 24)
+        want = np.einsum("ctk,ctk->t", sm, sm)[(np.arange(T) + src[3]) % T]
+        ps = mes[:, 0, f, 0]
+        assert np.max(np.abs(ps.imag) / np.abs(ps.real)) < 1e-10
+        assert np.max(np.abs(ps.real - want) / want) < 1e-10
