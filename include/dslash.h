@@ -42,6 +42,8 @@ void applyCovariantShift(ColorSpinorField &out, const ColorSpinorField &in, cons
                          const ColorSpinorField *x, double xcoef);
 // out(x) = in(x + dhat(dir)) for a 24-real fp64 planar site field (out: parity block `parity`, in: the other parity's block), ghost-aware
 void applyShift(double *out, const double *in, const LatticeGeom &g, int stride, int parity, int dir);
+// the ghost zone such a hop reads (partitioned dimension only), copied to ghostOut: faceCB[dir / 2] x 24 doubles, planar with stride faceCB
+void exchangeFullFace(void *ghostOut, const double *in, const LatticeGeom &g, int stride, int parity, int dir);
 
 // multi-right-hand-side FULL operator on block fields ([parity * Vh + x][12 spin-colour][nrhs] float2, see block.h):
 // out = (1 + i a g5) in - kappa D in for nrhs vectors per link load (fp32, recon 18, unpartitioned lattice)

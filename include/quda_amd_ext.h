@@ -205,6 +205,32 @@ void qudaAmdContractTwop(double *h_mesons, double *h_baryons, const void *h_prop
  * before.  CorrSpace = POSITION_SPACE and HighMomForm need HDF5 and are errors; CorrFileFormat = HDF5_FORM warns and writes ASCII. */
 void qudaAmdSetTwopOutput(int enable);
 
+/* ---- disconnected quark loops of the QKXTM drivers (reference lib/qudaQKXTM_Loops_Kepler.cpp:300-497) ----
+ * One-end-trick contractions with one covariant derivative of ONE solution vector x, phi = g5 D_W x (the kappa-normalised Wilson
+ * or Wilson-clover operator at mu = 0 on the resident fields), C[u, v][4a + b] = sum_c conj(u[(a + 2) mod 4, c]) v[b, c] in the UKQCD
+ * basis, F / B the forward / backward covariant shifts on the resident precise links.  18 blocks of 16 complex numbers:
+ *   0 Scalar -C[x,x];  1 dOp +C[x,phi];  2+mu Loops -(C[x,Fx] + C[Bx,x] - C[Fx,x] - C[x,Bx]);  6+mu LoopsCv -(the four added);
+ *   10+mu LpsDw +(C[x,F phi] + C[Bx,phi] - C[Fx,phi] - C[x,B phi]);  14+mu LpsDwCv +(the four added);
+ * each projected with sum_x e^{-2 pi i n.x/L} (global coordinates, no source offset) onto the momenta of qudaAmdLoopMomenta. */
+/* the momentum list of the loops (createLoopMomenta, lib/qudaQKXTM_Kepler_utils.cpp:255-298; NOT the two-point list): pz outermost,
+ * px innermost, every component 0 .. L/2-1, -L/2 .. -1 over the GLOBAL extent L, kept where |n|^2 <= Q_sq.  Host only; returns
+ * Nmoms and, if moms is not NULL, fills moms[Nmoms][3] (max_moms entries available) */
+int qudaAmdLoopMomenta(const int L[3], int Q_sq, int *moms, int max_moms);
+/* h_solution: V*24 doubles, LOCAL lattice, lexicographic UKQCD (the layout the solution sink receives), NOT rescaled by 2 kappa;
+ * param: dslash_type (twisted mass or twisted clover; anything else is an error) and kappa are read; the resident precise links
+ * (and clover term) must be fp64.  out[18][T global][Nmoms][16][re, im]: raw sums of this one vector (no factor 0.25); every rank
+ * receives the full result.  QUDA_AMD_LOOP_FUSED=0 in the environment selects the unfused chain of covariant shifts and pairwise
+ * contractions in the reference's call order instead of the fused stencil kernel. */
+void qudaAmdContractLoop(double *out, const void *h_solution, QudaInvertParam *param, int Q_sq);
+/* off by default.  On: calcMG_loop_wOneD_TSM_EvenOdd contracts every solution from the device-resident field, accumulates over the
+ * noise vectors in momentum space (momenta info.Q_sq) and rank 0 writes the reference's ASCII files at every dump (writeLoops_ASCII:
+ * <loop_fname>_stoch_MG_<type>.loop.<NNNN>.<nT>_<r>, under the truncated solver method <loop_fname>_stoch_TSM_MG_NLP<NNNN>_<type>.loop.<nT>_<r>
+ * and the _HighPrec / _LowPrec pair of the bias run); the solution sink is still called as before.  loopInfo.HighMomForm needs HDF5
+ * and is an error; FileFormat = HDF5_FORM warns and writes ASCII. */
+void qudaAmdSetLoopOutput(int enable);
+/* seconds of the last loop contraction on this rank (device events): phi, stencil (or the unfused chain), projection, all of it */
+void qudaAmdLoopLastTimings(double secs[4]);
+
 /* ILDG gauge configurations in LIME containers (the step in front of loadGaugeQuda in the QKXTM drivers).  qudaAmdReadLimeGauge
  * has the semantics of readLimeGauge / readLimeGaugeSmeared (qkxtm/QKXTM_read_conf.h:107-400, :819-835): every rank reads the
  * sub-block of its grid coordinates from the "ildg-binary-data" record into the even-odd QDP arrays gauge[4] (fp64, allocated

@@ -119,7 +119,8 @@ EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLo
                  "qudaAmdMultigridVerify", "qudaAmdMultigridCycle", "qudaAmdTimeAxpy", "qudaAmdMultigridLevels", "qudaAmdMultigridLevelInfo",
                  "qudaAmdMultigridSetHalfStorage", "qudaAmdMultigridGetNullVector", "qudaAmdMultigridGetV", "qudaAmdMultigridGetCoarseLinks", "qudaAmdMultigridApply", "qudaAmdMultigridApplyBlock",
                  "qudaAmdMultigridTimeApply", "qudaAmdMultigridTimeTransfer", "qudaAmdSetExitLine", "qudaAmdDiracPrepare", "qudaAmdDiracReconstruct", "qudaAmdSpinorRawInfo", "qudaAmdGaugeRawInfo", "qudaAmdCloverRawInfo", "qudaAmdRawDeviceCopy",
-                 "qudaAmdSetSolutionSink", "qudaAmdCommStats", "qudaAmdDescribeHaloError", "qudaAmdMultigridOrthoFallbackBlocks", "qudaAmdProfileMarker", "qudaAmdAccountStart", "qudaAmdAccountDump", "qudaAmdWriteSpinorFields", "qudaAmdReadSpinorFields", "qudaAmdMultigridRefine", "qudaAmdMultigridSetFused", "qudaAmdMultigridFusedStats", "qudaAmdMultiSrcStats", "qudaAmdTwopMomenta", "qudaAmdTwopTimeExtent", "qudaAmdContractTwop", "qudaAmdSetTwopOutput"]
+                 "qudaAmdSetSolutionSink", "qudaAmdCommStats", "qudaAmdDescribeHaloError", "qudaAmdMultigridOrthoFallbackBlocks", "qudaAmdProfileMarker", "qudaAmdAccountStart", "qudaAmdAccountDump", "qudaAmdWriteSpinorFields", "qudaAmdReadSpinorFields", "qudaAmdMultigridRefine", "qudaAmdMultigridSetFused", "qudaAmdMultigridFusedStats", "qudaAmdMultiSrcStats", "qudaAmdTwopMomenta", "qudaAmdTwopTimeExtent", "qudaAmdContractTwop", "qudaAmdSetTwopOutput",
+                 "qudaAmdLoopMomenta", "qudaAmdContractLoop", "qudaAmdSetLoopOutput", "qudaAmdLoopLastTimings"]
 
 _lib = None
 
@@ -244,6 +245,14 @@ def lib():
         L.qudaAmdContractTwop.restype = None
         L.qudaAmdSetTwopOutput.argtypes = [_i]
         L.qudaAmdSetTwopOutput.restype = None
+        L.qudaAmdLoopMomenta.argtypes = [C.POINTER(_i), _i, C.POINTER(_i), _i]
+        L.qudaAmdLoopMomenta.restype = _i
+        L.qudaAmdContractLoop.argtypes = [_p, _p, C.POINTER(QudaInvertParam), _i]
+        L.qudaAmdContractLoop.restype = None
+        L.qudaAmdSetLoopOutput.argtypes = [_i]
+        L.qudaAmdSetLoopOutput.restype = None
+        L.qudaAmdLoopLastTimings.argtypes = [C.POINTER(_d)]
+        L.qudaAmdLoopLastTimings.restype = None
         _lib = L
     return _lib
 
@@ -507,6 +516,40 @@ def contract_twop(prop_up, prop_dn, gauge_lex, source_position, Q_sq, nsmear, al
 def set_twop_output(enable):
     """qudaAmdSetTwopOutput: calcMG_threepTwop_EvenOdd writes the two-point ASCII files"""
     lib().qudaAmdSetTwopOutput(int(bool(enable)))
+
+
+def loop_momenta(L, Q_sq):
+    """qudaAmdLoopMomenta: the momenta |n|^2 <= Q_sq of the quark loops on a lattice of GLOBAL spatial extents L as an (Nmoms, 3) int
+    array, in the reference's order (pz outermost, px innermost, components 0 .. L/2-1, -L/2 .. -1); host only"""
+    ext = (_i * 3)(*[int(v) for v in L])
+    n = lib().qudaAmdLoopMomenta(ext, int(Q_sq), None, 0)
+    out = np.zeros((n, 3), dtype=np.int32)
+    lib().qudaAmdLoopMomenta(ext, int(Q_sq), out.ctypes.data_as(C.POINTER(_i)), n)
+    return out
+
+
+def contract_loop(solution, ip, Q_sq, L):
+    """qudaAmdContractLoop on ONE solution vector ((V*24,) lexicographic UKQCD, local lattice, not rescaled): the 18 blocks
+    (Scalar, dOp, Loops[4], LoopsCv[4], LpsDw[4], LpsDwCv[4]) as a complex128 array (18, T, Nmoms, 16), T global, raw sums.
+    L: the GLOBAL spatial extents (Lx, Ly, Lz) of the resident lattice (they fix the momentum list)"""
+    sol = np.ascontiguousarray(solution, dtype=np.float64)
+    nm = len(loop_momenta(L, Q_sq))
+    T = lib().qudaAmdTwopTimeExtent()
+    out = np.zeros((18, T, nm, 16, 2))
+    lib().qudaAmdContractLoop(_vp(out), _vp(sol), C.byref(ip), int(Q_sq))
+    return out[..., 0] + 1j * out[..., 1]
+
+
+def set_loop_output(enable):
+    """qudaAmdSetLoopOutput: calcMG_loop_wOneD_TSM_EvenOdd contracts its solutions and writes the loop ASCII files"""
+    lib().qudaAmdSetLoopOutput(int(bool(enable)))
+
+
+def loop_last_timings():
+    """qudaAmdLoopLastTimings: seconds of the last loop contraction: dict(phi, stencil, projection, total)"""
+    a = (_d * 4)()
+    lib().qudaAmdLoopLastTimings(a)
+    return dict(phi=a[0], stencil=a[1], projection=a[2], total=a[3])
 
 
 class Spinor:

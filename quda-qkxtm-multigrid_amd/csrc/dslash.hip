@@ -2567,6 +2567,29 @@ void applyShift(double *out, const double *in, const LatticeGeom &g, int stride,
   HIP_CHECK(hipGetLastError());
 }
 
+// the ghost zone a hop in direction `dir` to the sites of parity `parity` reads, copied into a buffer of the caller (faceCB[mu] x 24
+// doubles, planar with stride faceCB[mu], face index as in hop_dir_kernel): `in` is the other parity's block of a 24-real fp64 planar
+// field.  For kernels that need several ghost zones at once (the fused loop contraction, loop.hip).
+void exchangeFullFace(void *ghostOut, const double *in, const LatticeGeom &g, int stride, int parity, int dir) {
+  const int mu = dir >> 1;
+  if (!commGrid().partitioned(mu)) errorQuda("exchangeFullFace: dimension %d is not partitioned", mu);
+  const size_t bytes = (size_t)g.faceCB[mu] * 24 * sizeof(double);
+  if (bytes > g_ffBytes) {
+    freeFullFaceBuffers();
+    HIP_CHECK(qaMalloc((void **)&g_ffSend, bytes));
+    HIP_CHECK(qaMalloc((void **)&g_ffGhost, bytes));
+    g_ffBytes = bytes;
+  }
+  const bool fwd = !(dir & 1);
+  hipLaunchKernelGGL((face_full_pack_kernel<double>), dim3((g.faceCB[mu] + 255) / 256), dim3(256), 0, computeStream(), (void *)g_ffSend, (const void *)in,
+                     (const float *)nullptr, stride, g.X[0], g.X[1], g.X[2], g.X[3], mu, fwd ? 0 : g.X[mu] - 1, 1 - parity, g.faceCB[mu]);
+  HIP_CHECK(hipGetLastError());
+  std::vector<HaloMsg> msgs;
+  msgs.push_back({mu, fwd ? -1 : +1, g_ffSend, g_ffGhost, bytes});
+  commExchange(msgs, computeStream());
+  HIP_CHECK(hipMemcpyAsync(ghostOut, g_ffGhost, bytes, hipMemcpyDeviceToDevice, computeStream()));
+}
+
 template <typename T> static void launchSite(ColorSpinorField &out, const ColorSpinorField &in, SiteOp op, double a, double b,
                                              const CloverField *cl, int parity, bool inverse) {
   using real = typename Store<T>::real;

@@ -1,0 +1,669 @@
+// loop.hip — disconnected quark loops of the QKXTM drivers on the device: the one-end-trick contractions with one covariant
+// derivative of a solution vector, momentum projection per time slice, accumulation over the noise vectors in momentum space, the
+// sum over ranks and the reference's ASCII writer.
+//
+// Reference: oneEndTrick_w_One_Der (lib/qudaQKXTM_Loops_Kepler.cpp:300-497), contractGamma5Kernel
+// (lib/dslash_core/contract_core.h:65-336), CovD::M (lib/covDev.cu), performFFT / createLoopMomenta
+// (lib/qudaQKXTM_Kepler_utils.cpp:255-357), writeLoops_ASCII (lib/qudaQKXTM_Loops_Kepler.cpp:501-575).
+//
+// With x the solution as the solver leaves it, phi = g5 D_W x (the kappa-normalised Wilson or Wilson-clover operator, mu = 0),
+// F_mu v(x) = U_mu(x) v(x + mu), B_mu v(x) = U_mu(x - mu)^+ v(x - mu) and the open-spin, colour-traced building block
+//      C[u, v][4a + b] = sum_c conj(u[(a + 2) mod 4, c]) v[b, c]          (UKQCD basis: (u^+ g5)_a v_b)
+// every vector adds, per site, 18 blocks of 16 complex numbers:
+//      k = 0      Scalar   -= C[x, x]                      k = 1       dOp     += C[x, phi]
+//      k = 2 + mu Loops    -= C[x, (F - B) x] - C[(F - B) x, x]
+//      k = 6 + mu LoopsCv  -= C[x, (F + B) x] + C[(F + B) x, x]
+//      k = 10 + mu LpsDw   += C[x, (F - B) phi] - C[(F - B) x, phi]
+//      k = 14 + mu LpsDwCv += C[x, (F + B) phi] + C[(F + B) x, phi]
+// (the reference's four terms per block, folded with the linearity of C in each argument).
+//
+// Fused path (default): ONE stencil kernel forms D x = (F -+ B) x and D phi in registers and writes the blocks of a chunk of time
+// slices, cs[k][site][16]; eight threads share a site (direction mu x sign of B), each writes two blocks (and one of the two
+// ultra-local ones).  The staged blocks are projected onto the momenta with a fixed number of partial sums in a fixed order and
+// added to the accumulator [18][T_local][Nmoms][16], which lives in momentum space: there is no position-space accumulator.
+// QUDA_AMD_LOOP_FUSED=0: the reference's chain of single-direction covariant shifts (applyCovariantShift) and pairwise
+// contractions in its call order, the in-library cross-check.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "basis.h"
+#include "blas.h"
+#include "comm_quda.h"
+#include "device_io.h"
+#include "interface_internal.h"
+#include "p2p.h"
+#include "qa_core.h"
+#include "quda_amd_ext.h"
+
+namespace quda {
+
+void lexToDevice(ColorSpinorField &dst, const double *h_lex, const LatticeGeom &g, bool ukqcd);   // qkxtm.hip
+
+namespace loop {
+
+constexpr int NBLK = 18, NGM = 16;
+constexpr int NPART = 64;   // partial sums per (block, time slice, momentum): fixed, whatever the lattice or the launch
+constexpr int NLANE = 16;   // site lanes of a partial sum, reduced in order
+constexpr int MB_SMALL = 8, MB_LARGE = 36;   // momenta per projection block: 36 holds Q_sq <= 4 (33 momenta) in one pass over the staged blocks
+
+struct LoopArg {
+  const double *x[2], *phi[2];   // parity blocks of the two fields (12 double2 planes of stride sp_stride), device basis
+  int sp_stride;
+  const char *gauge[2];          // parityBase of the links
+  size_t link_bytes;
+  int g_stride;
+  int X0, Y, Z, T;               // local extents
+  int t0;                        // first time slice of the chunk
+  long S;                        // sites of the chunk
+  double tsign_fwd, tsign_bwd;   // boundary sign where the links do not carry it
+  const double *ghost[2][2][8];  // [field][parity of the reading site][dir]: ghost zone of a partitioned direction, else nullptr
+  int faceCB[4];
+  double2 *cs;                   // [18][S][16]
+};
+
+// o[4a + b] = w1 C[u1, v1] + w2 C[u2, v2], spinors in the UKQCD basis as 24 reals
+__device__ __forceinline__ void block2(double2 *o, const double *u1, const double *v1, double w1, const double *u2, const double *v2, double w2) {
+#pragma unroll
+  for (int a = 0; a < 4; a++) {
+    const double *p = u1 + 6 * ((a + 2) & 3), *q = u2 + 6 * ((a + 2) & 3);
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      const double *r = v1 + 6 * b, *s = v2 + 6 * b;
+      double re1 = 0, im1 = 0, re2 = 0, im2 = 0;
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        re1 += p[2 * c] * r[2 * c] + p[2 * c + 1] * r[2 * c + 1];
+        im1 += p[2 * c] * r[2 * c + 1] - p[2 * c + 1] * r[2 * c];
+        re2 += q[2 * c] * s[2 * c] + q[2 * c + 1] * s[2 * c + 1];
+        im2 += q[2 * c] * s[2 * c + 1] - q[2 * c + 1] * s[2 * c];
+      }
+      o[4 * a + b] = make_double2(w1 * re1 + w2 * re2, w1 * im1 + w2 * im2);
+    }
+  }
+}
+__device__ __forceinline__ void block1(double2 *o, const double *u, const double *v, double w) {
+#pragma unroll
+  for (int a = 0; a < 4; a++) {
+    const double *p = u + 6 * ((a + 2) & 3);
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      const double *r = v + 6 * b;
+      double re = 0, im = 0;
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        re += p[2 * c] * r[2 * c] + p[2 * c + 1] * r[2 * c + 1];
+        im += p[2 * c] * r[2 * c + 1] - p[2 * c + 1] * r[2 * c];
+      }
+      o[4 * a + b] = make_double2(w * re, w * im);
+    }
+  }
+}
+
+__device__ __forceinline__ void load_site(double *psi, const double *blk, int stride, int idx, const double *ghost, int faceCB, int face, bool cross) {
+  if (ghost && cross) Planar<double, 24>::load(psi, ghost, faceCB, face, nullptr, face);
+  else Planar<double, 24>::load(psi, blk, stride, idx, nullptr, idx);
+}
+
+// ---- the fused stencil: 32 sites x 8 (mu, sign) tasks per work-group ----
+template <int R> __global__ void __launch_bounds__(256) loop_fused_kernel(const LoopArg a) {
+  const int lane = threadIdx.x & 31, j = threadIdx.x >> 5;
+  const long s = (long)blockIdx.x * 32 + lane;
+  if (s >= a.S) return;
+  const int X0 = a.X0, Y = a.Y, Z = a.Z, T = a.T;
+  long l = s;
+  const int xc = (int)(l % X0); l /= X0;
+  const int y = (int)(l % Y); l /= Y;
+  const int z = (int)(l % Z);
+  const int t = a.t0 + (int)(l / Z);
+  const int parity = (xc + y + z + t) & 1;
+  const int idx = (((t * Z + z) * Y + y) * X0 + xc) >> 1;
+  const int mu = j >> 1;
+  const double sg = (j & 1) ? 1.0 : -1.0;   // D = F + sg B
+
+  int xf = xc, yf = y, zf = z, tf = t, xb = xc, yb = y, zb = z, tb = t, face;
+  bool crossF, crossB;
+  double signF = 1.0, signB = 1.0;
+  switch (mu) {
+    case 0: crossF = xc == X0 - 1; crossB = xc == 0; xf = crossF ? 0 : xc + 1; xb = crossB ? X0 - 1 : xc - 1; face = (y + Y * (z + Z * t)) >> 1; break;
+    case 1: crossF = y == Y - 1; crossB = y == 0; yf = crossF ? 0 : y + 1; yb = crossB ? Y - 1 : y - 1; face = (xc + X0 * (z + Z * t)) >> 1; break;
+    case 2: crossF = z == Z - 1; crossB = z == 0; zf = crossF ? 0 : z + 1; zb = crossB ? Z - 1 : z - 1; face = (xc + X0 * (y + Y * t)) >> 1; break;
+    default:
+      crossF = t == T - 1; crossB = t == 0; tf = crossF ? 0 : t + 1; tb = crossB ? T - 1 : t - 1; face = (xc + X0 * (y + Y * z)) >> 1;
+      if (crossF) signF = a.tsign_fwd;
+      if (crossB) signB = a.tsign_bwd;
+      break;
+  }
+  const int idxF = (((tf * Z + zf) * Y + yf) * X0 + xf) >> 1, idxB = (((tb * Z + zb) * Y + yb) * X0 + xb) >> 1;
+  const int op = 1 - parity;
+  const double *gxF = a.ghost[0][parity][2 * mu], *gxB = a.ghost[0][parity][2 * mu + 1];
+  const double *gpF = a.ghost[1][parity][2 * mu], *gpB = a.ghost[1][parity][2 * mu + 1];
+  const int fcb = a.faceCB[mu];
+
+  double Dx[24], Dp[24];
+  {
+    double U[18], psi[24], v[24];
+    Link<double, R>::load(U, a.gauge[parity] + (size_t)(2 * mu) * a.link_bytes, a.g_stride, idx, signF);
+    load_site(psi, a.x[op], a.sp_stride, idxF, gxF, fcb, face, crossF);
+#pragma unroll
+    for (int sp = 0; sp < 4; sp++) su3_mv(Dx + 6 * sp, U, psi + 6 * sp);
+    load_site(psi, a.phi[op], a.sp_stride, idxF, gpF, fcb, face, crossF);
+#pragma unroll
+    for (int sp = 0; sp < 4; sp++) su3_mv(Dp + 6 * sp, U, psi + 6 * sp);
+    Link<double, R>::load(U, a.gauge[parity] + (size_t)(2 * mu + 1) * a.link_bytes, a.g_stride, idx, signB);
+    load_site(psi, a.x[op], a.sp_stride, idxB, gxB, fcb, face, crossB);
+#pragma unroll
+    for (int sp = 0; sp < 4; sp++) su3_mv(v + 6 * sp, U, psi + 6 * sp);
+#pragma unroll
+    for (int k = 0; k < 24; k++) psi[k] = Dx[k] + sg * v[k];
+    rotate_basis(Dx, psi, BASIS_DR_TO_UKQCD);
+    load_site(psi, a.phi[op], a.sp_stride, idxB, gpB, fcb, face, crossB);
+#pragma unroll
+    for (int sp = 0; sp < 4; sp++) su3_mv(v + 6 * sp, U, psi + 6 * sp);
+#pragma unroll
+    for (int k = 0; k < 24; k++) psi[k] = Dp[k] + sg * v[k];
+    rotate_basis(Dp, psi, BASIS_DR_TO_UKQCD);
+  }
+  double x[24], ph[24];
+  {
+    double r[24];
+    Planar<double, 24>::load(r, a.x[parity], a.sp_stride, idx, nullptr, idx);
+    rotate_basis(x, r, BASIS_DR_TO_UKQCD);
+    Planar<double, 24>::load(r, a.phi[parity], a.sp_stride, idx, nullptr, idx);
+    rotate_basis(ph, r, BASIS_DR_TO_UKQCD);
+  }
+  const int kstd = ((j & 1) ? 6 : 2) + mu;
+  block2(a.cs + ((long)kstd * a.S + s) * NGM, x, Dx, -1.0, Dx, x, -sg);
+  block2(a.cs + ((long)(kstd + 8) * a.S + s) * NGM, x, Dp, 1.0, Dx, ph, sg);
+  if (j == 0) block1(a.cs + s * NGM, x, x, -1.0);
+  if (j == 1) block1(a.cs + ((long)a.S + s) * NGM, x, ph, 1.0);
+}
+
+// ---- the unfused chain: cs[k][site] (=, +=) w C[u, v] for full device fields u, v ----
+__global__ void __launch_bounds__(256) pair_contract_kernel(double2 *cs, long S, int k, const double *u0, const double *u1, const double *v0, const double *v1, int stride,
+                                                            int X0, int Y, int Z, int t0, double w, int accumulate) {
+  const long s = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+  long l = s;
+  const int xc = (int)(l % X0); l /= X0;
+  const int y = (int)(l % Y); l /= Y;
+  const int z = (int)(l % Z);
+  const int t = t0 + (int)(l / Z);
+  const int parity = (xc + y + z + t) & 1;
+  const int idx = (((t * Z + z) * Y + y) * X0 + xc) >> 1;
+  double r[24], u[24], v[24];
+  Planar<double, 24>::load(r, parity ? u1 : u0, stride, idx, nullptr, idx);
+  rotate_basis(u, r, BASIS_DR_TO_UKQCD);
+  Planar<double, 24>::load(r, parity ? v1 : v0, stride, idx, nullptr, idx);
+  rotate_basis(v, r, BASIS_DR_TO_UKQCD);
+  double2 o[NGM];
+  block1(o, u, v, w);
+  double2 *dst = cs + ((long)k * S + s) * NGM;
+#pragma unroll
+  for (int i = 0; i < NGM; i++) {
+    if (accumulate) { const double2 c = dst[i]; o[i].x += c.x; o[i].y += c.y; }
+    dst[i] = o[i];
+  }
+}
+
+// g5 in the device (DeGrand-Rossi) basis: diag(1, 1, -1, -1)
+__global__ void __launch_bounds__(256) gamma5_kernel(double *v, int stride, int Vh) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= Vh) return;
+  double2 *p = (double2 *)v;
+#pragma unroll
+  for (int k = 6; k < 12; k++) {
+    double2 c = p[(size_t)k * stride + idx];
+    p[(size_t)k * stride + idx] = make_double2(-c.x, -c.y);
+  }
+}
+
+// ---- momentum projection of the staged blocks ----
+// part[(((k * nt + tl) * NPART + p) * Nm + m) * 16 + gm] = sum over the p-th fixed share of the slice's sites of e^{-2 pi i n.x / L} cs[k][tl, site][gm],
+// x the GLOBAL coordinate.  One phase per (site, momentum) serves the 16 entries of a block; it is the product of three factors from
+// per-direction tables in LDS.  A share is summed by NLANE site lanes (sites s0 + lane, s0 + lane + NLANE, ...), then the lanes in order.
+template <int MB> __global__ void __launch_bounds__(256) loop_project_kernel(double2 *part, const double2 *cs, long S, int Vs, int nt, const int *moms, int Nm, int nmb, int X0, int Y, int Z,
+                                                           int gx0, int gx1, int gx2, int L0, int L1, int L2) {
+  extern __shared__ double2 lds[];
+  double2 *ex = lds, *ey = ex + MB * X0, *ez = ey + MB * Y, *red = ez + MB * Z;
+  // the momentum chunks of one share are neighbours in the launch order: they read the same staged data at the same time
+  const int p = blockIdx.x / nmb, tl = blockIdx.y, k = blockIdx.z, m0 = (blockIdx.x % nmb) * MB;
+  const int nm = min(MB, Nm - m0);
+  for (int i = threadIdx.x; i < MB * (X0 + Y + Z); i += blockDim.x) {
+    int m, c, L, n, gc;
+    if (i < MB * X0) { m = i / X0; c = i % X0; L = L0; gc = c + gx0; n = m < nm ? moms[3 * (m0 + m)] : 0; }
+    else if (i < MB * (X0 + Y)) { const int q = i - MB * X0; m = q / Y; c = q % Y; L = L1; gc = c + gx1; n = m < nm ? moms[3 * (m0 + m) + 1] : 0; }
+    else { const int q = i - MB * (X0 + Y); m = q / Z; c = q % Z; L = L2; gc = c + gx2; n = m < nm ? moms[3 * (m0 + m) + 2] : 0; }
+    const long kk = (((long)n * gc) % L + L) % L;   // reduced mod L so the phase argument stays small
+    double sn, cn;
+    sincos(2.0 * M_PI * (double)kk / L, &sn, &cn);
+    lds[i] = make_double2(cn, -sn);
+  }
+  __syncthreads();
+  const int gm = threadIdx.x & 15, sl = threadIdx.x >> 4;
+  const long s0 = (long)Vs * p / NPART, s1 = (long)Vs * (p + 1) / NPART;
+  double2 acc[MB];
+#pragma unroll
+  for (int m = 0; m < MB; m++) acc[m] = make_double2(0, 0);
+  const double2 *src = cs + ((long)k * S + (long)tl * Vs) * NGM + gm;
+  for (long s = s0 + sl; s < s1; s += NLANE) {
+    const int x = (int)(s % X0), y = (int)((s / X0) % Y), z = (int)(s / ((long)X0 * Y));
+    const double2 c = src[s * NGM];
+#pragma unroll
+    for (int m = 0; m < MB; m++) {
+      const double2 a = ex[m * X0 + x], b = ey[m * Y + y], d = ez[m * Z + z];
+      const double2 ab = make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+      const double2 ph = make_double2(ab.x * d.x - ab.y * d.y, ab.x * d.y + ab.y * d.x);
+      acc[m].x += c.x * ph.x - c.y * ph.y;
+      acc[m].y += c.x * ph.y + c.y * ph.x;
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < MB; m++) {
+    red[threadIdx.x] = acc[m];
+    __syncthreads();
+    if (sl == 0 && m < nm) {
+      double2 r = red[gm];
+      for (int q = 1; q < NLANE; q++) { r.x += red[q * 16 + gm].x; r.y += red[q * 16 + gm].y; }
+      part[((((long)k * nt + tl) * NPART + p) * Nm + m0 + m) * NGM + gm] = r;
+    }
+    __syncthreads();
+  }
+}
+
+// acc[((k * Lt + t0 + tl) * Nm + m) * 16 + gm] += sum_p part[...], p = 0 .. NPART-1 in order
+__global__ void __launch_bounds__(256) loop_reduce_kernel(double2 *acc, const double2 *part, int nt, int Lt, int t0, int Nm) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long per = (long)Nm * NGM;
+  if (i >= (long)NBLK * nt * per) return;
+  const int k = (int)(i / (nt * per)), tl = (int)((i / per) % nt);
+  const long r = i % per;
+  double2 sum = make_double2(0, 0);
+  for (int p = 0; p < NPART; p++) {
+    const double2 c = part[(((long)k * nt + tl) * NPART + p) * per + r];
+    sum.x += c.x; sum.y += c.y;
+  }
+  double2 *dst = acc + ((long)k * Lt + t0 + tl) * per + r;
+  const double2 old = *dst;
+  *dst = make_double2(old.x + sum.x, old.y + sum.y);
+}
+
+}  // namespace loop
+
+// momenta of the loops (createLoopMomenta): pz outermost, py, px innermost, each component 0 .. L/2-1, -L/2 .. -1 over the GLOBAL extent
+std::vector<int> loopMomenta(const int L[3], int Q_sq) {
+  std::vector<int> m;
+  for (int pz = 0; pz < L[2]; pz++)
+    for (int py = 0; py < L[1]; py++)
+      for (int px = 0; px < L[0]; px++) {
+        const int n0 = px < L[0] / 2 ? px : px - L[0], n1 = py < L[1] / 2 ? py : py - L[1], n2 = pz < L[2] / 2 ? pz : pz - L[2];
+        if (n0 * n0 + n1 * n1 + n2 * n2 <= Q_sq) { m.push_back(n0); m.push_back(n1); m.push_back(n2); }
+      }
+  return m;
+}
+
+static void globalL(int L[3]) {
+  const LatticeGeom &g = residentGeom();
+  for (int d = 0; d < 3; d++) L[d] = g.X[d] * commGrid().dims[d];
+}
+
+// cumulative sums of the 18 blocks over the noise vectors, in momentum space, this rank's time slices
+struct LoopAccum {
+  double2 *d = nullptr;
+  int *d_moms = nullptr;
+  std::vector<int> moms;
+  int Nm = 0, Lt = 0, Q_sq = 0;
+  size_t n = 0;   // complex numbers
+};
+
+LoopAccum *loopAccumCreate(int Q_sq) {
+  if (Q_sq < 0) errorQuda("loop contraction: Q_sq = %d", Q_sq);
+  LoopAccum *A = new LoopAccum;
+  int L[3];
+  globalL(L);
+  A->moms = loopMomenta(L, Q_sq);
+  A->Nm = (int)A->moms.size() / 3;
+  A->Lt = residentGeom().X[3];
+  A->Q_sq = Q_sq;
+  A->n = (size_t)loop::NBLK * A->Lt * A->Nm * loop::NGM;
+  HIP_CHECK(hipMalloc(&A->d, A->n * sizeof(double2)));
+  HIP_CHECK(hipMalloc(&A->d_moms, A->moms.size() * sizeof(int)));
+  HIP_CHECK(hipMemcpyAsync(A->d_moms, A->moms.data(), A->moms.size() * sizeof(int), hipMemcpyHostToDevice, computeStream()));
+  HIP_CHECK(hipMemsetAsync(A->d, 0, A->n * sizeof(double2), computeStream()));
+  HIP_CHECK(hipStreamSynchronize(computeStream()));
+  return A;
+}
+void loopAccumZero(LoopAccum &A) { HIP_CHECK(hipMemsetAsync(A.d, 0, A.n * sizeof(double2), computeStream())); }
+void loopAccumDestroy(LoopAccum *A) {
+  if (!A) return;
+  (void)hipFree(A->d); (void)hipFree(A->d_moms);
+  delete A;
+}
+
+static size_t parityDoublesOf(const ColorSpinorField &f) { return (size_t)((const char *)f.Odd().V() - (const char *)f.Even().V()) / sizeof(double); }
+
+// read at every contraction, so one process can time both paths (tools/loop_timing.py)
+static bool fusedEnabled() {
+  const char *e = getenv("QUDA_AMD_LOOP_FUSED");
+  return e ? atoi(e) != 0 : true;
+}
+
+static double g_loopSecs[4] = {0, 0, 0, 0};   // phi, stencil / chain, projection, total of the last contraction
+
+// phi = g5 D_W x with the operator classes: Wilson (twisted mass) or Wilson-clover (twisted clover) at mu = 0, kappa-normalised
+static void makePhi(ColorSpinorField &phi, const ColorSpinorField &x, QudaInvertParam *param) {
+  DiracParam dp;
+  dp.matpcType = QUDA_MATPC_EVEN_EVEN;
+  dp.dagger = QUDA_DAG_NO;
+  dp.gauge = gaugePrecise;
+  dp.kappa = param->kappa;
+  dp.mass = 1.0 / (2.0 * param->kappa) - 4.0;
+  dp.mu = 0.0;
+  if (param->dslash_type == QUDA_TWISTED_CLOVER_DSLASH) {
+    if (!cloverPrecise) errorQuda("loop contraction: Clover field not allocated");
+    if (cloverPrecise->precision != QUDA_DOUBLE_PRECISION) errorQuda("loop contraction: the resident clover term must be fp64 (clover_cuda_prec)");
+    dp.type = QUDA_TWISTED_CLOVER_DIRAC;   // A + i mu g5 - kappa D at mu = 0: the Wilson-clover operator
+    dp.clover = cloverPrecise;
+  } else if (param->dslash_type == QUDA_TWISTED_MASS_DSLASH) {
+    dp.type = QUDA_WILSON_DIRAC;
+  } else {
+    errorQuda("loop contraction: the one-end trick works only for twisted-mass and twisted-clover fermions (dslash_type %d)", param->dslash_type);
+  }
+  Dirac *dW = Dirac::create(dp);
+  dW->M(phi, x);
+  delete dW;
+  const int Vh = residentGeom().Vh;
+  for (int parity = 0; parity < 2; parity++) {
+    ColorSpinorField &h = parity ? phi.Odd() : phi.Even();
+    hipLaunchKernelGGL(loop::gamma5_kernel, dim3((Vh + 255) / 256), dim3(256), 0, computeStream(), (double *)h.V(), h.Stride(), Vh);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+static void launchFused(const loop::LoopArg &arg, int recon) {
+  const dim3 grid((unsigned)((arg.S + 31) / 32)), block(256);
+  if (recon == 12) hipLaunchKernelGGL((loop::loop_fused_kernel<12>), grid, block, 0, computeStream(), arg);
+  else if (recon == 8) hipLaunchKernelGGL((loop::loop_fused_kernel<8>), grid, block, 0, computeStream(), arg);
+  else hipLaunchKernelGGL((loop::loop_fused_kernel<18>), grid, block, 0, computeStream(), arg);
+  HIP_CHECK(hipGetLastError());
+}
+
+// the reference's chain for the time slices [t0, t0 + nt): shifted fields are whole-lattice, made once per call (chunk 0) by the caller
+struct ChainFields { ColorSpinorField *Fx[4], *Bx[4], *Fp[4], *Bp[4]; };
+
+static void shiftFull(ColorSpinorField &out, const ColorSpinorField &in, int dir) {
+  applyCovariantShift(out.Even(), in.Odd(), *gaugePrecise, 0, dir, 1.0, nullptr, 0.0);
+  applyCovariantShift(out.Odd(), in.Even(), *gaugePrecise, 1, dir, 1.0, nullptr, 0.0);
+}
+
+static void chainChunk(double2 *cs, long S, int t0, const ColorSpinorField &x, const ColorSpinorField &phi, const ChainFields &F, const LatticeGeom &g) {
+  const int stride = x.Stride();
+  auto contract = [&](int k, const ColorSpinorField &u, const ColorSpinorField &v, double w, bool add) {
+    hipLaunchKernelGGL(loop::pair_contract_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, computeStream(), cs, S, k, (const double *)u.Even().V(),
+                       (const double *)u.Odd().V(), (const double *)v.Even().V(), (const double *)v.Odd().V(), stride, g.X[0], g.X[1], g.X[2], t0, w, add ? 1 : 0);
+    HIP_CHECK(hipGetLastError());
+  };
+  const size_t blk = (size_t)S * loop::NGM * sizeof(double2);
+  auto copyBlock = [&](int dst, int src) {
+    HIP_CHECK(hipMemcpyAsync(cs + (size_t)dst * S * loop::NGM, cs + (size_t)src * S * loop::NGM, blk, hipMemcpyDeviceToDevice, computeStream()));
+  };
+  // LOCAL (:366-390)
+  contract(1, x, phi, 1.0, false);
+  contract(0, x, x, -1.0, false);
+  // generalised one-end trick (:397-444): S = term0 + term3 - term2 - term1 -> k = 10 + mu, C = the sum of the four -> k = 14 + mu
+  for (int mu = 0; mu < 4; mu++) {
+    const int kS = 10 + mu, kC = 14 + mu;
+    contract(kS, x, *F.Fp[mu], 1.0, false);
+    contract(kS, *F.Bx[mu], phi, 1.0, true);
+    copyBlock(kC, kS);
+    contract(kC, *F.Fx[mu], phi, 1.0, true);
+    contract(kS, *F.Fx[mu], phi, -1.0, true);
+    contract(kC, x, *F.Bp[mu], 1.0, true);
+    contract(kS, x, *F.Bp[mu], -1.0, true);
+  }
+  // standard one-end trick (:446-490), subtracted from the accumulators: every weight negated
+  for (int mu = 0; mu < 4; mu++) {
+    const int kS = 2 + mu, kC = 6 + mu;
+    contract(kS, x, *F.Fx[mu], -1.0, false);
+    contract(kS, *F.Bx[mu], x, -1.0, true);
+    copyBlock(kC, kS);
+    contract(kC, *F.Fx[mu], x, -1.0, true);
+    contract(kS, *F.Fx[mu], x, 1.0, true);
+    contract(kC, x, *F.Bx[mu], -1.0, true);
+    contract(kS, x, *F.Bx[mu], 1.0, true);
+  }
+}
+
+// A += the 18 blocks of the vector x (full fp64 device field as the solver leaves it), projected onto A's momenta
+void loopContractAdd(LoopAccum &A, ColorSpinorField &x, QudaInvertParam *param) {
+  using namespace loop;
+  if (!gaugePrecise) errorQuda("loop contraction: Gauge field not allocated");
+  if (x.Location() != QUDA_CUDA_FIELD_LOCATION || x.Precision() != QUDA_DOUBLE_PRECISION || x.SiteSubset() != QUDA_FULL_SITE_SUBSET || x.Nspin() != 4 || x.Ncolor() != 3)
+    errorQuda("loop contraction: expected a full fp64 device spinor");
+  if (gaugePrecise->precision != QUDA_DOUBLE_PRECISION) errorQuda("loop contraction: the resident precise links must be fp64 (cuda_prec of the gauge field)");
+  const LatticeGeom &g = residentGeom();
+  const CommGrid &cg = commGrid();
+  if (A.Lt != g.X[3]) errorQuda("loop contraction: the accumulator belongs to another lattice");
+  hipStream_t st = computeStream();
+  hipEvent_t ev[2];
+  for (int i = 0; i < 2; i++) HIP_CHECK(hipEventCreate(&ev[i]));
+  std::vector<hipEvent_t> marks;   // per chunk: before the stencil, after it, after the projection
+  auto mark = [&]() { hipEvent_t e; HIP_CHECK(hipEventCreate(&e)); HIP_CHECK(hipEventRecord(e, st)); marks.push_back(e); };
+  HIP_CHECK(hipEventRecord(ev[0], st));
+
+  if (x.TwistFlavor() != QUDA_TWIST_PLUS && x.TwistFlavor() != QUDA_TWIST_MINUS) x.changeTwist(QUDA_TWIST_PLUS);   // mu = 0: the flavour does not enter
+  ColorSpinorField phi(x);
+  makePhi(phi, x, param);
+  HIP_CHECK(hipEventRecord(ev[1], st));
+
+  const int Vs = g.X[0] * g.X[1] * g.X[2], Lt = g.X[3], Nm = A.Nm;
+  // time slices per chunk: the staged blocks stay below 2 GiB
+  const size_t perSlice = (size_t)Vs * NBLK * NGM * sizeof(double2);
+  int tc = (int)std::max<size_t>(1, std::min<size_t>((size_t)Lt, ((size_t)2 << 30) / perSlice));
+  {
+    static int env = -1;   // measurement aid: time slices per chunk
+    if (env < 0) { const char *e = getenv("QUDA_AMD_LOOP_TCHUNK"); env = e ? atoi(e) : 0; }
+    if (env > 0) tc = std::min(env, Lt);
+  }
+  double2 *cs = nullptr, *part = nullptr;
+  HIP_CHECK(hipMalloc(&cs, perSlice * tc));
+  HIP_CHECK(hipMalloc(&part, (size_t)NBLK * tc * NPART * Nm * NGM * sizeof(double2)));
+
+  const bool fused = fusedEnabled();
+  LoopArg arg;
+  memset(&arg, 0, sizeof(arg));
+  std::vector<void *> ghosts;
+  ChainFields F;
+  memset(&F, 0, sizeof(F));
+  if (fused) {
+    arg.x[0] = (const double *)x.Even().V(); arg.x[1] = (const double *)x.Odd().V();
+    arg.phi[0] = (const double *)phi.Even().V(); arg.phi[1] = (const double *)phi.Odd().V();
+    arg.sp_stride = x.Stride();
+    if (phi.Stride() != x.Stride()) errorQuda("loop contraction: stride mismatch");
+    arg.gauge[0] = (const char *)gaugePrecise->parityBase(0); arg.gauge[1] = (const char *)gaugePrecise->parityBase(1);
+    arg.link_bytes = gaugePrecise->link_bytes; arg.g_stride = gaugePrecise->stride;
+    arg.X0 = g.X[0]; arg.Y = g.X[1]; arg.Z = g.X[2]; arg.T = g.X[3];
+    const bool anti = gaugePrecise->reconstruct != QUDA_RECONSTRUCT_NO && gaugePrecise->t_boundary == QUDA_ANTI_PERIODIC_T;
+    arg.tsign_fwd = (anti && cg.coords[3] == cg.dims[3] - 1) ? -1.0 : 1.0;
+    arg.tsign_bwd = (anti && cg.coords[3] == 0) ? -1.0 : 1.0;
+    for (int mu = 0; mu < 4; mu++) {
+      arg.faceCB[mu] = g.faceCB[mu];
+      if (!cg.partitioned(mu)) continue;
+      for (int f = 0; f < 2; f++)
+        for (int parity = 0; parity < 2; parity++)
+          for (int d = 0; d < 2; d++) {
+            void *gh = nullptr;
+            HIP_CHECK(hipMalloc(&gh, (size_t)g.faceCB[mu] * 24 * sizeof(double)));
+            ghosts.push_back(gh);
+            const ColorSpinorField &fld = f ? phi : x;
+            const ColorSpinorField &other = parity ? fld.Even() : fld.Odd();
+            exchangeFullFace(gh, (const double *)other.V(), g, other.Stride(), parity, 2 * mu + d);
+            arg.ghost[f][parity][2 * mu + d] = (const double *)gh;
+          }
+    }
+    arg.cs = cs;
+  } else {
+    for (int mu = 0; mu < 4; mu++) {
+      F.Fx[mu] = new ColorSpinorField(x); F.Bx[mu] = new ColorSpinorField(x); F.Fp[mu] = new ColorSpinorField(x); F.Bp[mu] = new ColorSpinorField(x);
+      shiftFull(*F.Fx[mu], x, 2 * mu); shiftFull(*F.Bx[mu], x, 2 * mu + 1);
+      shiftFull(*F.Fp[mu], phi, 2 * mu); shiftFull(*F.Bp[mu], phi, 2 * mu + 1);
+    }
+  }
+  int gx[3], L[3];
+  for (int d = 0; d < 3; d++) { gx[d] = cg.coords[d] * g.X[d]; L[d] = g.X[d] * cg.dims[d]; }
+  // all momenta in one pass where the phase tables of MB_LARGE momenta fit into 64 KiB of LDS, else chunks of MB_SMALL
+  auto ldsOf = [&](int mb) { return ((size_t)mb * (g.X[0] + g.X[1] + g.X[2]) + 256) * sizeof(double2); };
+  const bool large = Nm > MB_SMALL && Nm <= MB_LARGE && ldsOf(MB_LARGE) <= 64 * 1024;
+  const int mbs = large ? MB_LARGE : MB_SMALL;
+  const int nmb = (Nm + mbs - 1) / mbs;
+  const size_t ldsBytes = ldsOf(mbs);
+  if (ldsBytes > 64 * 1024) errorQuda("loop contraction: spatial extents %d %d %d exceed the phase tables", g.X[0], g.X[1], g.X[2]);
+  for (int t0 = 0; t0 < Lt; t0 += tc) {
+    const int nt = std::min(tc, Lt - t0);
+    const long S = (long)nt * Vs;
+    mark();
+    if (fused) {
+      arg.t0 = t0; arg.S = S;
+      launchFused(arg, (int)gaugePrecise->reconstruct);
+    } else {
+      chainChunk(cs, S, t0, x, phi, F, g);
+    }
+    mark();
+    if (large)
+      hipLaunchKernelGGL((loop_project_kernel<MB_LARGE>), dim3(NPART * nmb, nt, NBLK), dim3(256), ldsBytes, st, part, cs, S, Vs, nt, A.d_moms, Nm, nmb, g.X[0], g.X[1], g.X[2],
+                         gx[0], gx[1], gx[2], L[0], L[1], L[2]);
+    else
+      hipLaunchKernelGGL((loop_project_kernel<MB_SMALL>), dim3(NPART * nmb, nt, NBLK), dim3(256), ldsBytes, st, part, cs, S, Vs, nt, A.d_moms, Nm, nmb, g.X[0], g.X[1], g.X[2],
+                         gx[0], gx[1], gx[2], L[0], L[1], L[2]);
+    const long nred = (long)NBLK * nt * Nm * NGM;
+    hipLaunchKernelGGL(loop_reduce_kernel, dim3((unsigned)((nred + 255) / 256)), dim3(256), 0, st, A.d, part, nt, Lt, t0, Nm);
+    HIP_CHECK(hipGetLastError());
+    mark();
+  }
+  HIP_CHECK(hipStreamSynchronize(st));
+  p2pCheck("loopContractAdd");
+  float ms = 0;
+  HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  g_loopSecs[0] = ms * 1e-3; g_loopSecs[1] = 0; g_loopSecs[2] = 0;
+  for (size_t i = 0; i + 2 < marks.size(); i += 3) {
+    HIP_CHECK(hipEventElapsedTime(&ms, marks[i], marks[i + 1])); g_loopSecs[1] += ms * 1e-3;
+    HIP_CHECK(hipEventElapsedTime(&ms, marks[i + 1], marks[i + 2])); g_loopSecs[2] += ms * 1e-3;
+  }
+  HIP_CHECK(hipEventElapsedTime(&ms, ev[0], marks.back()));
+  g_loopSecs[3] = ms * 1e-3;
+  if (!fused) g_loopSecs[1] = g_loopSecs[3] - g_loopSecs[0] - g_loopSecs[2];   // the covariant shifts of the chain run before the first chunk
+  for (hipEvent_t e : marks) (void)hipEventDestroy(e);
+  for (int i = 0; i < 2; i++) (void)hipEventDestroy(ev[i]);
+  for (void *gh : ghosts) (void)hipFree(gh);
+  for (int mu = 0; mu < 4; mu++) { delete F.Fx[mu]; delete F.Bx[mu]; delete F.Fp[mu]; delete F.Bp[mu]; }
+  (void)hipFree(cs); (void)hipFree(part);
+}
+
+// out[18][T global][Nmoms][16][re, im]: this rank's time slices at their global position, then one all-gather and the ranks added in
+// rank order, so every rank holds the same numbers
+void loopAccumGet(const LoopAccum &A, double *out) {
+  const CommGrid &cg = commGrid();
+  const int Lt = A.Lt, T = Lt * cg.dims[3];
+  const size_t per = (size_t)A.Nm * loop::NGM * 2;
+  std::vector<double> loc(A.n * 2);
+  HIP_CHECK(hipMemcpyAsync(loc.data(), A.d, loc.size() * sizeof(double), hipMemcpyDeviceToHost, computeStream()));
+  HIP_CHECK(hipStreamSynchronize(computeStream()));
+  const size_t total = (size_t)loop::NBLK * T * per;
+  std::vector<double> glob(total, 0.0);
+  for (int k = 0; k < loop::NBLK; k++)
+    memcpy(&glob[((size_t)k * T + (size_t)cg.coords[3] * Lt) * per], &loc[(size_t)k * Lt * per], (size_t)Lt * per * sizeof(double));
+  if (cg.size > 1) {
+    std::vector<double> all(total * cg.size);
+    commAllgatherBytes(glob.data(), all.data(), total * sizeof(double));
+    for (size_t i = 0; i < total; i++) {
+      double v = 0;
+      for (int r = 0; r < cg.size; r++) v += all[(size_t)r * total + i];
+      glob[i] = v;
+    }
+  }
+  memcpy(out, glob.data(), total * sizeof(double));
+}
+
+static const char *const loopTypeName[6] = {"Scalar", "dOp", "Loops", "LoopsCv", "LpsDw", "LpsDwCv"};
+static const bool loopTypeOneD[6] = {false, false, true, true, true, true};
+static const int loopTypeFirst[6] = {0, 1, 2, 6, 10, 14};
+
+// writeLoops_ASCII: one file per loop type and time rank r, holding that rank's time slices; rank 0 writes them all.
+// tsmTag = nullptr: <pref>_<type>.loop.<NNNN>.<nT>_<r>; "NLP" / "NHP": <pref>_<tag><NNNN>_<type>.loop.<nT>_<r>
+void loopWriteAscii(const LoopAccum &A, const char *pref, const char *tsmTag, int nnnn) {
+  const CommGrid &cg = commGrid();
+  const int Lt = A.Lt, nT = cg.dims[3], T = Lt * nT, Nm = A.Nm;
+  std::vector<double> glob((size_t)loop::NBLK * T * Nm * loop::NGM * 2);
+  loopAccumGet(A, glob.data());   // collective
+  if (cg.rank != 0) return;
+  for (int type = 0; type < 6; type++)
+    for (int r = 0; r < nT; r++) {
+      char name[1024];
+      if (tsmTag) snprintf(name, sizeof(name), "%s_%s%04d_%s.loop.%d_%d", pref, tsmTag, nnnn, loopTypeName[type], nT, r);
+      else snprintf(name, sizeof(name), "%s_%s.loop.%04d.%d_%d", pref, loopTypeName[type], nnnn, nT, r);
+      for (int mu = 0; mu < (loopTypeOneD[type] ? 4 : 1); mu++) {
+        FILE *f = fopen(name, mu == 0 ? "w" : "a");
+        if (!f) errorQuda("Cannot open %s to write the loop", name);
+        const int k = loopTypeFirst[type] + mu;
+        for (int ip = 0; ip < Nm; ip++)
+          for (int lt = 0; lt < Lt; lt++) {
+            const int t = lt + r * Lt;
+            for (int gm = 0; gm < 16; gm++) {
+              const double *v = &glob[((((size_t)k * T + t) * Nm + ip) * loop::NGM + gm) * 2];
+              if (loopTypeOneD[type])
+                fprintf(f, "%02d %02d %02d %+d %+d %+d %+16.15e %+16.15e\n", t, gm, mu, A.moms[3 * ip], A.moms[3 * ip + 1], A.moms[3 * ip + 2], 0.25 * v[0], 0.25 * v[1]);
+              else
+                fprintf(f, "%02d %02d %+d %+d %+d %+16.15e %+16.15e\n", t, gm, A.moms[3 * ip], A.moms[3 * ip + 1], A.moms[3 * ip + 2], v[0], v[1]);
+            }
+          }
+        fclose(f);
+      }
+    }
+}
+
+static bool g_loopOutput = false;
+bool loopOutputEnabled() { return g_loopOutput; }
+
+}  // namespace quda
+
+using namespace quda;
+
+extern "C" {
+
+int qudaAmdLoopMomenta(const int L[3], int Q_sq, int *moms, int max_moms) {
+  if (!L || L[0] < 1 || L[1] < 1 || L[2] < 1 || Q_sq < 0) errorQuda("qudaAmdLoopMomenta: bad extents or Q_sq = %d", Q_sq);
+  const std::vector<int> m = loopMomenta(L, Q_sq);
+  const int n = (int)m.size() / 3;
+  if (moms) {
+    if (max_moms < n) errorQuda("qudaAmdLoopMomenta: %d momenta do not fit into max_moms = %d", n, max_moms);
+    memcpy(moms, m.data(), m.size() * sizeof(int));
+  }
+  return n;
+}
+
+void qudaAmdSetLoopOutput(int enable) { g_loopOutput = enable != 0; }
+
+void qudaAmdContractLoop(double *out, const void *h_solution, QudaInvertParam *param, int Q_sq) {
+  if (!gaugePrecise) errorQuda("qudaAmdContractLoop: Gauge field not allocated");
+  if (!out || !h_solution || !param) errorQuda("qudaAmdContractLoop: NULL argument");
+  const LatticeGeom &g = residentGeom();
+  const QudaTwistFlavorType fl = (param->twist_flavor == QUDA_TWIST_MINUS) ? QUDA_TWIST_MINUS : QUDA_TWIST_PLUS;
+  ColorSpinorParam cp = deviceSpinorParam(QUDA_DOUBLE_PRECISION, QUDA_FULL_SITE_SUBSET, fl);
+  cp.create = QUDA_ZERO_FIELD_CREATE;
+  ColorSpinorField v(cp);
+  lexToDevice(v, (const double *)h_solution, g, true);
+  LoopAccum *A = loopAccumCreate(Q_sq);
+  loopContractAdd(*A, v, param);
+  loopAccumGet(*A, out);
+  loopAccumDestroy(A);
+}
+
+void qudaAmdLoopLastTimings(double secs[4]) {
+  for (int i = 0; i < 4; i++) secs[i] = g_loopSecs[i];
+}
+
+}  // extern "C"

@@ -17,6 +17,7 @@
 //    device basis happen in the copy kernels.
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "basis.h"
@@ -382,8 +383,19 @@ static void stochasticSource(double *h, size_t ncomplex, unsigned long seed, int
   }
 }
 
-// the loop of calcMG_loop_wOneD_TSM_EvenOdd (reference lib/interface_quda.cpp:8535-9230) without its contractions
-static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInfo, const qudaQKXTMinfo_Kepler &info, const char *fname) {
+// loop.hip
+struct LoopAccum;
+bool loopOutputEnabled();
+LoopAccum *loopAccumCreate(int Q_sq);
+void loopAccumZero(LoopAccum &A);
+void loopAccumDestroy(LoopAccum *A);
+void loopContractAdd(LoopAccum &A, ColorSpinorField &x, QudaInvertParam *param);
+void loopWriteAscii(const LoopAccum &A, const char *pref, const char *tsmTag, int nnnn);
+
+// the loop of calcMG_loop_wOneD_TSM_EvenOdd (reference lib/interface_quda.cpp:8535-9430).  writeLoops (the loop output switched on,
+// qudaAmdSetLoopOutput): every solution is contracted from the device-resident field after the reconstruction (loop.hip), the sums
+// over the noise vectors are cumulative and a snapshot goes to the reference's ASCII files whenever (is + 1) % Ndump == 0
+static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInfo, const qudaQKXTMinfo_Kepler &info, const char *fname, bool writeLoops) {
   if (!gaugePrecise) errorQuda("%s: Gauge field not allocated", fname);
   if (!cloverPrecise && param->dslash_type == QUDA_TWISTED_CLOVER_DSLASH) errorQuda("%s: Clover field not allocated", fname);
   if (param->solve_type != QUDA_DIRECT_PC_SOLVE) errorQuda("%s: This function works only with Direct solve and even odd preconditioning", fname);
@@ -426,7 +438,36 @@ static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInf
   double secs = 0, gflops = 0;
   int iters = 0;
 
-  auto solve = [&](bool lowPrecision, const char *kind, int index) {
+  // loop output: accumulator 0 the production run (then the high-precision solves of the bias run), 1 the low-precision solves of the bias run
+  LoopAccum *acc[2] = {nullptr, nullptr};
+  std::string pref[2];
+  const char *tsmTag = nullptr;
+  int Ndump = 0;
+  if (writeLoops) {
+    if (param->dslash_type != QUDA_TWISTED_MASS_DSLASH && param->dslash_type != QUDA_TWISTED_CLOVER_DSLASH)
+      errorQuda("%s: the one-end trick works only for twisted-mass and twisted-clover fermions", fname);
+    if (loopInfo.HighMomForm) errorQuda("%s: the high-momenta form is written only as HDF5, which this library does not link; set HighMomForm = false", fname);
+    if (loopInfo.FileFormat == HDF5_FORM) warningQuda("%s: HDF5 is not linked into this library; writing the loops in ASCII format", fname);
+    if (info.Q_sq < 0) errorQuda("%s: Q_sq = %d", fname, info.Q_sq);
+    acc[0] = loopAccumCreate(info.Q_sq);
+    if (useTSM) acc[1] = loopAccumCreate(info.Q_sq);
+    int L[3];
+    for (int k = 0; k < 3; k++) L[k] = g.X[k] * commGrid().dims[k];
+    const int Nmoms = qudaAmdLoopMomenta(L, info.Q_sq, nullptr, 0);
+    if (loopInfo.Nmoms != 0 && loopInfo.Nmoms != Nmoms) errorQuda("%s: loopInfo.Nmoms = %d, but Q_sq = %d holds %d momenta", fname, loopInfo.Nmoms, info.Q_sq, Nmoms);
+    Ndump = useTSM ? loopInfo.TSM_NdumpLP : loopInfo.Ndump;
+    if (Ndump <= 0 || (useTSM && loopInfo.TSM_NHP > 0 && loopInfo.TSM_NdumpHP <= 0)) errorQuda("%s: the dump interval must be positive", fname);
+    pref[0] = std::string(loopInfo.loop_fname) + (useTSM ? "_stoch_TSM_MG" : "_stoch_MG");
+    tsmTag = useTSM ? "NLP" : nullptr;
+  }
+  // `stage` holds the reconstructed solution in the solver's normalisation (the reference contracts it without the 2 kappa rescale)
+  auto absorb = [&](int which, int index) {
+    if (!acc[which]) return;
+    loopContractAdd(*acc[which], stage, param);
+    if ((index + 1) % Ndump == 0) loopWriteAscii(*acc[which], pref[which].c_str(), tsmTag, index + 1);
+  };
+
+  auto solve = [&](bool lowPrecision, const char *kind, int index, int which) {
     lexToDevice(stage, h_src.data(), g, true);
     b = stage;
     blas::zero(x);
@@ -445,6 +486,7 @@ static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInf
     secs += param->secs; gflops += param->gflops; iters += param->iter;
     dirac.reconstruct(x, b, param->solution_type);
     stage = x;
+    absorb(which, index);
     deviceToLex(h_sol.data(), stage, g, true, rescale ? 2.0 * param->kappa : 1.0);
     toSink(kind, index, (int)param->twist_flavor, h_src.data(), h_sol.data(), vec);
   };
@@ -489,6 +531,7 @@ static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInf
     for (int j = 0; j < n; j++) {
       dirac.reconstruct(*xs[j], *bs[j], param->solution_type);
       stage = *xs[j];
+      absorb(0, first + j);
       deviceToLex(h_sol.data(), stage, g, true, rescale ? 2.0 * param->kappa : 1.0);
       toSink(kind, first + j, (int)param->twist_flavor, h_srcs[j].data(), h_sol.data(), vec);
       delete bs[j]; delete xs[j];
@@ -501,16 +544,25 @@ static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInf
     const int n = std::min(group, Nrun - is);
     if (n >= 2) { solveGroup(useTSM, useTSM ? "loop_LP" : "loop_stoch", is, n); is += n; continue; }
     stochasticSource(h_src.data(), (size_t)g.V * 12, loopInfo.seed, is, info.source_type);
-    solve(useTSM, useTSM ? "loop_LP" : "loop_stoch", is);
+    solve(useTSM, useTSM ? "loop_LP" : "loop_stoch", is, 0);
     is++;
   }
   // bias correction of the truncated solver method: TSM_NHP fresh sources solved to both precisions (:9170-9230)
-  if (useTSM)
+  if (useTSM) {
+    if (writeLoops) {   // :9164-9410: fresh accumulators, the high- and the low-precision sums side by side, both dumped every TSM_NdumpHP
+      loopAccumZero(*acc[0]);
+      pref[0] = std::string(loopInfo.loop_fname) + "_stoch_TSM_MG_HighPrec";
+      pref[1] = std::string(loopInfo.loop_fname) + "_stoch_TSM_MG_LowPrec";
+      tsmTag = "NHP";
+      Ndump = loopInfo.TSM_NdumpHP;
+    }
     for (int is = 0; is < loopInfo.TSM_NHP; is++) {
       stochasticSource(h_src.data(), (size_t)g.V * 12, loopInfo.seed, Nrun + is, info.source_type);
-      solve(false, "loop_HP", is);
-      solve(true, "loop_HP_LP", is);
+      solve(false, "loop_HP", is, 0);
+      solve(true, "loop_HP_LP", is, 1);
     }
+  }
+  loopAccumDestroy(acc[0]); loopAccumDestroy(acc[1]);
   param->secs = secs; param->gflops = gflops; param->iter = iters;
   delete d; delete dSloppy; delete dPre;
 }
@@ -595,12 +647,17 @@ void calcMG_threepTwop_EvenOdd(void **gaugeSmeared, void **gauge, QudaGaugeParam
 void calcMG_loop_wOneD_TSM_EvenOdd(void **gaugeToPlaquette, QudaInvertParam *param, QudaGaugeParam *gauge_param, quda::qudaQKXTM_loopInfo loopInfo,
                                    quda::qudaQKXTMinfo_Kepler info) {
   (void)gaugeToPlaquette; (void)gauge_param;   // plaquette check and covariant derivatives of the contraction stage
-  quda::loopSolves(param, loopInfo, info, "calcMG_loop_wOneD_TSM_EvenOdd");
+  quda::loopSolves(param, loopInfo, info, "calcMG_loop_wOneD_TSM_EvenOdd", quda::loopOutputEnabled());
 }
 
 void calcMG_loop_wOneD_TSM_wExact(void **gaugeToPlaquette, QudaInvertParam *EVparam, QudaInvertParam *param, QudaGaugeParam *gauge_param,
                                   quda::qudaQKXTM_arpackInfo arpackInfo, quda::qudaQKXTM_loopInfo loopInfo, quda::qudaQKXTMinfo_Kepler info) {
   (void)gaugeToPlaquette; (void)gauge_param; (void)EVparam;
   if (arpackInfo.nEv != 0) errorQuda("calcMG_loop_wOneD_TSM_wExact: exact deflation with %d eigenvectors needs ARPACK, which this library does not link; nEv = 0 runs the undeflated loop", arpackInfo.nEv);
-  quda::loopSolves(param, loopInfo, info, "calcMG_loop_wOneD_TSM_wExact");
+  if (quda::loopOutputEnabled()) {
+    static bool warned = false;
+    if (!warned) warningQuda("calcMG_loop_wOneD_TSM_wExact: the exact part of the loops needs ARPACK, which this library does not link; the solves run, no loop files are written");
+    warned = true;
+  }
+  quda::loopSolves(param, loopInfo, info, "calcMG_loop_wOneD_TSM_wExact", false);
 }
