@@ -1,6 +1,6 @@
 // contract.hip — two-point correlators of the QKXTM drivers on the device: rotation of the propagators to the physical (twisted)
-// basis, meson and baryon contractions site by site, momentum projection per time slice, the sum over ranks and the reference's
-// ASCII writers.
+// basis, meson and baryon contractions site by site into the staged blocks that the shared momentum projection reads (momproj.hip,
+// which also sums over the ranks) and the reference's ASCII writers.
 //
 // Reference: calcMG_threepTwop_EvenOdd (lib/interface_quda.cpp:6960-7030), rotateToPhysicalBase_core_Kepler.h,
 // contractMesons_core_Kepler.h, contractBaryons_core_Kepler.h, writeTwop{Mesons,Baryons}_ASCII
@@ -32,21 +32,18 @@
 #include "interface_internal.h"
 #include "lex_index.h"
 #include "qa_core.h"
+#include "qkxtm_internal.h"
 #include "quda_amd_ext.h"
 #include "comm_quda.h"
-#include "p2p.h"
 
 namespace quda {
-
-GaugeField *loadLexGauge(void **gauge_lex, const LatticeGeom &g);                       // qkxtm.hip
-void gaussianSmear(ColorSpinorField &v, const GaugeField &U, double alpha, int nsmear);  // qkxtm.hip
-void lexToDevice(ColorSpinorField &dst, const double *h_lex, const LatticeGeom &g, bool ukqcd);
 
 namespace twop {
 
 constexpr int NMES = 10, NBAR = 10;
-constexpr int NCH = 2 * NMES + 2 * NBAR * 16;   // complex values per site: mesons [flavour][10], baryons [flavour][10][4][4]
-constexpr int NPART = 64;                        // partial sums per (time slice, momentum): fixed, whatever the lattice
+// staged blocks of 16 complex values per site: block fl holds the 10 meson channels of flavour fl (entries 10..15 zero), block
+// 2 + fl * 10 + ch the open spins [4][4] of baryon channel ch
+constexpr int NBLK = 2 + 2 * NBAR;
 constexpr int MAX_TERMS = 64;
 
 struct SPerm { int col[4]; double2 val[4]; };    // row r holds val[r] in column col[r]
@@ -116,7 +113,7 @@ __global__ void __launch_bounds__(256) field_to_prop_kernel(double2 *P, long V, 
 
 #define PR(p, s, t, c, d) (p)[(((s) * 4 + (t)) * 9 + (c) * 3 + (d)) * V + site]
 
-// ---- mesons: out[s][flavour * 10 + channel], sites of one time slice ----
+// ---- mesons: out[flavour][s][channel], sites of one time slice ----
 __global__ void __launch_bounds__(128) meson_kernel(double2 *out, const double2 *P0, const double2 *P1, long V, int Vs, int t) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= Vs) return;
@@ -134,12 +131,13 @@ __global__ void __launch_bounds__(128) meson_kernel(double2 *out, const double2 
           for (int ab = 0; ab < 9; ab++) sum = cadd(sum, cmulc(P[((G.col[de] * 4 + be) * 9 + ab) * V + site], P[((de * 4 + G.col[be]) * 9 + ab) * V + site]));
           acc = cadd(acc, cmul(gg, sum));
         }
-      out[(long)s * NCH + fl * NMES + ch] = acc;
+      out[((long)fl * Vs + s) * 16 + ch] = acc;
     }
+    for (int ch = NMES; ch < 16; ch++) out[((long)fl * Vs + s) * 16 + ch] = make_double2(0, 0);   // nothing uninitialised is projected
   }
 }
 
-// ---- baryons: out[s][20 + (flavour * 10 + channel) * 16 + gamma * 4 + gamma'] ----
+// ---- baryons: out[2 + flavour * 10 + channel][s][gamma * 4 + gamma'] ----
 __constant__ int c_eps[6][3] = {{0, 1, 2}, {1, 2, 0}, {2, 0, 1}, {0, 2, 1}, {2, 1, 0}, {1, 0, 2}};
 __constant__ double c_eps_sign[6] = {1, 1, 1, -1, -1, -1};
 
@@ -213,7 +211,7 @@ __global__ void __launch_bounds__(64) baryon_kernel(double2 *out, const double2 
       }
   }
   // g5 (UKQCD: spin mu <-> mu ^ 2) on the sink and / or source side of the Roper channels
-  double2 *o = out + (long)s * NCH + 2 * NMES + (fl * NBAR + ch) * 16;
+  double2 *o = out + ((long)(2 + fl * NBAR + ch) * Vs + s) * 16;
 #pragma unroll
   for (int g = 0; g < 4; g++)
 #pragma unroll
@@ -229,39 +227,6 @@ __global__ void __launch_bounds__(64) baryon_kernel(double2 *out, const double2 
     }
 }
 #undef PR
-
-// ---- momentum projection: part[(m * NPART + p) * NCH + ch] = sum over the p-th fixed share of the slice's sites of e^{-i p.(x - x0)} c(x) ----
-__global__ void __launch_bounds__(256) project_kernel(double2 *part, const double2 *cs, const int *moms, int Vs, int X0, int X1, int X2, int gx0, int gx1,
-                                                      int gx2, int L0, int L1, int L2) {
-  const int p = blockIdx.x, m = blockIdx.y;
-  const int n0 = moms[3 * m], n1 = moms[3 * m + 1], n2 = moms[3 * m + 2];
-  const long s0 = (long)Vs * p / NPART, s1 = (long)Vs * (p + 1) / NPART;
-  for (int ch = threadIdx.x; ch < NCH; ch += blockDim.x) {
-    double2 acc = make_double2(0, 0);
-    for (long s = s0; s < s1; s++) {
-      const int x = (int)(s % X0), y = (int)((s / X0) % X1), z = (int)(s / ((long)X0 * X1));
-      // global coordinate minus the source, reduced mod L so the phase argument stays small
-      const long k0 = (((long)n0 * (x + gx0)) % L0 + L0) % L0, k1 = (((long)n1 * (y + gx1)) % L1 + L1) % L1, k2 = (((long)n2 * (z + gx2)) % L2 + L2) % L2;
-      const double ph = 2.0 * M_PI * ((double)k0 / L0 + (double)k1 / L1 + (double)k2 / L2);
-      double sn, cn;
-      sincos(ph, &sn, &cn);
-      const double2 c = cs[s * NCH + ch];
-      acc.x += c.x * cn + c.y * sn;
-      acc.y += c.y * cn - c.x * sn;
-    }
-    part[((long)m * NPART + p) * NCH + ch] = acc;
-  }
-}
-
-// res[m * NCH + ch] = sum_p part[...], p = 0 .. NPART-1 in order
-__global__ void __launch_bounds__(256) reduce_kernel(double2 *res, const double2 *part, int Nmom) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Nmom * NCH) return;
-  const int m = i / NCH, ch = i % NCH;
-  double2 acc = make_double2(0, 0);
-  for (int p = 0; p < NPART; p++) acc = cadd(acc, part[((long)m * NPART + p) * NCH + ch]);
-  res[i] = acc;
-}
 
 // ================================ host: gamma algebra, term lists ================================
 typedef std::complex<double> cd;
@@ -421,15 +386,13 @@ struct TwopProps {
 TwopProps *twopPropsCreate(const LatticeGeom &g) { return new TwopProps(g); }
 void twopPropsDestroy(TwopProps *p) { delete p; }
 
-static size_t parityDoublesOf(const ColorSpinorField &f) { return (size_t)((const char *)f.Odd().V() - (const char *)f.Even().V()) / sizeof(double); }
-
 // column isc = nu * 3 + b of flavour fl from a full fp64 device spinor: sink smearing (colour only, any spin basis), basis change to
 // UKQCD if the field is in the device basis, scale
 void twopAbsorbColumn(TwopProps &props, int fl, int isc, ColorSpinorField &v, const LatticeGeom &g, const GaugeField *U, int nsmear, double alpha, bool deviceBasis,
                       double scale) {
   if (U && nsmear > 0) gaussianSmear(v, *U, alpha, nsmear);
   hipLaunchKernelGGL(twop::field_to_prop_kernel, dim3((g.Vh + 255) / 256, 2), dim3(256), 0, computeStream(), props.P[fl], props.V, (const double *)v.V(), v.Stride(),
-                     parityDoublesOf(v), g.Vh, g.Xh, g.X[1], g.X[2], deviceBasis ? BASIS_DR_TO_UKQCD : BASIS_NONE, scale, isc / 3, isc % 3);
+                     parityDoubles(v), g.Vh, g.Xh, g.X[1], g.X[2], deviceBasis ? BASIS_DR_TO_UKQCD : BASIS_NONE, scale, isc / 3, isc % 3);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -446,47 +409,38 @@ void twopContract(TwopProps &props, const LatticeGeom &g, const int src[4], int 
   hipLaunchKernelGGL(rotate_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, props.P[0], V, +1.0);
   hipLaunchKernelGGL(rotate_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, props.P[1], V, -1.0);
   HIP_CHECK(hipGetLastError());
-  double2 *cs = nullptr, *part = nullptr, *res = nullptr;
+  double2 *cs = nullptr, *acc = nullptr;
   int *d_moms = nullptr;
-  HIP_CHECK(hipMalloc(&cs, (size_t)Vs * NCH * sizeof(double2)));
-  HIP_CHECK(hipMalloc(&part, (size_t)Nm * NPART * NCH * sizeof(double2)));
-  HIP_CHECK(hipMalloc(&res, (size_t)Lt * Nm * NCH * sizeof(double2)));
+  const size_t per = (size_t)Nm * 16 * 2;   // doubles per (block, time slice)
+  HIP_CHECK(hipMalloc(&cs, (size_t)NBLK * Vs * 16 * sizeof(double2)));
+  HIP_CHECK(hipMalloc(&acc, (size_t)NBLK * Lt * per * sizeof(double)));
+  HIP_CHECK(hipMemsetAsync(acc, 0, (size_t)NBLK * Lt * per * sizeof(double), st));
   HIP_CHECK(hipMalloc(&d_moms, moms.size() * sizeof(int)));
   HIP_CHECK(hipMemcpyAsync(d_moms, moms.data(), moms.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  int gx[3];
-  for (int d = 0; d < 3; d++) gx[d] = cg.coords[d] * g.X[d] - src[d];
+  // phases relative to the source: the origin of the local lattice minus the source position
+  int gx[3], L[3];
+  for (int d = 0; d < 3; d++) { gx[d] = cg.coords[d] * g.X[d] - src[d]; L[d] = g.X[d] * cg.dims[d]; }
   for (int t = 0; t < Lt; t++) {
     hipLaunchKernelGGL(meson_kernel, dim3((Vs + 127) / 128), dim3(128), 0, st, cs, props.P[0], props.P[1], V, Vs, t);
     hipLaunchKernelGGL(baryon_kernel, dim3((Vs + 63) / 64, NBAR, 2), dim3(64), 0, st, cs, props.P[0], props.P[1], V, Vs, t);
-    hipLaunchKernelGGL(project_kernel, dim3(NPART, Nm), dim3(256), 0, st, part, cs, d_moms, Vs, g.X[0], g.X[1], g.X[2], gx[0], gx[1], gx[2], g.X[0] * cg.dims[0],
-                       g.X[1] * cg.dims[1], g.X[2] * cg.dims[2]);
-    hipLaunchKernelGGL(reduce_kernel, dim3((Nm * NCH + 255) / 256), dim3(256), 0, st, res + (size_t)t * Nm * NCH, part, Nm);
     HIP_CHECK(hipGetLastError());
+    momentumProject(acc, cs, NBLK, t, 1, Lt, d_moms, Nm, g.X, gx, L);
   }
-  std::vector<double> loc((size_t)Lt * Nm * NCH * 2), glob((size_t)T * Nm * NCH * 2, 0.0);
-  HIP_CHECK(hipMemcpyAsync(loc.data(), res, loc.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
-  (void)hipFree(cs); (void)hipFree(part); (void)hipFree(res); (void)hipFree(d_moms);
-  memcpy(&glob[(size_t)cg.coords[3] * Lt * Nm * NCH * 2], loc.data(), loc.size() * sizeof(double));
-  if (cg.size > 1) {
-    // one collective for the whole result; the ranks' contributions are then added in rank order, the same sum on every rank
-    std::vector<double> all(glob.size() * cg.size);
-    commAllgatherBytes(glob.data(), all.data(), glob.size() * sizeof(double));
-    for (size_t i = 0; i < glob.size(); i++) {
-      double v = 0;
-      for (int r = 0; r < cg.size; r++) v += all[(size_t)r * glob.size() + i];
-      glob[i] = v;
-    }
-  }
+  std::vector<double> glob((size_t)NBLK * T * per);
+  gatherTimeBlocks(glob.data(), (const double *)acc, NBLK, Lt, per);   // synchronises
+  (void)hipFree(cs); (void)hipFree(acc); (void)hipFree(d_moms);
   for (int it = 0; it < T; it++) {
     const int ts = (it + src[3]) % T;
     const double sign = it + src[3] >= T ? -1.0 : 1.0;
-    for (int m = 0; m < Nm; m++) {
-      const double *G = &glob[((size_t)ts * Nm + m) * NCH * 2];
-      if (h_mes) memcpy(h_mes + ((size_t)it * Nm + m) * 2 * NMES * 2, G, 2 * NMES * 2 * sizeof(double));
-      if (h_bar)
-        for (int k = 0; k < 2 * NBAR * 16 * 2; k++) h_bar[((size_t)it * Nm + m) * 2 * NBAR * 16 * 2 + k] = sign * G[2 * NMES * 2 + k];
-    }
+    for (int m = 0; m < Nm; m++)
+      for (int fl = 0; fl < 2; fl++) {
+        if (h_mes) memcpy(h_mes + (((size_t)it * Nm + m) * 2 + fl) * NMES * 2, &glob[((size_t)fl * T + ts) * per + (size_t)m * 32], NMES * 2 * sizeof(double));
+        for (int ch = 0; ch < NBAR && h_bar; ch++) {
+          const double *G = &glob[((size_t)(2 + fl * NBAR + ch) * T + ts) * per + (size_t)m * 32];
+          double *o = h_bar + ((((size_t)it * Nm + m) * 2 + fl) * NBAR + ch) * 32;
+          for (int k = 0; k < 32; k++) o[k] = sign * G[k];
+        }
+      }
   }
 }
 
@@ -535,13 +489,7 @@ extern "C" {
 
 int qudaAmdTwopMomenta(int Q_sq, int *moms, int max_moms) {
   if (Q_sq < 0) errorQuda("qudaAmdTwopMomenta: Q_sq = %d", Q_sq);
-  const std::vector<int> m = twopMomenta(Q_sq);
-  const int n = (int)m.size() / 3;
-  if (moms) {
-    if (max_moms < n) errorQuda("qudaAmdTwopMomenta: %d momenta do not fit into max_moms = %d", n, max_moms);
-    memcpy(moms, m.data(), m.size() * sizeof(int));
-  }
-  return n;
+  return copyMomenta(twopMomenta(Q_sq), moms, max_moms, "qudaAmdTwopMomenta");
 }
 
 int qudaAmdTwopTimeExtent(void) {

@@ -24,7 +24,6 @@
 // QUDA_AMD_LOOP_FUSED=0: the reference's chain of single-direction covariant shifts (applyCovariantShift) and pairwise
 // contractions in its call order, the in-library cross-check.
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -38,18 +37,14 @@
 #include "interface_internal.h"
 #include "p2p.h"
 #include "qa_core.h"
+#include "qkxtm_internal.h"
 #include "quda_amd_ext.h"
 
 namespace quda {
 
-void lexToDevice(ColorSpinorField &dst, const double *h_lex, const LatticeGeom &g, bool ukqcd);   // qkxtm.hip
-
 namespace loop {
 
 constexpr int NBLK = 18, NGM = 16;
-constexpr int NPART = 64;   // partial sums per (block, time slice, momentum): fixed, whatever the lattice or the launch
-constexpr int NLANE = 16;   // site lanes of a partial sum, reduced in order
-constexpr int MB_SMALL = 8, MB_LARGE = 36;   // momenta per projection block: 36 holds Q_sq <= 4 (33 momenta) in one pass over the staged blocks
 
 struct LoopArg {
   const double *x[2], *phi[2];   // parity blocks of the two fields (12 double2 planes of stride sp_stride), device basis
@@ -222,76 +217,6 @@ __global__ void __launch_bounds__(256) gamma5_kernel(double *v, int stride, int 
   }
 }
 
-// ---- momentum projection of the staged blocks ----
-// part[(((k * nt + tl) * NPART + p) * Nm + m) * 16 + gm] = sum over the p-th fixed share of the slice's sites of e^{-2 pi i n.x / L} cs[k][tl, site][gm],
-// x the GLOBAL coordinate.  One phase per (site, momentum) serves the 16 entries of a block; it is the product of three factors from
-// per-direction tables in LDS.  A share is summed by NLANE site lanes (sites s0 + lane, s0 + lane + NLANE, ...), then the lanes in order.
-template <int MB> __global__ void __launch_bounds__(256) loop_project_kernel(double2 *part, const double2 *cs, long S, int Vs, int nt, const int *moms, int Nm, int nmb, int X0, int Y, int Z,
-                                                           int gx0, int gx1, int gx2, int L0, int L1, int L2) {
-  extern __shared__ double2 lds[];
-  double2 *ex = lds, *ey = ex + MB * X0, *ez = ey + MB * Y, *red = ez + MB * Z;
-  // the momentum chunks of one share are neighbours in the launch order: they read the same staged data at the same time
-  const int p = blockIdx.x / nmb, tl = blockIdx.y, k = blockIdx.z, m0 = (blockIdx.x % nmb) * MB;
-  const int nm = min(MB, Nm - m0);
-  for (int i = threadIdx.x; i < MB * (X0 + Y + Z); i += blockDim.x) {
-    int m, c, L, n, gc;
-    if (i < MB * X0) { m = i / X0; c = i % X0; L = L0; gc = c + gx0; n = m < nm ? moms[3 * (m0 + m)] : 0; }
-    else if (i < MB * (X0 + Y)) { const int q = i - MB * X0; m = q / Y; c = q % Y; L = L1; gc = c + gx1; n = m < nm ? moms[3 * (m0 + m) + 1] : 0; }
-    else { const int q = i - MB * (X0 + Y); m = q / Z; c = q % Z; L = L2; gc = c + gx2; n = m < nm ? moms[3 * (m0 + m) + 2] : 0; }
-    const long kk = (((long)n * gc) % L + L) % L;   // reduced mod L so the phase argument stays small
-    double sn, cn;
-    sincos(2.0 * M_PI * (double)kk / L, &sn, &cn);
-    lds[i] = make_double2(cn, -sn);
-  }
-  __syncthreads();
-  const int gm = threadIdx.x & 15, sl = threadIdx.x >> 4;
-  const long s0 = (long)Vs * p / NPART, s1 = (long)Vs * (p + 1) / NPART;
-  double2 acc[MB];
-#pragma unroll
-  for (int m = 0; m < MB; m++) acc[m] = make_double2(0, 0);
-  const double2 *src = cs + ((long)k * S + (long)tl * Vs) * NGM + gm;
-  for (long s = s0 + sl; s < s1; s += NLANE) {
-    const int x = (int)(s % X0), y = (int)((s / X0) % Y), z = (int)(s / ((long)X0 * Y));
-    const double2 c = src[s * NGM];
-#pragma unroll
-    for (int m = 0; m < MB; m++) {
-      const double2 a = ex[m * X0 + x], b = ey[m * Y + y], d = ez[m * Z + z];
-      const double2 ab = make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-      const double2 ph = make_double2(ab.x * d.x - ab.y * d.y, ab.x * d.y + ab.y * d.x);
-      acc[m].x += c.x * ph.x - c.y * ph.y;
-      acc[m].y += c.x * ph.y + c.y * ph.x;
-    }
-  }
-#pragma unroll
-  for (int m = 0; m < MB; m++) {
-    red[threadIdx.x] = acc[m];
-    __syncthreads();
-    if (sl == 0 && m < nm) {
-      double2 r = red[gm];
-      for (int q = 1; q < NLANE; q++) { r.x += red[q * 16 + gm].x; r.y += red[q * 16 + gm].y; }
-      part[((((long)k * nt + tl) * NPART + p) * Nm + m0 + m) * NGM + gm] = r;
-    }
-    __syncthreads();
-  }
-}
-
-// acc[((k * Lt + t0 + tl) * Nm + m) * 16 + gm] += sum_p part[...], p = 0 .. NPART-1 in order
-__global__ void __launch_bounds__(256) loop_reduce_kernel(double2 *acc, const double2 *part, int nt, int Lt, int t0, int Nm) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long per = (long)Nm * NGM;
-  if (i >= (long)NBLK * nt * per) return;
-  const int k = (int)(i / (nt * per)), tl = (int)((i / per) % nt);
-  const long r = i % per;
-  double2 sum = make_double2(0, 0);
-  for (int p = 0; p < NPART; p++) {
-    const double2 c = part[(((long)k * nt + tl) * NPART + p) * per + r];
-    sum.x += c.x; sum.y += c.y;
-  }
-  double2 *dst = acc + ((long)k * Lt + t0 + tl) * per + r;
-  const double2 old = *dst;
-  *dst = make_double2(old.x + sum.x, old.y + sum.y);
-}
-
 }  // namespace loop
 
 // momenta of the loops (createLoopMomenta): pz outermost, py, px innermost, each component 0 .. L/2-1, -L/2 .. -1 over the GLOBAL extent
@@ -343,8 +268,6 @@ void loopAccumDestroy(LoopAccum *A) {
   (void)hipFree(A->d); (void)hipFree(A->d_moms);
   delete A;
 }
-
-static size_t parityDoublesOf(const ColorSpinorField &f) { return (size_t)((const char *)f.Odd().V() - (const char *)f.Even().V()) / sizeof(double); }
 
 // read at every contraction, so one process can time both paths (tools/loop_timing.py)
 static bool fusedEnabled() {
@@ -460,7 +383,7 @@ void loopContractAdd(LoopAccum &A, ColorSpinorField &x, QudaInvertParam *param) 
   makePhi(phi, x, param);
   HIP_CHECK(hipEventRecord(ev[1], st));
 
-  const int Vs = g.X[0] * g.X[1] * g.X[2], Lt = g.X[3], Nm = A.Nm;
+  const int Vs = g.X[0] * g.X[1] * g.X[2], Lt = g.X[3];
   // time slices per chunk: the staged blocks stay below 2 GiB
   const size_t perSlice = (size_t)Vs * NBLK * NGM * sizeof(double2);
   int tc = (int)std::max<size_t>(1, std::min<size_t>((size_t)Lt, ((size_t)2 << 30) / perSlice));
@@ -469,9 +392,8 @@ void loopContractAdd(LoopAccum &A, ColorSpinorField &x, QudaInvertParam *param) 
     if (env < 0) { const char *e = getenv("QUDA_AMD_LOOP_TCHUNK"); env = e ? atoi(e) : 0; }
     if (env > 0) tc = std::min(env, Lt);
   }
-  double2 *cs = nullptr, *part = nullptr;
+  double2 *cs = nullptr;
   HIP_CHECK(hipMalloc(&cs, perSlice * tc));
-  HIP_CHECK(hipMalloc(&part, (size_t)NBLK * tc * NPART * Nm * NGM * sizeof(double2)));
 
   const bool fused = fusedEnabled();
   LoopArg arg;
@@ -515,13 +437,6 @@ void loopContractAdd(LoopAccum &A, ColorSpinorField &x, QudaInvertParam *param) 
   }
   int gx[3], L[3];
   for (int d = 0; d < 3; d++) { gx[d] = cg.coords[d] * g.X[d]; L[d] = g.X[d] * cg.dims[d]; }
-  // all momenta in one pass where the phase tables of MB_LARGE momenta fit into 64 KiB of LDS, else chunks of MB_SMALL
-  auto ldsOf = [&](int mb) { return ((size_t)mb * (g.X[0] + g.X[1] + g.X[2]) + 256) * sizeof(double2); };
-  const bool large = Nm > MB_SMALL && Nm <= MB_LARGE && ldsOf(MB_LARGE) <= 64 * 1024;
-  const int mbs = large ? MB_LARGE : MB_SMALL;
-  const int nmb = (Nm + mbs - 1) / mbs;
-  const size_t ldsBytes = ldsOf(mbs);
-  if (ldsBytes > 64 * 1024) errorQuda("loop contraction: spatial extents %d %d %d exceed the phase tables", g.X[0], g.X[1], g.X[2]);
   for (int t0 = 0; t0 < Lt; t0 += tc) {
     const int nt = std::min(tc, Lt - t0);
     const long S = (long)nt * Vs;
@@ -533,15 +448,7 @@ void loopContractAdd(LoopAccum &A, ColorSpinorField &x, QudaInvertParam *param) 
       chainChunk(cs, S, t0, x, phi, F, g);
     }
     mark();
-    if (large)
-      hipLaunchKernelGGL((loop_project_kernel<MB_LARGE>), dim3(NPART * nmb, nt, NBLK), dim3(256), ldsBytes, st, part, cs, S, Vs, nt, A.d_moms, Nm, nmb, g.X[0], g.X[1], g.X[2],
-                         gx[0], gx[1], gx[2], L[0], L[1], L[2]);
-    else
-      hipLaunchKernelGGL((loop_project_kernel<MB_SMALL>), dim3(NPART * nmb, nt, NBLK), dim3(256), ldsBytes, st, part, cs, S, Vs, nt, A.d_moms, Nm, nmb, g.X[0], g.X[1], g.X[2],
-                         gx[0], gx[1], gx[2], L[0], L[1], L[2]);
-    const long nred = (long)NBLK * nt * Nm * NGM;
-    hipLaunchKernelGGL(loop_reduce_kernel, dim3((unsigned)((nred + 255) / 256)), dim3(256), 0, st, A.d, part, nt, Lt, t0, Nm);
-    HIP_CHECK(hipGetLastError());
+    momentumProject(A.d, cs, NBLK, t0, nt, Lt, A.d_moms, A.Nm, g.X, gx, L);
     mark();
   }
   HIP_CHECK(hipStreamSynchronize(st));
@@ -560,33 +467,11 @@ void loopContractAdd(LoopAccum &A, ColorSpinorField &x, QudaInvertParam *param) 
   for (int i = 0; i < 2; i++) (void)hipEventDestroy(ev[i]);
   for (void *gh : ghosts) (void)hipFree(gh);
   for (int mu = 0; mu < 4; mu++) { delete F.Fx[mu]; delete F.Bx[mu]; delete F.Fp[mu]; delete F.Bp[mu]; }
-  (void)hipFree(cs); (void)hipFree(part);
+  (void)hipFree(cs);
 }
 
-// out[18][T global][Nmoms][16][re, im]: this rank's time slices at their global position, then one all-gather and the ranks added in
-// rank order, so every rank holds the same numbers
-void loopAccumGet(const LoopAccum &A, double *out) {
-  const CommGrid &cg = commGrid();
-  const int Lt = A.Lt, T = Lt * cg.dims[3];
-  const size_t per = (size_t)A.Nm * loop::NGM * 2;
-  std::vector<double> loc(A.n * 2);
-  HIP_CHECK(hipMemcpyAsync(loc.data(), A.d, loc.size() * sizeof(double), hipMemcpyDeviceToHost, computeStream()));
-  HIP_CHECK(hipStreamSynchronize(computeStream()));
-  const size_t total = (size_t)loop::NBLK * T * per;
-  std::vector<double> glob(total, 0.0);
-  for (int k = 0; k < loop::NBLK; k++)
-    memcpy(&glob[((size_t)k * T + (size_t)cg.coords[3] * Lt) * per], &loc[(size_t)k * Lt * per], (size_t)Lt * per * sizeof(double));
-  if (cg.size > 1) {
-    std::vector<double> all(total * cg.size);
-    commAllgatherBytes(glob.data(), all.data(), total * sizeof(double));
-    for (size_t i = 0; i < total; i++) {
-      double v = 0;
-      for (int r = 0; r < cg.size; r++) v += all[(size_t)r * total + i];
-      glob[i] = v;
-    }
-  }
-  memcpy(out, glob.data(), total * sizeof(double));
-}
+// out[18][T global][Nmoms][16][re, im], the same numbers on every rank
+void loopAccumGet(const LoopAccum &A, double *out) { gatherTimeBlocks(out, (const double *)A.d, loop::NBLK, A.Lt, (size_t)A.Nm * loop::NGM * 2); }
 
 static const char *const loopTypeName[6] = {"Scalar", "dOp", "Loops", "LoopsCv", "LpsDw", "LpsDwCv"};
 static const bool loopTypeOneD[6] = {false, false, true, true, true, true};
@@ -636,13 +521,7 @@ extern "C" {
 
 int qudaAmdLoopMomenta(const int L[3], int Q_sq, int *moms, int max_moms) {
   if (!L || L[0] < 1 || L[1] < 1 || L[2] < 1 || Q_sq < 0) errorQuda("qudaAmdLoopMomenta: bad extents or Q_sq = %d", Q_sq);
-  const std::vector<int> m = loopMomenta(L, Q_sq);
-  const int n = (int)m.size() / 3;
-  if (moms) {
-    if (max_moms < n) errorQuda("qudaAmdLoopMomenta: %d momenta do not fit into max_moms = %d", n, max_moms);
-    memcpy(moms, m.data(), m.size() * sizeof(int));
-  }
-  return n;
+  return copyMomenta(loopMomenta(L, Q_sq), moms, max_moms, "qudaAmdLoopMomenta");
 }
 
 void qudaAmdSetLoopOutput(int enable) { g_loopOutput = enable != 0; }

@@ -28,12 +28,11 @@
 #include "lex_index.h"
 #include "multigrid.h"
 #include "p2p.h"
+#include "qkxtm_internal.h"
 #include "quda_amd_ext.h"
 #include "solver.h"
 
 namespace quda {
-
-void *stagingBuffer(size_t bytes);   // fields.hip
 
 // ---- site order / basis: QKXTM host vector (lexicographic sites, UKQCD spin) <-> device full field (even-odd, DeGrand-Rossi) ----
 
@@ -83,8 +82,6 @@ __global__ void __launch_bounds__(256) spread_slot_kernel(double *out, const dou
   rotate_basis(q, r, BASIS_UKQCD_TO_DR);
   Planar<double, 24>::store(q, out + parity * parityDoubles, stride, idx, nullptr, idx);
 }
-
-static size_t parityDoubles(const ColorSpinorField &f) { return (size_t)((const char *)f.Odd().V() - (const char *)f.Even().V()) / sizeof(double); }
 
 static void checkFullDouble(const ColorSpinorField &f) {
   if (f.Location() != QUDA_CUDA_FIELD_LOCATION || f.Precision() != QUDA_DOUBLE_PRECISION || f.SiteSubset() != QUDA_FULL_SITE_SUBSET || f.Nspin() != 4 || f.Ncolor() != 3)
@@ -166,6 +163,18 @@ static void checkCalcParam(const QudaInvertParam *param, const char *fname) {
   if (param->dslash_type != QUDA_TWISTED_MASS_DSLASH && param->dslash_type != QUDA_TWISTED_CLOVER_DSLASH) errorQuda("%s: twisted-mass / twisted-clover operators only", fname);
   if (param->inv_type_precondition == QUDA_MG_INVERTER && (!param->preconditionerUP || !param->preconditionerDN))
     errorQuda("%s: preconditionerUP / preconditionerDN not set (one multigrid hierarchy per twist flavour)", fname);
+}
+
+// Do n sources fit through one lockstep solve (block_solver.cpp)?  A source takes three full fields and 2 + 2 gcrNkrylov sloppy parity
+// fields; all of them within 0.6 of the free device memory.  QUDA_AMD_QKXTM_LOCKSTEP=0 answers no.
+static bool lockstepFits(int n, const QudaInvertParam *param, const LatticeGeom &g) {
+  static int env = -1;
+  if (env < 0) { const char *e = getenv("QUDA_AMD_QKXTM_LOCKSTEP"); env = e ? atoi(e) : 1; }
+  if (!env) return false;
+  size_t freeB = 0, totalB = 0;
+  HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
+  const double full = (double)g.V * 24 * (int)param->cuda_prec, parS = 0.5 * (double)g.V * 24 * (int)param->cuda_prec_sloppy;
+  return n * (3.0 * full + (2.0 + 2.0 * param->gcrNkrylov) * parS) <= 0.6 * (double)freeB;
 }
 
 }  // namespace quda
@@ -250,20 +259,8 @@ void calcMGPropagatorsEach(void **gauge_APE, QudaInvertParam *param, const QudaA
   // The twelve spin-colour sources of a flavour through ONE lockstep solve (block_solver.cpp; DESIGN 3 "Several sources in lockstep") when the
   // solver is multigrid-preconditioned GCR without an initial guess and the fields fit: the hierarchy's cycle runs once per iteration for all of
   // them.  QUDA_AMD_QKXTM_LOCKSTEP=0 keeps the reference's order of 24 separate solves.
-  bool lockstep = param->inv_type == QUDA_GCR_INVERTER && param->inv_type_precondition == QUDA_MG_INVERTER && param->preconditionerUP && param->preconditionerDN &&
-                  param->use_init_guess != QUDA_USE_INIT_GUESS_YES;
-  {
-    static int env = -1;
-    if (env < 0) { const char *e = getenv("QUDA_AMD_QKXTM_LOCKSTEP"); env = e ? atoi(e) : 1; }
-    if (!env) lockstep = false;
-    if (lockstep) {
-      size_t freeB = 0, totalB = 0;
-      HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
-      const double full = (double)g.V * 24 * (int)param->cuda_prec, parS = 0.5 * (double)g.V * 24 * (int)param->cuda_prec_sloppy;
-      const double need = 12.0 * (2.0 * full + 1.0 * full + (2.0 + 2.0 * param->gcrNkrylov) * parS);
-      if (need > 0.6 * (double)freeB) lockstep = false;
-    }
-  }
+  const bool lockstep = param->inv_type == QUDA_GCR_INVERTER && param->inv_type_precondition == QUDA_MG_INVERTER && param->preconditionerUP && param->preconditionerDN &&
+                        param->use_init_guess != QUDA_USE_INIT_GUESS_YES && lockstepFits(12, param, g);
   if (lockstep) {
     std::vector<ColorSpinorField *> bs(12), xs(12), ins(12), outs(12);
     for (int isc = 0; isc < 12; isc++) { bs[isc] = new ColorSpinorField(cp); xs[isc] = new ColorSpinorField(cp); }
@@ -383,15 +380,6 @@ static void stochasticSource(double *h, size_t ncomplex, unsigned long seed, int
   }
 }
 
-// loop.hip
-struct LoopAccum;
-bool loopOutputEnabled();
-LoopAccum *loopAccumCreate(int Q_sq);
-void loopAccumZero(LoopAccum &A);
-void loopAccumDestroy(LoopAccum *A);
-void loopContractAdd(LoopAccum &A, ColorSpinorField &x, QudaInvertParam *param);
-void loopWriteAscii(const LoopAccum &A, const char *pref, const char *tsmTag, int nnnn);
-
 // the loop of calcMG_loop_wOneD_TSM_EvenOdd (reference lib/interface_quda.cpp:8535-9430).  writeLoops (the loop output switched on,
 // qudaAmdSetLoopOutput): every solution is contracted from the device-resident field after the reconstruction (loop.hip), the sums
 // over the noise vectors are cumulative and a snapshot goes to the reference's ASCII files whenever (is + 1) % Ndump == 0
@@ -495,18 +483,8 @@ static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInf
   // guess: the hierarchy's cycle runs once per iteration for the whole group.  The sources of a group are drawn exactly as one by one (the
   // generator is keyed by the source number); QUDA_AMD_QKXTM_LOCKSTEP=0 keeps the reference's one-by-one order.
   int group = 1;
-  if (param->inv_type == QUDA_GCR_INVERTER && param->inv_type_precondition == QUDA_MG_INVERTER && param->preconditioner && param->use_init_guess != QUDA_USE_INIT_GUESS_YES) {
-    static int env = -1;
-    if (env < 0) { const char *e = getenv("QUDA_AMD_QKXTM_LOCKSTEP"); env = e ? atoi(e) : 1; }
-    if (env) {
-      size_t freeB = 0, totalB = 0;
-      HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
-      const double full = (double)g.V * 24 * (int)param->cuda_prec, parS = 0.5 * (double)g.V * 24 * (int)param->cuda_prec_sloppy;
-      const double perSource = 3.0 * full + (2.0 + 2.0 * param->gcrNkrylov) * parS;
-      group = 12;
-      while (group > 1 && group * perSource > 0.6 * (double)freeB) group /= 2;
-    }
-  }
+  if (param->inv_type == QUDA_GCR_INVERTER && param->inv_type_precondition == QUDA_MG_INVERTER && param->preconditioner && param->use_init_guess != QUDA_USE_INIT_GUESS_YES)
+    for (group = 12; group > 1 && !lockstepFits(group, param, g); group /= 2) {}
   auto solveGroup = [&](bool lowPrecision, const char *kind, int first, int n) {
     std::vector<std::vector<double>> h_srcs(n, std::vector<double>(vec));
     std::vector<ColorSpinorField *> bs(n), xs(n), ins(n), outs(n);
@@ -570,17 +548,6 @@ static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInf
 }  // namespace quda
 
 extern "C" void qudaAmdSetSolutionSink(QudaAmdSolutionSink sink, void *ctx) { quda::g_sink = sink; quda::g_sinkCtx = ctx; }
-
-namespace quda {
-struct TwopProps;
-bool twopOutputEnabled();
-TwopProps *twopPropsCreate(const LatticeGeom &g);
-void twopPropsDestroy(TwopProps *p);
-void twopAbsorbColumn(TwopProps &props, int fl, int isc, ColorSpinorField &v, const LatticeGeom &g, const GaugeField *U, int nsmear, double alpha, bool deviceBasis,
-                      double scale);
-void twopContract(TwopProps &props, const LatticeGeom &g, const int src[4], int Q_sq, double *h_mes, double *h_bar);
-void twopWriteAscii(const char *fname_twop, const int src[4], int Q_sq, int T, const double *h_mes, const double *h_bar);
-}  // namespace quda
 
 void calcMG_threepTwop_EvenOdd(void **gaugeSmeared, void **gauge, QudaGaugeParam *gauge_param, QudaInvertParam *param, quda::qudaQKXTMinfo_Kepler info,
                                char *filename_twop, char *filename_threep, quda::WHICHPARTICLE NUCLEON) {

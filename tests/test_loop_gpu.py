@@ -105,14 +105,22 @@ def _load(qa, gauge, X, antiperiodic, recon=18):
 
 @pytest.mark.parametrize("X", LATTICES)
 @pytest.mark.parametrize("antiperiodic", [False, True])
-def test_twisted_mass_matches_numpy(qa, oracle, X, antiperiodic):
+def test_twisted_mass_matches_numpy(qa, oracle, X, antiperiodic, qsq=QSQ):
     gauge, _, x = _fields(oracle, X, antiperiodic)
     _load(qa, gauge, X, antiperiodic)
-    got = qa.contract_loop(x, _ip(qa, False), QSQ, X[:3])
-    moms = qa.loop_momenta(X[:3], QSQ)
+    got = qa.contract_loop(x, _ip(qa, False), qsq, X[:3])
+    moms = qa.loop_momenta(X[:3], qsq)
     assert got.shape == (18, X[3], len(moms), 16)
     want = numpy_loops(x, _wilson(oracle, gauge, None, x, X), _lex_links(oracle, gauge, X), X, moms)
     assert _block_err(got, want) < 1e-12
+
+
+@pytest.mark.parametrize("qsq,nmoms", [(1, 7), (5, 42)])
+def test_twisted_mass_matches_numpy_momentum_chunks(qa, oracle, qsq, nmoms):
+    """QSQ = 3 (27 momenta on 4^3) takes the one-pass branch of the shared projection (up to 36 momenta); 7 momenta are one chunk of 8,
+    42 are six chunks of 8, the last holding two.  Same restatement, same bound."""
+    assert len(qa.loop_momenta(LATTICES[0][:3], qsq)) == nmoms
+    test_twisted_mass_matches_numpy(qa, oracle, LATTICES[0], False, qsq)
 
 
 @pytest.mark.parametrize("X", LATTICES)

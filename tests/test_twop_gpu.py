@@ -124,7 +124,7 @@ def _momenta(Q):
 @pytest.mark.parametrize("X,src", [((4, 4, 4, 4), (1, 2, 3, 3)), ((6, 4, 2, 8), (5, 1, 1, 6))])
 @pytest.mark.parametrize("nsmear", [0, 2])
 @pytest.mark.parametrize("mask", [0, 0b0110, 0b1010])
-def test_contractions_match_numpy(qa, oracle, X, src, nsmear, mask):
+def test_contractions_match_numpy(qa, oracle, X, src, nsmear, mask, Q=3):
     """random complex propagators (nothing relies on g5-hermiticity); 1e-12 relative to the largest entry of each (channel, flavour) block"""
     gauge, _, _ = oracle.make_fields(list(X), seed=5, antiperiodic_t=False, clover=False)
     qa.load_gauge(gauge, qa.gauge_param(X, t_boundary=qa.QUDA_PERIODIC_T))
@@ -132,7 +132,7 @@ def test_contractions_match_numpy(qa, oracle, X, src, nsmear, mask):
     V = int(np.prod(X))
     rng = np.random.default_rng(11 + nsmear + mask)
     up, dn = rng.standard_normal((12, V * 24)), rng.standard_normal((12, V * 24))
-    Q, alpha = 3, 0.7
+    alpha = 0.7
     qa.lib().qudaAmdSetPartitionMask(mask)
     try:
         mes, bar = qa.contract_twop(up, dn, g_lex if nsmear else None, src, Q, nsmear, alpha)
@@ -145,6 +145,16 @@ def test_contractions_match_numpy(qa, oracle, X, src, nsmear, mask):
     assert mes.shape == (X[3], len(moms), 2, 10) and bar.shape == (X[3], len(moms), 2, 10, 4, 4)
     em, eb = _blockwise_err(mes, wm, (2, 3)), _blockwise_err(bar, wb, (2, 3))
     assert em < 1e-12 and eb < 1e-12, (em, eb)
+
+
+@pytest.mark.parametrize("Q,nmoms", [(1, 7), (5, 57)])
+def test_contractions_match_numpy_momentum_chunks(qa, oracle, Q, nmoms):
+    """Q = 3 (27 momenta) takes the one-pass branch of the shared projection (up to 36 momenta); 7 momenta are one chunk of 8, 57 are
+    eight chunks, the last holding one.  On 6 x 4 x 2 a slice has 48 sites for 64 shares (empty shares, one-site shares, shares shorter
+    than the 16 site lanes), the source puts the phase origin at negative coordinates, and the 57 momenta include aliased ones (n and
+    n +- L), which the restatement handles by formula.  Same restatement, same bound."""
+    assert len(_momenta(Q)) == nmoms
+    test_contractions_match_numpy(qa, oracle, (6, 4, 2, 8), (5, 1, 1, 6), 0, 0, Q)
 
 
 def test_pseudoscalar_on_solved_propagators(qa, oracle):
