@@ -6,9 +6,14 @@
  * multigrid hierarchies in param->preconditioner[UP|DN], Dirac::reconstruct, normalisation.  Each finished solution is handed
  * to the sink registered with qudaAmdSetSolutionSink (quda_amd_ext.h).  With qudaAmdSetTwopOutput(1), calcMG_threepTwop_EvenOdd
  * also computes the two-point functions of every source on the device (meson and baryon contractions, momentum projection up to
- * info.Q_sq) and writes the reference's ASCII files named from filename_twop.  Three-point functions, loop contractions and HDF5
- * output are not part of this library; the arguments only they consume (gauge for the plaquette / derivative operators,
- * filename_threep, NUCLEON) are accepted and ignored.
+ * info.Q_sq) and writes the reference's ASCII files named from filename_twop.  With qudaAmdSetThreepOutput(1) it also runs the
+ * fixed-sink stage for every source with info.run3pt_src != 0: for every sink separation info.tsinkSource[its], projector
+ * info.proj_list[its][ip] and part (1, 2) the sequential source, twelve solves with the twist opposite to the inserted flavour and
+ * the contraction with the forward propagator (ultra-local and one-derivative operators, conserved current; links from `gauge` in the
+ * QKXTM lexicographic layout with the boundary applied, or the resident precise links where it is NULL), and rank 0 writes
+ * <filename_threep>_tsink<t>_proj<info.thrp_proj_type[P]>.<proton|neutron>.<up|down>.<ultra_local|noether|oneD>.SS.xx.yy.zz.tt.dat in the
+ * line formats of writeThrp_ASCII.  With qudaAmdSetLoopOutput(1) calcMG_loop_wOneD_TSM_EvenOdd contracts and writes the quark loops.
+ * HDF5 output, position-space correlators and the high-momenta form are not part of this library; gauge_param is accepted and ignored.
  */
 #ifndef _QUDAQKXTM_KEPLER_H
 #define _QUDAQKXTM_KEPLER_H
@@ -17,7 +22,11 @@
 #include <qudaQKXTM_Kepler_utils.h>
 
 /* for every source position info.sourcePosition[0 .. Nsources-1]: 12 Gaussian-smeared point sources x (up, down):
- * sink("prop_up" | "prop_dn", index = 12 * isource + spin * 3 + colour, flavour +1 | -1, source = NULL, solution) */
+ * sink("prop_up" | "prop_dn", index = 12 * isource + spin * 3 + colour, flavour +1 | -1, source = NULL, solution);
+ * with the three-point output on, after the 24 solves of a source with run3pt_src != 0, for every (its, ip, part):
+ * sink("seq_part1" | "seq_part2", index = ((isource * Ntsink + its) * Nproj[its] + ip) * 12 + column, flavour of the solve,
+ * the smeared sequential source, solution), in the order its, ip, part, column.  Where Nproj differs between the sink
+ * separations two (its, ip) pairs can share an index: tell them apart by the order of the calls. */
 void calcMG_threepTwop_EvenOdd(void **gaugeSmeared, void **gauge, QudaGaugeParam *gauge_param, QudaInvertParam *param, quda::qudaQKXTMinfo_Kepler info,
                                char *filename_twop, char *filename_threep, quda::WHICHPARTICLE NUCLEON);
 

@@ -23,6 +23,7 @@ namespace quda {
   enum FILE_WRITE_FORMAT { ASCII_FORM, HDF5_FORM };
   enum WHICHSPECTRUM { SR, LR, SM, LM, SI, LI };
   enum WHICHPARTICLE { PROTON, NEUTRON };
+  enum WHICHPROJECTOR { G4, G5G123, G5G1, G5G2, G5G3 };
 
   typedef struct {
     int nsmearAPE;

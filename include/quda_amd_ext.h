@@ -144,8 +144,10 @@ double qudaAmdMultigridTimeTransfer(void *mg_instance, int level, int what, int 
  * loop: for every spin-colour component of a point source, Gaussian-smear it with the APE-smeared links, solve for the up
  * quark (twist +, inv_param->preconditionerUP) and the down quark (twist -, preconditionerDN) with even-odd preconditioned
  * GCR, reconstruct, rescale by 2 kappa under mass normalisation.  The reference then contracts and writes its files; these
- * entry points hand the propagators back, and the two-point contractions below (qudaAmdContractTwop, qudaAmdSetTwopOutput)
- * compute the correlators on the device.  Three-point functions, loop contractions and HDF5 output are not part of the library.
+ * entry points hand the propagators back, and the contractions below compute the correlators on the device: two-point functions
+ * (qudaAmdContractTwop, qudaAmdSetTwopOutput), nucleon three-point functions by the fixed-sink method (qudaAmdThreepSeqSource,
+ * qudaAmdContractThreep, qudaAmdSetThreepOutput) and quark loops (qudaAmdContractLoop, qudaAmdSetLoopOutput).  HDF5 output is not
+ * part of the library.
  * Host layouts are the QKXTM ones: sites lexicographic x fastest (LOCAL lattice of the calling rank), vectors
  * iv*24 + (spin*3 + colour)*2 + re/im in the UKQCD basis (lib/qudaQKXTM_Vector_Kepler.cpp:72-81), smearing links
  * gauge_APE[dir][iv*18 + (row*3 + col)*2 + re/im] (lib/qudaQKXTM_Gauge_Kepler.cpp:73-89, what mapEvenOddToNormalGauge
@@ -230,6 +232,60 @@ void qudaAmdContractLoop(double *out, const void *h_solution, QudaInvertParam *p
 void qudaAmdSetLoopOutput(int enable);
 /* seconds of the last loop contraction on this rank (device events): phi, stencil (or the unfused chain), projection, all of it */
 void qudaAmdLoopLastTimings(double secs[4]);
+
+/* ---- nucleon three-point functions by the fixed-sink sequential method (reference lib/interface_quda.cpp:6560-6950) ----
+ * UKQCD basis, fp64.  s = +1 where the operator is inserted on the up quark, -1 on the down quark: proton part 1 up, part 2 down;
+ * neutron part 1 down, part 2 up.  Projectors (enum WHICHPROJECTOR of qudaQKXTM_Kepler_utils.h): G4 = (1 + g4)/4,
+ * G5Gk = (1 + g4) i g5 gk / 4, G5G123 their sum over k; the code uses G_tm = R_p G R_p, R_p = (1 + p i g5)/sqrt2, p = +1 proton,
+ * -1 neutron.
+ * Sequential source: U3 / D3 the up / down propagators, sink-smeared and not rotated; N[x; k, n] the nucleon Wick sum (diquark
+ * C g5 at source and sink, direct minus exchange term; the neutron with up and down exchanged), f(x) = sum_kn G_tm[n][k] N[x; k, n].
+ * Part 1 is the derivative of f with respect to the propagator of the flavour that occurs twice (both slots), part 2 with respect
+ * to the other; component (nu, c) of the source for column (nu', c') is sigma = df/dP[x; nu, nu'; c, c'].  The solver gets
+ * g5 conj(sigma) on the sink time slice (tsinkSource + t0) mod T, Gaussian-smeared, zero elsewhere.
+ * Contraction: y_(pi, b) the twelve sequential solutions, q[x; kappa, pi; a, b] = conj((g5 y_(pi, b))[x; kappa, a]), F the forward
+ * propagator of the inserted flavour, per site
+ *   S0[kappa][lambda] = sum q[x] F[x],  A_mu = sum q[x] U_mu(x) F[x + mu],  B_mu = sum q[x] U_mu(x - mu)^+ F[x - mu],
+ *   C_mu = sum q[x + mu] U_mu(x)^+ F[x],  D_mu = sum q[x - mu] U_mu(x - mu) F[x]     (sums over pi, b and the colours),
+ *   local[i] = tr O_i^T S0,  oneD[mu][i] = tr O_i^T ((A + D) - (B + C))_mu / 4,
+ *   noether[mu] = (tr (1 + g_mu)^T (B + C)_mu - tr (1 - g_mu)^T (A + D)_mu) / 4,
+ * O_i = s i g5, g1 .. g4, s i 1, g5g1 .. g5g4, s g5g1g2, s g5g1g3, s g5g2g3, s g5g4g1, s g5g4g2, s g5g4g3 (tr X^T Y = sum X[k][l] Y[k][l]),
+ * projected with sum_x e^{+2 pi i n.(x - x0)/L} (the sign opposite to the two-point functions) onto the momenta of
+ * qudaAmdTwopMomenta.  Time runs from the source (it = 0: global slice (it + t0) mod T); everything carries -1 when
+ * tsinkSource + t0 >= T. */
+typedef struct QudaAmdThreepParam_s {
+  int sourcePosition[4];   /* GLOBAL (x, y, z, t) */
+  int Q_sq;                /* momenta of the contraction */
+  int tsinkSource;         /* sink time slice relative to the source */
+  int projector;           /* enum WHICHPROJECTOR */
+  int particle;            /* enum WHICHPARTICLE: PROTON or NEUTRON */
+  int part;                /* 1 or 2 */
+  int nsmearGauss;         /* smearing of the propagators at the sink and of the sequential source; 0: none, gauge_APE may be NULL */
+  double alphaGauss;
+} QudaAmdThreepParam;
+/* h_prop_up / h_prop_dn: the 12 + 12 unsmeared columns as qudaAmdCalcMGPropagators returns them; h_out: the twelve vectors as
+ * they go to the solver (V * 24 doubles each, LOCAL lattice, lexicographic UKQCD).  A rank that does not own the sink slice gets zeros. */
+void qudaAmdThreepSeqSource(void *h_out, const void *h_prop_up, const void *h_prop_dn, void **gauge_APE, const QudaAmdThreepParam *p);
+/* h_seq: the twelve sequential solutions as the solver returns them (solved with the twist opposite to the inserted flavour);
+ * h_fwd: the twelve forward columns of the inserted flavour; gauge: the links of the derivative in the QKXTM lexicographic layout
+ * with the boundary condition already applied, or NULL for the resident precise links (fp64).  h_local [T][Nmoms][16],
+ * h_noether [T][Nmoms][4], h_oneD [T][Nmoms][4][16] complex, T global; any of them may be NULL; every rank receives the full result. */
+void qudaAmdContractThreep(double *h_local, double *h_noether, double *h_oneD, const void *h_seq, const void *h_fwd, void **gauge, const QudaAmdThreepParam *p);
+/* host-only queries of the spin tables, row-major 4 x 4 complex: O_i for the flavour sign s = +-1; G_tm of a projector and particle */
+void qudaAmdThreepOperator(int i, int s, double out[32]);
+void qudaAmdThreepProjector(int pid, int particle, double out[32]);
+/* off by default.  On: calcMG_threepTwop_EvenOdd runs, for every source with info.run3pt_src != 0, every sink separation
+ * info.tsinkSource[its < Ntsink], every projector info.proj_list[its][ip < Nproj[its]] and both parts: the sequential source from the
+ * device-resident forward solutions, twelve solves through the path of the forward solves (lockstep where it fits, one by one
+ * otherwise and with QUDA_AMD_QKXTM_LOCKSTEP=0) with the twist opposite to the inserted flavour, the contraction, and rank 0 writes the
+ * reference's three ASCII files <filename_threep>_tsink<t>_proj<info.thrp_proj_type[P]>.<proton|neutron>.<up|down>.
+ * <ultra_local|noether|oneD>.SS.xx.yy.zz.tt.dat (writeThrp_ASCII; a NULL thrp_proj_type entry falls back to the enumerator's name).
+ * Every sequential solution also goes to the solution sink as "seq_part1" / "seq_part2" with its smeared source.  CorrSpace =
+ * POSITION_SPACE and HighMomForm are errors; CorrFileFormat = HDF5_FORM warns and writes ASCII.  Off: no file, no extra solve, no
+ * extra sink call. */
+void qudaAmdSetThreepOutput(int enable);
+/* seconds of the last calls on this rank (device events): source construction, ghost exchange, stencil, projection */
+void qudaAmdThreepLastTimings(double secs[4]);
 
 /* ILDG gauge configurations in LIME containers (the step in front of loadGaugeQuda in the QKXTM drivers).  qudaAmdReadLimeGauge
  * has the semantics of readLimeGauge / readLimeGaugeSmeared (qkxtm/QKXTM_read_conf.h:107-400, :819-835): every rank reads the

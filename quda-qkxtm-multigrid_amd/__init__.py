@@ -135,6 +135,17 @@ class QudaAmdTwopParam(C.Structure):
     _fields_ = [("sourcePosition", C.c_int * 4), ("Q_sq", C.c_int), ("nsmearGauss", C.c_int), ("alphaGauss", C.c_double)]
 
 
+class QudaAmdThreepParam(C.Structure):
+    """include/quda_amd_ext.h: source, sink, projector and flavour assignment of the three-point functions"""
+    _fields_ = [("sourcePosition", C.c_int * 4), ("Q_sq", C.c_int), ("tsinkSource", C.c_int), ("projector", C.c_int), ("particle", C.c_int),
+                ("part", C.c_int), ("nsmearGauss", C.c_int), ("alphaGauss", C.c_double)]
+
+
+# include/qudaQKXTM_Kepler_utils.h: enum WHICHPARTICLE, enum WHICHPROJECTOR
+PROTON, NEUTRON = 0, 1
+G4, G5G123, G5G1, G5G2, G5G3 = 0, 1, 2, 3, 4
+
+
 def lib():
     """The loaded libquda.so; raises if the HIP extension has not been built (no fallback)."""
     global _lib
@@ -253,6 +264,18 @@ def lib():
         L.qudaAmdSetLoopOutput.restype = None
         L.qudaAmdLoopLastTimings.argtypes = [C.POINTER(_d)]
         L.qudaAmdLoopLastTimings.restype = None
+        L.qudaAmdThreepSeqSource.argtypes = [_p, _p, _p, C.POINTER(_p), C.POINTER(QudaAmdThreepParam)]
+        L.qudaAmdThreepSeqSource.restype = None
+        L.qudaAmdContractThreep.argtypes = [_p, _p, _p, _p, _p, C.POINTER(_p), C.POINTER(QudaAmdThreepParam)]
+        L.qudaAmdContractThreep.restype = None
+        L.qudaAmdThreepOperator.argtypes = [_i, _i, C.POINTER(_d)]
+        L.qudaAmdThreepOperator.restype = None
+        L.qudaAmdThreepProjector.argtypes = [_i, _i, C.POINTER(_d)]
+        L.qudaAmdThreepProjector.restype = None
+        L.qudaAmdSetThreepOutput.argtypes = [_i]
+        L.qudaAmdSetThreepOutput.restype = None
+        L.qudaAmdThreepLastTimings.argtypes = [C.POINTER(_d)]
+        L.qudaAmdThreepLastTimings.restype = None
         _lib = L
     return _lib
 
@@ -543,6 +566,75 @@ def contract_loop(solution, ip, Q_sq, L):
 def set_loop_output(enable):
     """qudaAmdSetLoopOutput: calcMG_loop_wOneD_TSM_EvenOdd contracts its solutions and writes the loop ASCII files"""
     lib().qudaAmdSetLoopOutput(int(bool(enable)))
+
+
+def _threep_param(source_position, Q_sq, tsink, projector, particle, part, nsmear, alpha):
+    p = QudaAmdThreepParam()
+    for k in range(4):
+        p.sourcePosition[k] = int(source_position[k])
+    p.Q_sq, p.tsinkSource, p.projector, p.particle, p.part = int(Q_sq), int(tsink), int(projector), int(particle), int(part)
+    p.nsmearGauss, p.alphaGauss = int(nsmear), float(alpha)
+    return p
+
+
+def threep_seq_source(prop_up, prop_dn, gauge_lex, source_position, tsink, projector, particle, part, nsmear, alpha):
+    """qudaAmdThreepSeqSource: the twelve sequential sources of the fixed-sink method, (12, V*24) lexicographic UKQCD, as they go to
+    the solver, from the unsmeared propagators of calc_mg_propagators.  tsink is relative to the source; particle PROTON / NEUTRON,
+    part 1 / 2, projector G4 .. G5G3"""
+    up = np.ascontiguousarray(prop_up, dtype=np.float64)
+    dn = np.ascontiguousarray(prop_dn, dtype=np.float64)
+    if up.shape != dn.shape or up.shape[0] != 12:
+        raise ValueError("prop_up / prop_dn must both be (12, V*24)")
+    p = _threep_param(source_position, 0, tsink, projector, particle, part, nsmear, alpha)
+    out = np.zeros_like(up)
+    keep, links = _lex_links(gauge_lex)
+    lib().qudaAmdThreepSeqSource(_vp(out), _vp(up), _vp(dn), links, C.byref(p))
+    return out
+
+
+def contract_threep(seq, fwd, gauge_lex, source_position, Q_sq, tsink, particle, part):
+    """qudaAmdContractThreep: seq the twelve sequential solutions, fwd the twelve forward columns of the inserted flavour (both
+    (12, V*24) lexicographic UKQCD), gauge_lex the links of the derivative with the boundary applied (None: the resident precise
+    links).  Returns (local (T, Nmoms, 16), noether (T, Nmoms, 4), oneD (T, Nmoms, 4, 16)) complex128, time relative to the source"""
+    y = np.ascontiguousarray(seq, dtype=np.float64)
+    f = np.ascontiguousarray(fwd, dtype=np.float64)
+    if y.shape != f.shape or y.shape[0] != 12:
+        raise ValueError("seq / fwd must both be (12, V*24)")
+    p = _threep_param(source_position, Q_sq, tsink, G4, particle, part, 0, 0.0)
+    T = lib().qudaAmdTwopTimeExtent()
+    nm = lib().qudaAmdTwopMomenta(int(Q_sq), None, 0)
+    local, noether, oneD = np.zeros((T, nm, 16, 2)), np.zeros((T, nm, 4, 2)), np.zeros((T, nm, 4, 16, 2))
+    keep, links = _lex_links(gauge_lex)
+    lib().qudaAmdContractThreep(_vp(local), _vp(noether), _vp(oneD), _vp(y), _vp(f), links, C.byref(p))
+    return local[..., 0] + 1j * local[..., 1], noether[..., 0] + 1j * noether[..., 1], oneD[..., 0] + 1j * oneD[..., 1]
+
+
+def threep_operator(i, s):
+    """qudaAmdThreepOperator: the insertion O_i (i = 0 .. 15) for the flavour sign s = +-1 as a 4 x 4 complex matrix; host only"""
+    a = (_d * 32)()
+    lib().qudaAmdThreepOperator(int(i), int(s), a)
+    v = np.array(a[:]).reshape(4, 4, 2)
+    return v[..., 0] + 1j * v[..., 1]
+
+
+def threep_projector(pid, particle):
+    """qudaAmdThreepProjector: the projector in the twisted basis, R_p G R_p, as a 4 x 4 complex matrix; host only"""
+    a = (_d * 32)()
+    lib().qudaAmdThreepProjector(int(pid), int(particle), a)
+    v = np.array(a[:]).reshape(4, 4, 2)
+    return v[..., 0] + 1j * v[..., 1]
+
+
+def set_threep_output(enable):
+    """qudaAmdSetThreepOutput: calcMG_threepTwop_EvenOdd runs the sequential solves and writes the three-point ASCII files"""
+    lib().qudaAmdSetThreepOutput(int(bool(enable)))
+
+
+def threep_last_timings():
+    """qudaAmdThreepLastTimings: seconds of the last calls: dict(source, ghost, stencil, projection)"""
+    a = (_d * 4)()
+    lib().qudaAmdThreepLastTimings(a)
+    return dict(source=a[0], ghost=a[1], stencil=a[2], projection=a[3])
 
 
 def loop_last_timings():

@@ -29,6 +29,7 @@
 
 #include "basis.h"
 #include "device_io.h"
+#include "gamma_host.h"
 #include "interface_internal.h"
 #include "lex_index.h"
 #include "qa_core.h"
@@ -229,28 +230,7 @@ __global__ void __launch_bounds__(64) baryon_kernel(double2 *out, const double2 
 #undef PR
 
 // ================================ host: gamma algebra, term lists ================================
-typedef std::complex<double> cd;
-struct M4 { cd a[4][4]; };
-static M4 mzero() { M4 m; for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) m.a[i][j] = 0; return m; }
-static M4 mid4() { M4 m = mzero(); for (int i = 0; i < 4; i++) m.a[i][i] = 1; return m; }
-static M4 operator*(const M4 &x, const M4 &y) {
-  M4 r = mzero();
-  for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) for (int k = 0; k < 4; k++) r.a[i][j] += x.a[i][k] * y.a[k][j];
-  return r;
-}
-static M4 transpose(const M4 &x) { M4 r; for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) r.a[i][j] = x.a[j][i]; return r; }
-static M4 dagger(const M4 &x) { M4 r; for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) r.a[i][j] = std::conj(x.a[j][i]); return r; }
-
-// UKQCD basis: g_k = [[0, i s_k], [-i s_k, 0]], g4 = diag(1, 1, -1, -1), g5 = g1 g2 g3 g4 = [[0, 1], [1, 0]]
-static M4 gammaU(int mu) {
-  const cd I(0, 1);
-  const cd s[3][2][2] = {{{0, 1}, {1, 0}}, {{0, -I}, {I, 0}}, {{1, 0}, {0, -1}}};
-  M4 g = mzero();
-  if (mu == 4) { g.a[0][0] = g.a[1][1] = 1; g.a[2][2] = g.a[3][3] = -1; return g; }
-  if (mu == 5) return gammaU(1) * gammaU(2) * gammaU(3) * gammaU(4);
-  for (int i = 0; i < 2; i++) for (int j = 0; j < 2; j++) { g.a[i][2 + j] = I * s[mu - 1][i][j]; g.a[2 + i][j] = -I * s[mu - 1][i][j]; }
-  return g;
-}
+using namespace gammah;   // M4, gammaU and the matrix helpers (gamma_host.h)
 
 static void toSPerm(const M4 &m, int col[4], double2 val[4]) {
   for (int r = 0; r < 4; r++) {
@@ -385,6 +365,7 @@ struct TwopProps {
 
 TwopProps *twopPropsCreate(const LatticeGeom &g) { return new TwopProps(g); }
 void twopPropsDestroy(TwopProps *p) { delete p; }
+double2 *twopPropsData(TwopProps &p, int fl) { return p.P[fl]; }
 
 // column isc = nu * 3 + b of flavour fl from a full fp64 device spinor: sink smearing (colour only, any spin basis), basis change to
 // UKQCD if the field is in the device basis, scale

@@ -5,8 +5,8 @@
 // Reference: calcMG_threepTwop_EvenOdd (lib/interface_quda.cpp:6018-6531; the same loop opens calcMG_loop_wOneD_TSM_*,
 // :7093, :8535), QKXTM_Vector_Kepler::gaussianSmearing (lib/qudaQKXTM_Vector_Kepler.cpp:386-421),
 // lib/code_pieces_Kepler/Gauss_core_Kepler.h, uploadToCuda / downloadFromCuda (lib/qudaQKXTM_Kepler_kernels.cu:972-1056).
-// Contractions, momentum projection and the HDF5 / ASCII writers that follow the loop in the reference are out of scope
-// (SURVEY 2 row 20): the caller gets the propagators instead.
+// The contractions and ASCII writers that follow the loop in the reference live in contract.hip (two-point functions), threep.hip
+// (three-point functions) and loop.hip; HDF5 output is out of scope.
 //
 // Everything stays on the device between the point source and the finished propagator:
 //  * smearing acts on colour only, so ONE smearing pass per source position serves all twelve spin-colour sources: the
@@ -93,13 +93,18 @@ void lexToDevice(ColorSpinorField &dst, const double *h_lex, const LatticeGeom &
   const size_t bytes = (size_t)g.V * 24 * sizeof(double);
   double *stage = (double *)stagingBuffer(bytes);
   HIP_CHECK(hipMemcpyAsync(stage, h_lex, bytes, hipMemcpyHostToDevice, computeStream()));
-  hipLaunchKernelGGL(lex_to_dev_kernel, dim3((g.Vh + 255) / 256, 2), dim3(256), 0, computeStream(), (double *)dst.V(), dst.Stride(), parityDoubles(dst), stage, g.Vh, g.Xh,
+  deviceLexToField(dst, stage, g, ukqcd);
+}
+
+void deviceLexToField(ColorSpinorField &dst, const double *d_lex, const LatticeGeom &g, bool ukqcd) {
+  checkFullDouble(dst);
+  hipLaunchKernelGGL(lex_to_dev_kernel, dim3((g.Vh + 255) / 256, 2), dim3(256), 0, computeStream(), (double *)dst.V(), dst.Stride(), parityDoubles(dst), d_lex, g.Vh, g.Xh,
                      g.X[1], g.X[2], ukqcd ? BASIS_UKQCD_TO_DR : BASIS_NONE);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(computeStream()));
 }
 
-static void deviceToLex(double *h_lex, const ColorSpinorField &src, const LatticeGeom &g, bool ukqcd, double scale) {
+void deviceToLex(double *h_lex, const ColorSpinorField &src, const LatticeGeom &g, bool ukqcd, double scale) {
   checkFullDouble(src);
   const size_t bytes = (size_t)g.V * 24 * sizeof(double);
   double *stage = (double *)stagingBuffer(bytes);
@@ -333,6 +338,85 @@ void calcMGPropagatorsEach(void **gauge_APE, QudaInvertParam *param, const QudaA
   delete d; delete dSloppy; delete dPre;
   if (gauge_APE) delete Uape;
 }
+
+// Twelve given sources of ONE twist flavour (+1 up, -1 down; full fp64 device fields in the device basis) through the path of the forward
+// solves above: one lockstep solve where the solver is multigrid-preconditioned GCR and lockstepFits allows it, one by one otherwise.
+// Every reconstructed solution is handed to `done` unscaled, with the factor of the normalisation.  param->secs / gflops / iter are
+// those of these twelve solves.
+void solveTwelveEach(QudaInvertParam *param, int flavorSign, ColorSpinorField *const sources[12], const char *fname,
+                     void (*done)(void *ctx, int isc, ColorSpinorField &result, double scale), void *ctx) {
+  checkCalcParam(param, fname);
+  const bool flag_eo = param->matpc_type == QUDA_MATPC_EVEN_EVEN;
+  const LatticeGeom &g = residentGeom();
+  const QudaTwistFlavorType flavor = flavorSign > 0 ? QUDA_TWIST_PLUS : QUDA_TWIST_MINUS;
+  param->twist_flavor = flavor;
+  param->preconditioner = flavorSign > 0 ? param->preconditionerUP : param->preconditionerDN;
+  const bool pc_solve = true;
+  DiracParam dp, dpSloppy, dpPre;
+  setDiracParam(dp, param, pc_solve);
+  setDiracSloppyParam(dpSloppy, param, pc_solve);
+  setDiracPreParam(dpPre, param, pc_solve);
+  Dirac *d = Dirac::create(dp), *dSloppy = Dirac::create(dpSloppy), *dPre = Dirac::create(dpPre);
+  Dirac &dirac = *d;
+  DiracM m(dirac), mSloppy(*dSloppy), mPre(*dPre);
+  ColorSpinorParam cp64 = deviceSpinorParam(QUDA_DOUBLE_PRECISION, QUDA_FULL_SITE_SUBSET, flavor);
+  cp64.create = QUDA_ZERO_FIELD_CREATE;
+  ColorSpinorField result(cp64);
+  ColorSpinorParam cp = deviceSpinorParam(param->cuda_prec, QUDA_FULL_SITE_SUBSET, flavor);
+  cp.create = QUDA_ZERO_FIELD_CREATE;
+  const double scale = (param->mass_normalization == QUDA_MASS_NORMALIZATION || param->mass_normalization == QUDA_ASYMMETRIC_MASS_NORMALIZATION) ? 2.0 * param->kappa : 1.0;
+  double secs = 0, gflops = 0;
+  int iters = 0;
+  const bool lockstep = param->inv_type == QUDA_GCR_INVERTER && param->inv_type_precondition == QUDA_MG_INVERTER && param->preconditionerUP && param->preconditionerDN &&
+                        param->use_init_guess != QUDA_USE_INIT_GUESS_YES && lockstepFits(12, param, g);
+  if (lockstep) {
+    std::vector<ColorSpinorField *> bs(12), xs(12), ins(12), outs(12);
+    for (int isc = 0; isc < 12; isc++) {
+      bs[isc] = new ColorSpinorField(cp); xs[isc] = new ColorSpinorField(cp);
+      *bs[isc] = *sources[isc];
+      bs[isc]->changeTwist(flavor); xs[isc]->changeTwist(flavor);
+      blas::zero(*xs[isc]);
+      dirac.prepare(ins[isc], outs[isc], *xs[isc], *bs[isc], param->solution_type);
+      ins[isc]->changeTwist(flavor); outs[isc]->changeTwist(flavor);
+    }
+    param->secs = 0; param->gflops = 0; param->iter = 0;
+    SolverParam sp(*param);
+    MG *K = static_cast<multigrid_solver *>(param->preconditioner)->mg;
+    const MultiSrcSolve res = solveMultiSrcGCR(outs, ins, m, mSloppy, K, sp, dSloppy);
+    secs += res.secs; iters += 12 * res.iter;
+    double worst = 0;
+    for (int isc = 0; isc < 12; isc++) worst = std::max(worst, sqrt(res.r2[isc] / res.b2[isc]));
+    param->true_res = worst;
+    for (int isc = 0; isc < 12; isc++) {
+      dirac.reconstruct(*xs[isc], *bs[isc], param->solution_type);
+      result = *xs[isc];
+      done(ctx, isc, result, scale);
+      delete bs[isc]; delete xs[isc];
+    }
+  } else {
+    ColorSpinorField b(cp), x(cp);
+    for (int isc = 0; isc < 12; isc++) {
+      b = *sources[isc];
+      b.changeTwist(flavor); x.changeTwist(flavor);
+      ColorSpinorField *in = nullptr, *out = nullptr;
+      dirac.prepare(in, out, x, b, param->solution_type);
+      param->secs = 0; param->gflops = 0; param->iter = 0;
+      SolverParam sp(*param);
+      Solver *solve = Solver::create(sp, m, mSloppy, mPre);
+      *out = flag_eo ? sources[isc]->Even() : sources[isc]->Odd();   // the source on the solve parity is the initial guess, as for the forward solves
+      out->changeTwist(flavor);
+      (*solve)(*out, *in);
+      sp.updateInvertParam(*param);
+      secs += param->secs; gflops += param->gflops; iters += param->iter;
+      dirac.reconstruct(x, b, param->solution_type);
+      delete solve;
+      result = x;
+      done(ctx, isc, result, scale);
+    }
+  }
+  param->secs = secs; param->gflops = gflops; param->iter = iters;
+  delete d; delete dSloppy; delete dPre;
+}
 }  // namespace quda
 
 extern "C" {
@@ -551,18 +635,34 @@ extern "C" void qudaAmdSetSolutionSink(QudaAmdSolutionSink sink, void *ctx) { qu
 
 void calcMG_threepTwop_EvenOdd(void **gaugeSmeared, void **gauge, QudaGaugeParam *gauge_param, QudaInvertParam *param, quda::qudaQKXTMinfo_Kepler info,
                                char *filename_twop, char *filename_threep, quda::WHICHPARTICLE NUCLEON) {
-  (void)gauge; (void)gauge_param; (void)filename_threep; (void)NUCLEON;   // consumed by the three-point stage only
-  if (info.Nsources < 0 || info.Nsources > MAX_NSOURCES) errorQuda("calcMG_threepTwop_EvenOdd: Nsources = %d", info.Nsources);
-  // two-point output (qudaAmdSetTwopOutput): contractions from the device-resident solutions, the reference's ASCII files
-  const bool twop = quda::twopOutputEnabled();
-  if (twop) {
+  (void)gauge_param;
+  const char *fname = "calcMG_threepTwop_EvenOdd";
+  if (info.Nsources < 0 || info.Nsources > MAX_NSOURCES) errorQuda("%s: Nsources = %d", fname, info.Nsources);
+  // two-point output (qudaAmdSetTwopOutput): contractions from the device-resident solutions, the reference's ASCII files;
+  // three-point output (qudaAmdSetThreepOutput): the fixed-sink sequential solves and contractions of the sources with run3pt_src != 0
+  const bool twop = quda::twopOutputEnabled(), threep = quda::threepOutputEnabled();
+  if (twop || threep) {
     if (info.CorrSpace == quda::POSITION_SPACE)
-      errorQuda("calcMG_threepTwop_EvenOdd: position-space correlators are written only as HDF5, which this library does not link; use CorrSpace = MOMENTUM_SPACE");
-    if (info.HighMomForm)
-      errorQuda("calcMG_threepTwop_EvenOdd: the high-momenta form is written only as HDF5, which this library does not link; set HighMomForm = false");
-    if (info.CorrFileFormat == quda::HDF5_FORM) warningQuda("calcMG_threepTwop_EvenOdd: HDF5 is not linked into this library; writing the two-point functions in ASCII format");
-    if (!filename_twop) errorQuda("calcMG_threepTwop_EvenOdd: filename_twop is NULL");
-    if (info.Q_sq < 0) errorQuda("calcMG_threepTwop_EvenOdd: Q_sq = %d", info.Q_sq);
+      errorQuda("%s: position-space correlators are written only as HDF5, which this library does not link; use CorrSpace = MOMENTUM_SPACE", fname);
+    if (info.HighMomForm) errorQuda("%s: the high-momenta form is written only as HDF5, which this library does not link; set HighMomForm = false", fname);
+    if (info.CorrFileFormat == quda::HDF5_FORM) warningQuda("%s: HDF5 is not linked into this library; writing the correlation functions in ASCII format", fname);
+    if (twop && !filename_twop) errorQuda("%s: filename_twop is NULL", fname);
+    if (info.Q_sq < 0) errorQuda("%s: Q_sq = %d", fname, info.Q_sq);
+  }
+  static const char *const projName[MAX_PROJS] = {"G4", "G5G123", "G5G1", "G5G2", "G5G3"};
+  quda::GaugeField *Uder = nullptr;   // the links of the derivative operators and the conserved current
+  if (threep) {
+    if (!filename_threep) errorQuda("%s: filename_threep is NULL", fname);
+    if (NUCLEON != quda::PROTON && NUCLEON != quda::NEUTRON) errorQuda("%s: NUCLEON = %d (proton and neutron only)", fname, (int)NUCLEON);
+    if (info.Ntsink < 0 || info.Ntsink > MAX_TSINK) errorQuda("%s: Ntsink = %d", fname, info.Ntsink);
+    for (int its = 0; its < info.Ntsink; its++) {
+      if (info.Nproj[its] < 0 || info.Nproj[its] > MAX_PROJS) errorQuda("%s: Nproj[%d] = %d", fname, its, info.Nproj[its]);
+      for (int ip = 0; ip < info.Nproj[its]; ip++)
+        if (info.proj_list[its][ip] < 0 || info.proj_list[its][ip] >= MAX_PROJS) errorQuda("%s: proj_list[%d][%d] = %d", fname, its, ip, info.proj_list[its][ip]);
+    }
+    bool any = false;
+    for (int isource = 0; isource < info.Nsources; isource++) any = any || info.run3pt_src[isource] != 0;
+    if (any) Uder = gauge ? quda::loadLexGauge(gauge, quda::residentGeom()) : gaugePrecise;
   }
   double secs = 0, gflops = 0;
   int iters = 0;
@@ -571,43 +671,103 @@ void calcMG_threepTwop_EvenOdd(void **gaugeSmeared, void **gauge, QudaGaugeParam
     for (int k = 0; k < 4; k++) src.sourcePosition[k] = info.sourcePosition[isource][k];
     src.nsmearGauss = info.nsmearGauss;
     src.alphaGauss = info.alphaGauss;
+    const bool do3 = threep && info.run3pt_src[isource] != 0;
     struct Ctx {
       int base;
-      quda::TwopProps *props;
+      quda::TwopProps *props;    // the two-point stage rotates these in place
+      quda::TwopProps *sprops;   // sink-smeared, unrotated: what the sequential source is built from
+      quda::ColorSpinorField **fwd;   // [2][12]: the unsmeared forward columns in the UKQCD basis, what the three-point contraction reads
       quda::ColorSpinorField *work;
       quda::GaugeField *U;
       int nsmear;
       double alpha;
-    } ctx = {12 * isource, nullptr, nullptr, nullptr, info.nsmearGauss, info.alphaGauss};
+    } ctx = {12 * isource, nullptr, nullptr, nullptr, nullptr, nullptr, info.nsmearGauss, info.alphaGauss};
     const quda::LatticeGeom &g = quda::residentGeom();
-    if (twop) {
-      if (info.nsmearGauss > 0 && !gaugeSmeared && !quda::gaugeSmeared) errorQuda("calcMG_threepTwop_EvenOdd: gaugeSmeared is NULL and no smeared field is resident (performAPEnStep)");
+    std::vector<quda::ColorSpinorField *> fwd;
+    if (twop || do3) {
+      if (info.nsmearGauss > 0 && !gaugeSmeared && !quda::gaugeSmeared) errorQuda("%s: gaugeSmeared is NULL and no smeared field is resident (performAPEnStep)", fname);
       ctx.U = info.nsmearGauss > 0 ? (gaugeSmeared ? quda::loadLexGauge(gaugeSmeared, g) : quda::gaugeSmeared) : nullptr;
-      ctx.props = quda::twopPropsCreate(g);
+      if (twop) ctx.props = quda::twopPropsCreate(g);
       quda::ColorSpinorParam cp = quda::deviceSpinorParam(QUDA_DOUBLE_PRECISION, QUDA_FULL_SITE_SUBSET, QUDA_TWIST_NO);
       cp.create = QUDA_ZERO_FIELD_CREATE;
       ctx.work = new quda::ColorSpinorField(cp);
+      if (do3) {
+        ctx.sprops = quda::twopPropsCreate(g);
+        for (int k = 0; k < 24; k++) fwd.push_back(new quda::ColorSpinorField(cp));
+        ctx.fwd = fwd.data();
+      }
     }
     quda::calcMGPropagatorsEach(
-        gaugeSmeared, param, &src, "calcMG_threepTwop_EvenOdd",
+        gaugeSmeared, param, &src, fname,
         [](void *c, int isc, int flavor, const double *h, size_t n) { quda::toSink(flavor > 0 ? "prop_up" : "prop_dn", ((Ctx *)c)->base + isc, flavor, nullptr, h, n); }, &ctx,
-        twop ? +[](void *c, int isc, int flavor, quda::ColorSpinorField &x, double scale) {
+        (twop || do3) ? +[](void *c, int isc, int flavor, quda::ColorSpinorField &x, double scale) {
           Ctx *o = (Ctx *)c;
+          const int fl = flavor > 0 ? 0 : 1;
+          if (o->fwd) quda::threepToUkqcd(*o->fwd[fl * 12 + isc], x, scale);   // before the sink smearing, from the solution itself
           quda::blas::copy(*o->work, x);   // the solution itself still goes to the sink unsmeared
-          quda::twopAbsorbColumn(*o->props, flavor > 0 ? 0 : 1, isc, *o->work, quda::residentGeom(), o->U, o->nsmear, o->alpha, true, scale);
+          bool smeared = false;
+          if (o->props) { quda::twopAbsorbColumn(*o->props, fl, isc, *o->work, quda::residentGeom(), o->U, o->nsmear, o->alpha, true, scale); smeared = true; }
+          if (o->sprops) quda::twopAbsorbColumn(*o->sprops, fl, isc, *o->work, quda::residentGeom(), smeared ? nullptr : o->U, o->nsmear, o->alpha, true, scale);
         } : nullptr);
     secs += param->secs; gflops += param->gflops; iters += param->iter;
+    const int T = g.X[3] * quda::commGrid().dims[3];
+    const int Nm = (twop || do3) ? qudaAmdTwopMomenta(info.Q_sq, nullptr, 0) : 0;
     if (twop) {
-      const int T = g.X[3] * quda::commGrid().dims[3];
-      const int Nm = qudaAmdTwopMomenta(info.Q_sq, nullptr, 0);
       std::vector<double> mes((size_t)T * Nm * 2 * 10 * 2), bar((size_t)T * Nm * 2 * 10 * 16 * 2);
       quda::twopContract(*ctx.props, g, src.sourcePosition, info.Q_sq, mes.data(), bar.data());
       quda::twopWriteAscii(filename_twop, src.sourcePosition, info.Q_sq, T, mes.data(), bar.data());
-      delete ctx.work;
       quda::twopPropsDestroy(ctx.props);
+    }
+    if (do3) {
+      // fixed-sink stage (reference :6560-6950): for every sink separation, projector and part the sequential source, twelve solves
+      // with the twist opposite to the inserted flavour, the contraction with the forward propagator of that flavour, three files
+      quda::ColorSpinorParam cp = quda::deviceSpinorParam(QUDA_DOUBLE_PRECISION, QUDA_FULL_SITE_SUBSET, QUDA_TWIST_NO);
+      cp.create = QUDA_ZERO_FIELD_CREATE;
+      quda::ColorSpinorField *seqSrc[12], *seqSol[12];
+      for (int k = 0; k < 12; k++) { seqSrc[k] = new quda::ColorSpinorField(cp); seqSol[k] = new quda::ColorSpinorField(cp); }
+      const size_t vec = (size_t)g.V * 24;
+      std::vector<double> h_src(vec), h_sol(vec), loc((size_t)T * Nm * 16 * 2), noe((size_t)T * Nm * 4 * 2), oneD((size_t)T * Nm * 64 * 2);
+      QudaAmdThreepParam tp;
+      for (int k = 0; k < 4; k++) tp.sourcePosition[k] = src.sourcePosition[k];
+      tp.Q_sq = info.Q_sq; tp.particle = (int)NUCLEON; tp.nsmearGauss = info.nsmearGauss; tp.alphaGauss = info.alphaGauss;
+      for (int its = 0; its < info.Ntsink; its++)
+        for (int ip = 0; ip < info.Nproj[its]; ip++)
+          for (int part = 1; part <= 2; part++) {
+            tp.tsinkSource = info.tsinkSource[its]; tp.projector = info.proj_list[its][ip]; tp.part = part;
+            if (tp.tsinkSource < 0 || tp.tsinkSource >= T) errorQuda("%s: tsinkSource[%d] = %d", fname, its, tp.tsinkSource);
+            quda::threepSeqSourceDevice(seqSrc, *ctx.sprops, ctx.U, &tp);
+            const int s = quda::threepInsertedFlavor(tp.particle, part);
+            struct SeqCtx {
+              const char *kind;
+              int base, flavor;
+              quda::ColorSpinorField **src, **sol;
+              double *h_src, *h_sol;
+              size_t vec;
+            } sc = {part == 1 ? "seq_part1" : "seq_part2", ((isource * info.Ntsink + its) * info.Nproj[its] + ip) * 12, -s, seqSrc, seqSol, h_src.data(), h_sol.data(), vec};
+            quda::solveTwelveEach(param, -s, seqSrc, fname, [](void *c, int isc, quda::ColorSpinorField &x, double scale) {
+              SeqCtx *o = (SeqCtx *)c;
+              const quda::LatticeGeom &gg = quda::residentGeom();
+              quda::threepToUkqcd(*o->sol[isc], x, scale);
+              quda::deviceToLex(o->h_src, *o->src[isc], gg, true, 1.0);
+              quda::deviceToLex(o->h_sol, x, gg, true, scale);
+              quda::toSink(o->kind, o->base + isc, o->flavor, o->h_src, o->h_sol, o->vec);
+            }, &sc);
+            secs += param->secs; gflops += param->gflops; iters += param->iter;
+            quda::threepContract(loc.data(), noe.data(), oneD.data(), seqSol, ctx.fwd + (s > 0 ? 0 : 12), *Uder, &tp);
+            const char *pname = info.thrp_proj_type[tp.projector] ? info.thrp_proj_type[tp.projector] : projName[tp.projector];
+            const std::string out = std::string(filename_threep) + "_tsink" + std::to_string(tp.tsinkSource) + "_proj" + pname;
+            quda::threepWriteAscii(out.c_str(), &tp, T, loc.data(), noe.data(), oneD.data());
+          }
+      for (int k = 0; k < 12; k++) { delete seqSrc[k]; delete seqSol[k]; }
+      quda::twopPropsDestroy(ctx.sprops);
+      for (quda::ColorSpinorField *f : fwd) delete f;
+    }
+    if (twop || do3) {
+      delete ctx.work;
       if (ctx.U && gaugeSmeared) delete ctx.U;
     }
   }
+  if (Uder && gauge) delete Uder;
   param->secs = secs; param->gflops = gflops; param->iter = iters;
 }
 

@@ -1,4 +1,4 @@
-// qkxtm_internal.h — what the translation units of the QKXTM drivers (qkxtm.hip, contract.hip, loop.hip, momproj.hip) call across
+// qkxtm_internal.h — what the translation units of the QKXTM drivers (qkxtm.hip, contract.hip, loop.hip, threep.hip, momproj.hip) call across
 // each other.  No .hip file declares another file's function itself.
 #pragma once
 
@@ -6,6 +6,7 @@
 
 #include "interface_internal.h"
 #include "qa_core.h"
+#include "quda_amd_ext.h"
 
 namespace quda {
 
@@ -17,8 +18,12 @@ void *stagingBuffer(size_t bytes);   // the library's one grow-only device buffe
 
 // ---- qkxtm.hip ----
 void lexToDevice(ColorSpinorField &dst, const double *h_lex, const LatticeGeom &g, bool ukqcd);
+void deviceLexToField(ColorSpinorField &dst, const double *d_lex, const LatticeGeom &g, bool ukqcd);   // the same from a device buffer
+void deviceToLex(double *h_lex, const ColorSpinorField &src, const LatticeGeom &g, bool ukqcd, double scale);
 GaugeField *loadLexGauge(void **gauge_lex, const LatticeGeom &g);
 void gaussianSmear(ColorSpinorField &v, const GaugeField &U, double alpha, int nsmear);
+void solveTwelveEach(QudaInvertParam *param, int flavorSign, ColorSpinorField *const sources[12], const char *fname,
+                     void (*done)(void *ctx, int isc, ColorSpinorField &result, double scale), void *ctx);
 
 // ---- contract.hip: two-point functions ----
 struct TwopProps;
@@ -26,6 +31,7 @@ bool twopOutputEnabled();
 std::vector<int> twopMomenta(int Q_sq);
 TwopProps *twopPropsCreate(const LatticeGeom &g);
 void twopPropsDestroy(TwopProps *p);
+double2 *twopPropsData(TwopProps &p, int fl);   // P[(mu * 4 + nu) * 9 + a * 3 + b][site] of flavour fl
 void twopAbsorbColumn(TwopProps &props, int fl, int isc, ColorSpinorField &v, const LatticeGeom &g, const GaugeField *U, int nsmear, double alpha, bool deviceBasis, double scale);
 void twopContract(TwopProps &props, const LatticeGeom &g, const int src[4], int Q_sq, double *h_mes, double *h_bar);
 void twopWriteAscii(const char *fname_twop, const int src[4], int Q_sq, int T, const double *h_mes, const double *h_bar);
@@ -40,6 +46,16 @@ void loopAccumDestroy(LoopAccum *A);
 void loopContractAdd(LoopAccum &A, ColorSpinorField &x, QudaInvertParam *param);
 void loopAccumGet(const LoopAccum &A, double *out);
 void loopWriteAscii(const LoopAccum &A, const char *pref, const char *tsmTag, int nnnn);
+
+// ---- threep.hip: three-point functions by the fixed-sink method ----
+bool threepOutputEnabled();
+int threepInsertedFlavor(int particle, int part);   // +1 up, -1 down
+void threepToUkqcd(ColorSpinorField &ukqcd, const ColorSpinorField &dev, double scale);
+void threepSeqSourceDevice(ColorSpinorField *const src[12], TwopProps &props, const GaugeField *Uape, const QudaAmdThreepParam *p);
+void threepWriteAscii(const char *filename_out, const QudaAmdThreepParam *p, int T, const double *h_local, const double *h_noether, const double *h_oneD);
+void threepSeqSource(double *h_out, const double *h_up, const double *h_dn, const GaugeField *Uape, const QudaAmdThreepParam *p);
+void threepContract(double *h_local, double *h_noether, double *h_oneD, ColorSpinorField *const y[12], ColorSpinorField *const F[12], const GaugeField &U,
+                    const QudaAmdThreepParam *p);
 
 // ---- momproj.hip: the tail both contractions share ----
 // Project the staged blocks cs[nblk][nt * Vs][16] (complex; Vs = X[0] X[1] X[2] sites per slice, x fastest) of the local time slices
