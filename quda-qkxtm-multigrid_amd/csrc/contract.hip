@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "basis.h"
+#include "contract_stencil.h"
 #include "device_io.h"
 #include "gamma_host.h"
 #include "interface_internal.h"
@@ -65,7 +66,6 @@ __constant__ SPerm c_mes[NMES];
 __constant__ Term c_terms[MAX_TERMS];
 __constant__ Channel c_chan[NBAR];
 
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ double2 cmulc(double2 a, double2 b) { return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }   // a conj(b)
 __device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ double2 cscale(double s, double2 a) { return make_double2(s * a.x, s * a.y); }
@@ -112,8 +112,6 @@ __global__ void __launch_bounds__(256) field_to_prop_kernel(double2 *P, long V, 
     for (int a = 0; a < 3; a++) P[((mu * 4 + nu) * 9 + a * 3 + b) * V + site] = make_double2(scale * s[(mu * 3 + a) * 2], scale * s[(mu * 3 + a) * 2 + 1]);
 }
 
-#define PR(p, s, t, c, d) (p)[(((s) * 4 + (t)) * 9 + (c) * 3 + (d)) * V + site]
-
 // ---- mesons: out[flavour][s][channel], sites of one time slice ----
 __global__ void __launch_bounds__(128) meson_kernel(double2 *out, const double2 *P0, const double2 *P1, long V, int Vs, int t) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -139,9 +137,6 @@ __global__ void __launch_bounds__(128) meson_kernel(double2 *out, const double2 
 }
 
 // ---- baryons: out[2 + flavour * 10 + channel][s][gamma * 4 + gamma'] ----
-__constant__ int c_eps[6][3] = {{0, 1, 2}, {1, 2, 0}, {2, 0, 1}, {0, 2, 1}, {2, 1, 0}, {1, 0, 2}};
-__constant__ double c_eps_sign[6] = {1, 1, 1, -1, -1, -1};
-
 __global__ void __launch_bounds__(64) baryon_kernel(double2 *out, const double2 *P0, const double2 *P1, long V, int Vs, int t) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= Vs) return;
@@ -170,19 +165,19 @@ __global__ void __launch_bounds__(64) baryon_kernel(double2 *out, const double2 
 #pragma unroll
         for (int x = 0; x < 4; x++)
 #pragma unroll
-          for (int y = 0; y < 4; y++) D[x][y] = cmul(cmul(T.aval[x], T.bval[y]), PR(Pm, T.acol[x], T.brow[y], cm, cmp));
+          for (int y = 0; y < 4; y++) D[x][y] = cmul(cmul(T.aval[x], T.bval[y]), Pm[prop_index(T.acol[x], T.brow[y], cm, cmp, V, site)]);
         if (!T.chain) {
           // the open spins on one propagator: sum_xy D_xy Q_xy times P_{gamma gamma'}
           double2 sc = make_double2(0, 0);
 #pragma unroll
           for (int x = 0; x < 4; x++)
 #pragma unroll
-            for (int y = 0; y < 4; y++) sc = cadd(sc, cmul(D[x][y], PR(Pp, x, y, cp, cpp)));
+            for (int y = 0; y < 4; y++) sc = cadd(sc, cmul(D[x][y], Pp[prop_index(x, y, cp, cpp, V, site)]));
           sc = cscale(w, sc);
 #pragma unroll
           for (int g = 0; g < 4; g++)
 #pragma unroll
-            for (int gp = 0; gp < 4; gp++) acc[g][gp] = cadd(acc[g][gp], cmul(sc, PR(Po, g, gp, co, cop)));
+            for (int gp = 0; gp < 4; gp++) acc[g][gp] = cadd(acc[g][gp], cmul(sc, Po[prop_index(g, gp, co, cop, V, site)]));
         } else {
           // (Y D^T Z)_{gamma gamma'}: Y = P_{gamma y} of the sink gamma quark, Z = P_{x gamma'} of the quark that reaches gamma'
           double2 E[4][4];   // E_{y gp} = sum_x D_xy Z_{x gp}
@@ -192,14 +187,14 @@ __global__ void __launch_bounds__(64) baryon_kernel(double2 *out, const double2 
             for (int gp = 0; gp < 4; gp++) {
               double2 e = make_double2(0, 0);
 #pragma unroll
-              for (int x = 0; x < 4; x++) e = cadd(e, cmul(D[x][y], PR(Pp, x, gp, cp, cpp)));
+              for (int x = 0; x < 4; x++) e = cadd(e, cmul(D[x][y], Pp[prop_index(x, gp, cp, cpp, V, site)]));
               E[y][gp] = e;
             }
 #pragma unroll
           for (int g = 0; g < 4; g++) {
             double2 Yg[4];
 #pragma unroll
-            for (int y = 0; y < 4; y++) Yg[y] = cscale(w, PR(Po, g, y, co, cop));
+            for (int y = 0; y < 4; y++) Yg[y] = cscale(w, Po[prop_index(g, y, co, cop, V, site)]);
 #pragma unroll
             for (int gp = 0; gp < 4; gp++) {
               double2 e = acc[g][gp];
@@ -227,19 +222,9 @@ __global__ void __launch_bounds__(64) baryon_kernel(double2 *out, const double2 
       o[g * 4 + gp] = v;
     }
 }
-#undef PR
 
 // ================================ host: gamma algebra, term lists ================================
 using namespace gammah;   // M4, gammaU and the matrix helpers (gamma_host.h)
-
-static void toSPerm(const M4 &m, int col[4], double2 val[4]) {
-  for (int r = 0; r < 4; r++) {
-    int n = 0;
-    for (int c = 0; c < 4; c++)
-      if (std::abs(m.a[r][c]) > 1e-12) { col[r] = c; val[r] = make_double2(m.a[r][c].real(), m.a[r][c].imag()); n++; }
-    if (n != 1) errorQuda("twop: spin matrix is not a signed permutation");
-  }
-}
 
 // one Wick contraction: sink slot s goes to source slot pi[s]; flavours f[s]; A_{alpha beta}, B_{beta' alpha'}
 static Term termFor(double w, const int pi[3], const int f[3], const M4 &A, const M4 &B) {
@@ -382,34 +367,25 @@ void twopContract(TwopProps &props, const LatticeGeom &g, const int src[4], int 
   using namespace twop;
   uploadTables();
   const CommGrid &cg = commGrid();
-  const std::vector<int> moms = twopMomenta(Q_sq);
-  const int Nm = (int)moms.size() / 3;
-  const int Vs = g.X[0] * g.X[1] * g.X[2], Lt = g.X[3], T = Lt * cg.dims[3];
+  const int Vs = g.X[0] * g.X[1] * g.X[2], T = g.X[3] * cg.dims[3];
   const long V = props.V;
   hipStream_t st = computeStream();
   hipLaunchKernelGGL(rotate_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, props.P[0], V, +1.0);
   hipLaunchKernelGGL(rotate_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, props.P[1], V, -1.0);
   HIP_CHECK(hipGetLastError());
-  double2 *cs = nullptr, *acc = nullptr;
-  int *d_moms = nullptr;
-  const size_t per = (size_t)Nm * 16 * 2;   // doubles per (block, time slice)
-  HIP_CHECK(hipMalloc(&cs, (size_t)NBLK * Vs * 16 * sizeof(double2)));
-  HIP_CHECK(hipMalloc(&acc, (size_t)NBLK * Lt * per * sizeof(double)));
-  HIP_CHECK(hipMemsetAsync(acc, 0, (size_t)NBLK * Lt * per * sizeof(double), st));
-  HIP_CHECK(hipMalloc(&d_moms, moms.size() * sizeof(int)));
-  HIP_CHECK(hipMemcpyAsync(d_moms, moms.data(), moms.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  MomAccum A(NBLK, twopMomenta(Q_sq));
+  const int Nm = A.Nm;
+  const size_t per = A.per();
   // phases relative to the source: the origin of the local lattice minus the source position
-  int gx[3], L[3];
-  for (int d = 0; d < 3; d++) { gx[d] = cg.coords[d] * g.X[d] - src[d]; L[d] = g.X[d] * cg.dims[d]; }
-  for (int t = 0; t < Lt; t++) {
+  int gx[3];
+  for (int d = 0; d < 3; d++) gx[d] = cg.coords[d] * g.X[d] - src[d];
+  stageAndProject(A, gx, 1, [&](int t, int, double2 *cs) {   // the kernels take one time slice
     hipLaunchKernelGGL(meson_kernel, dim3((Vs + 127) / 128), dim3(128), 0, st, cs, props.P[0], props.P[1], V, Vs, t);
     hipLaunchKernelGGL(baryon_kernel, dim3((Vs + 63) / 64, NBAR, 2), dim3(64), 0, st, cs, props.P[0], props.P[1], V, Vs, t);
     HIP_CHECK(hipGetLastError());
-    momentumProject(acc, cs, NBLK, t, 1, Lt, d_moms, Nm, g.X, gx, L);
-  }
+  }, nullptr);
   std::vector<double> glob((size_t)NBLK * T * per);
-  gatherTimeBlocks(glob.data(), (const double *)acc, NBLK, Lt, per);   // synchronises
-  (void)hipFree(cs); (void)hipFree(acc); (void)hipFree(d_moms);
+  A.get(glob.data());
   for (int it = 0; it < T; it++) {
     const int ts = (it + src[3]) % T;
     const double sign = it + src[3] >= T ? -1.0 : 1.0;

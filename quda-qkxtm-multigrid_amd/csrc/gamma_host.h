@@ -4,6 +4,8 @@
 
 #include <complex>
 
+#include "qa_core.h"
+
 namespace quda {
 namespace gammah {
 
@@ -30,6 +32,16 @@ inline M4 gammaU(int mu) {
   if (mu == 5) return gammaU(1) * gammaU(2) * gammaU(3) * gammaU(4);
   for (int i = 0; i < 2; i++) for (int j = 0; j < 2; j++) { g.a[i][2 + j] = I * s[mu - 1][i][j]; g.a[2 + i][j] = -I * s[mu - 1][i][j]; }
   return g;
+}
+
+// m as a signed permutation: row r holds val[r] in column col[r]
+inline void toSPerm(const M4 &m, int col[4], double2 val[4]) {
+  for (int r = 0; r < 4; r++) {
+    int n = 0;
+    for (int c = 0; c < 4; c++)
+      if (std::abs(m.a[r][c]) > 1e-12) { col[r] = c; val[r] = make_double2(m.a[r][c].real(), m.a[r][c].imag()); n++; }
+    if (n != 1) errorQuda("spin matrix is not a signed permutation");
+  }
 }
 
 }  // namespace gammah

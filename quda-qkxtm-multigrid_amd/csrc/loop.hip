@@ -33,6 +33,7 @@
 #include "basis.h"
 #include "blas.h"
 #include "comm_quda.h"
+#include "contract_stencil.h"
 #include "device_io.h"
 #include "interface_internal.h"
 #include "p2p.h"
@@ -46,62 +47,34 @@ namespace loop {
 
 constexpr int NBLK = 18, NGM = 16;
 
-struct LoopArg {
-  const double *x[2], *phi[2];   // parity blocks of the two fields (12 double2 planes of stride sp_stride), device basis
-  int sp_stride;
-  const char *gauge[2];          // parityBase of the links
-  size_t link_bytes;
-  int g_stride;
-  int X0, Y, Z, T;               // local extents
-  int t0;                        // first time slice of the chunk
-  long S;                        // sites of the chunk
-  double tsign_fwd, tsign_bwd;   // boundary sign where the links do not carry it
-  const double *ghost[2][2][8];  // [field][parity of the reading site][dir]: ghost zone of a partitioned direction, else nullptr
-  int faceCB[4];
-  double2 *cs;                   // [18][S][16]
+struct LoopArg : StencilGeom {
+  const double *x[2], *phi[2];   // parity blocks of the two fields, device basis: fields 0 and 1 of the ghost zones
 };
 
 // o[4a + b] = w1 C[u1, v1] + w2 C[u2, v2], spinors in the UKQCD basis as 24 reals
 __device__ __forceinline__ void block2(double2 *o, const double *u1, const double *v1, double w1, const double *u2, const double *v2, double w2) {
 #pragma unroll
-  for (int a = 0; a < 4; a++) {
-    const double *p = u1 + 6 * ((a + 2) & 3), *q = u2 + 6 * ((a + 2) & 3);
+  for (int a = 0; a < 4; a++)
 #pragma unroll
     for (int b = 0; b < 4; b++) {
-      const double *r = v1 + 6 * b, *s = v2 + 6 * b;
       double re1 = 0, im1 = 0, re2 = 0, im2 = 0;
 #pragma unroll
-      for (int c = 0; c < 3; c++) {
-        re1 += p[2 * c] * r[2 * c] + p[2 * c + 1] * r[2 * c + 1];
-        im1 += p[2 * c] * r[2 * c + 1] - p[2 * c + 1] * r[2 * c];
-        re2 += q[2 * c] * s[2 * c] + q[2 * c + 1] * s[2 * c + 1];
-        im2 += q[2 * c] * s[2 * c + 1] - q[2 * c + 1] * s[2 * c];
+      for (int c = 0; c < 3; c++) {   // the two sums interleaved: the order the register allocation of the fused kernel was settled with
+        colour_mac(re1, im1, u1 + 6 * ((a + 2) & 3), v1 + 6 * b, c);
+        colour_mac(re2, im2, u2 + 6 * ((a + 2) & 3), v2 + 6 * b, c);
       }
       o[4 * a + b] = make_double2(w1 * re1 + w2 * re2, w1 * im1 + w2 * im2);
     }
-  }
 }
 __device__ __forceinline__ void block1(double2 *o, const double *u, const double *v, double w) {
 #pragma unroll
-  for (int a = 0; a < 4; a++) {
-    const double *p = u + 6 * ((a + 2) & 3);
+  for (int a = 0; a < 4; a++)
 #pragma unroll
     for (int b = 0; b < 4; b++) {
-      const double *r = v + 6 * b;
       double re = 0, im = 0;
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        re += p[2 * c] * r[2 * c] + p[2 * c + 1] * r[2 * c + 1];
-        im += p[2 * c] * r[2 * c + 1] - p[2 * c + 1] * r[2 * c];
-      }
+      spin_dot(re, im, u + 6 * ((a + 2) & 3), v + 6 * b);
       o[4 * a + b] = make_double2(w * re, w * im);
     }
-  }
-}
-
-__device__ __forceinline__ void load_site(double *psi, const double *blk, int stride, int idx, const double *ghost, int faceCB, int face, bool cross) {
-  if (ghost && cross) Planar<double, 24>::load(psi, ghost, faceCB, face, nullptr, face);
-  else Planar<double, 24>::load(psi, blk, stride, idx, nullptr, idx);
 }
 
 // ---- the fused stencil: 32 sites x 8 (mu, sign) tasks per work-group ----
@@ -120,43 +93,30 @@ template <int R> __global__ void __launch_bounds__(256) loop_fused_kernel(const 
   const int mu = j >> 1;
   const double sg = (j & 1) ? 1.0 : -1.0;   // D = F + sg B
 
-  int xf = xc, yf = y, zf = z, tf = t, xb = xc, yb = y, zb = z, tb = t, face;
-  bool crossF, crossB;
-  double signF = 1.0, signB = 1.0;
-  switch (mu) {
-    case 0: crossF = xc == X0 - 1; crossB = xc == 0; xf = crossF ? 0 : xc + 1; xb = crossB ? X0 - 1 : xc - 1; face = (y + Y * (z + Z * t)) >> 1; break;
-    case 1: crossF = y == Y - 1; crossB = y == 0; yf = crossF ? 0 : y + 1; yb = crossB ? Y - 1 : y - 1; face = (xc + X0 * (z + Z * t)) >> 1; break;
-    case 2: crossF = z == Z - 1; crossB = z == 0; zf = crossF ? 0 : z + 1; zb = crossB ? Z - 1 : z - 1; face = (xc + X0 * (y + Y * t)) >> 1; break;
-    default:
-      crossF = t == T - 1; crossB = t == 0; tf = crossF ? 0 : t + 1; tb = crossB ? T - 1 : t - 1; face = (xc + X0 * (y + Y * z)) >> 1;
-      if (crossF) signF = a.tsign_fwd;
-      if (crossB) signB = a.tsign_bwd;
-      break;
-  }
-  const int idxF = (((tf * Z + zf) * Y + yf) * X0 + xf) >> 1, idxB = (((tb * Z + zb) * Y + yb) * X0 + xb) >> 1;
+  const HopNeighbours h = hop_neighbours(mu, xc, y, z, t, X0, Y, Z, T, a.tsign_fwd, a.tsign_bwd);
   const int op = 1 - parity;
-  const double *gxF = a.ghost[0][parity][2 * mu], *gxB = a.ghost[0][parity][2 * mu + 1];
-  const double *gpF = a.ghost[1][parity][2 * mu], *gpB = a.ghost[1][parity][2 * mu + 1];
+  const double *gxF = ghost_zone(a, mu, 0, parity, 0), *gxB = ghost_zone(a, mu, 0, parity, 1);
+  const double *gpF = ghost_zone(a, mu, 1, parity, 0), *gpB = ghost_zone(a, mu, 1, parity, 1);
   const int fcb = a.faceCB[mu];
 
   double Dx[24], Dp[24];
   {
     double U[18], psi[24], v[24];
-    Link<double, R>::load(U, a.gauge[parity] + (size_t)(2 * mu) * a.link_bytes, a.g_stride, idx, signF);
-    load_site(psi, a.x[op], a.sp_stride, idxF, gxF, fcb, face, crossF);
+    Link<double, R>::load(U, a.gauge[parity] + (size_t)(2 * mu) * a.link_bytes, a.g_stride, idx, h.signF);
+    load_site(psi, a.x[op], a.sp_stride, h.idxF, gxF, fcb, h.face, h.crossF);
 #pragma unroll
     for (int sp = 0; sp < 4; sp++) su3_mv(Dx + 6 * sp, U, psi + 6 * sp);
-    load_site(psi, a.phi[op], a.sp_stride, idxF, gpF, fcb, face, crossF);
+    load_site(psi, a.phi[op], a.sp_stride, h.idxF, gpF, fcb, h.face, h.crossF);
 #pragma unroll
     for (int sp = 0; sp < 4; sp++) su3_mv(Dp + 6 * sp, U, psi + 6 * sp);
-    Link<double, R>::load(U, a.gauge[parity] + (size_t)(2 * mu + 1) * a.link_bytes, a.g_stride, idx, signB);
-    load_site(psi, a.x[op], a.sp_stride, idxB, gxB, fcb, face, crossB);
+    Link<double, R>::load(U, a.gauge[parity] + (size_t)(2 * mu + 1) * a.link_bytes, a.g_stride, idx, h.signB);
+    load_site(psi, a.x[op], a.sp_stride, h.idxB, gxB, fcb, h.face, h.crossB);
 #pragma unroll
     for (int sp = 0; sp < 4; sp++) su3_mv(v + 6 * sp, U, psi + 6 * sp);
 #pragma unroll
     for (int k = 0; k < 24; k++) psi[k] = Dx[k] + sg * v[k];
     rotate_basis(Dx, psi, BASIS_DR_TO_UKQCD);
-    load_site(psi, a.phi[op], a.sp_stride, idxB, gpB, fcb, face, crossB);
+    load_site(psi, a.phi[op], a.sp_stride, h.idxB, gpB, fcb, h.face, h.crossB);
 #pragma unroll
     for (int sp = 0; sp < 4; sp++) su3_mv(v + 6 * sp, U, psi + 6 * sp);
 #pragma unroll
@@ -237,36 +197,11 @@ static void globalL(int L[3]) {
 }
 
 // cumulative sums of the 18 blocks over the noise vectors, in momentum space, this rank's time slices
-struct LoopAccum {
-  double2 *d = nullptr;
-  int *d_moms = nullptr;
-  std::vector<int> moms;
-  int Nm = 0, Lt = 0, Q_sq = 0;
-  size_t n = 0;   // complex numbers
-};
-
 LoopAccum *loopAccumCreate(int Q_sq) {
   if (Q_sq < 0) errorQuda("loop contraction: Q_sq = %d", Q_sq);
-  LoopAccum *A = new LoopAccum;
   int L[3];
   globalL(L);
-  A->moms = loopMomenta(L, Q_sq);
-  A->Nm = (int)A->moms.size() / 3;
-  A->Lt = residentGeom().X[3];
-  A->Q_sq = Q_sq;
-  A->n = (size_t)loop::NBLK * A->Lt * A->Nm * loop::NGM;
-  HIP_CHECK(hipMalloc(&A->d, A->n * sizeof(double2)));
-  HIP_CHECK(hipMalloc(&A->d_moms, A->moms.size() * sizeof(int)));
-  HIP_CHECK(hipMemcpyAsync(A->d_moms, A->moms.data(), A->moms.size() * sizeof(int), hipMemcpyHostToDevice, computeStream()));
-  HIP_CHECK(hipMemsetAsync(A->d, 0, A->n * sizeof(double2), computeStream()));
-  HIP_CHECK(hipStreamSynchronize(computeStream()));
-  return A;
-}
-void loopAccumZero(LoopAccum &A) { HIP_CHECK(hipMemsetAsync(A.d, 0, A.n * sizeof(double2), computeStream())); }
-void loopAccumDestroy(LoopAccum *A) {
-  if (!A) return;
-  (void)hipFree(A->d); (void)hipFree(A->d_moms);
-  delete A;
+  return new MomAccum(loop::NBLK, loopMomenta(L, Q_sq));
 }
 
 // read at every contraction, so one process can time both paths (tools/loop_timing.py)
@@ -304,14 +239,6 @@ static void makePhi(ColorSpinorField &phi, const ColorSpinorField &x, QudaInvert
     ColorSpinorField &h = parity ? phi.Odd() : phi.Even();
     hipLaunchKernelGGL(loop::gamma5_kernel, dim3((Vh + 255) / 256), dim3(256), 0, computeStream(), (double *)h.V(), h.Stride(), Vh);
   }
-  HIP_CHECK(hipGetLastError());
-}
-
-static void launchFused(const loop::LoopArg &arg, int recon) {
-  const dim3 grid((unsigned)((arg.S + 31) / 32)), block(256);
-  if (recon == 12) hipLaunchKernelGGL((loop::loop_fused_kernel<12>), grid, block, 0, computeStream(), arg);
-  else if (recon == 8) hipLaunchKernelGGL((loop::loop_fused_kernel<8>), grid, block, 0, computeStream(), arg);
-  else hipLaunchKernelGGL((loop::loop_fused_kernel<18>), grid, block, 0, computeStream(), arg);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -370,12 +297,10 @@ void loopContractAdd(LoopAccum &A, ColorSpinorField &x, QudaInvertParam *param) 
   if (gaugePrecise->precision != QUDA_DOUBLE_PRECISION) errorQuda("loop contraction: the resident precise links must be fp64 (cuda_prec of the gauge field)");
   const LatticeGeom &g = residentGeom();
   const CommGrid &cg = commGrid();
-  if (A.Lt != g.X[3]) errorQuda("loop contraction: the accumulator belongs to another lattice");
+  const int Vs = g.X[0] * g.X[1] * g.X[2];
   hipStream_t st = computeStream();
-  hipEvent_t ev[2];
-  for (int i = 0; i < 2; i++) HIP_CHECK(hipEventCreate(&ev[i]));
-  std::vector<hipEvent_t> marks;   // per chunk: before the stencil, after it, after the projection
-  auto mark = [&]() { hipEvent_t e; HIP_CHECK(hipEventCreate(&e)); HIP_CHECK(hipEventRecord(e, st)); marks.push_back(e); };
+  hipEvent_t ev[3];   // start, phi made, ghost zones / shifted fields made
+  for (int i = 0; i < 3; i++) HIP_CHECK(hipEventCreate(&ev[i]));
   HIP_CHECK(hipEventRecord(ev[0], st));
 
   if (x.TwistFlavor() != QUDA_TWIST_PLUS && x.TwistFlavor() != QUDA_TWIST_MINUS) x.changeTwist(QUDA_TWIST_PLUS);   // mu = 0: the flavour does not enter
@@ -383,95 +308,43 @@ void loopContractAdd(LoopAccum &A, ColorSpinorField &x, QudaInvertParam *param) 
   makePhi(phi, x, param);
   HIP_CHECK(hipEventRecord(ev[1], st));
 
-  const int Vs = g.X[0] * g.X[1] * g.X[2], Lt = g.X[3];
-  // time slices per chunk: the staged blocks stay below 2 GiB
-  const size_t perSlice = (size_t)Vs * NBLK * NGM * sizeof(double2);
-  int tc = (int)std::max<size_t>(1, std::min<size_t>((size_t)Lt, ((size_t)2 << 30) / perSlice));
-  {
-    static int env = -1;   // measurement aid: time slices per chunk
-    if (env < 0) { const char *e = getenv("QUDA_AMD_LOOP_TCHUNK"); env = e ? atoi(e) : 0; }
-    if (env > 0) tc = std::min(env, Lt);
-  }
-  double2 *cs = nullptr;
-  HIP_CHECK(hipMalloc(&cs, perSlice * tc));
-
+  static const int tchunk = [] { const char *e = getenv("QUDA_AMD_LOOP_TCHUNK"); return e ? atoi(e) : 0; }();   // measurement aid: time slices per chunk
+  int gx[3];
+  for (int d = 0; d < 3; d++) gx[d] = cg.coords[d] * g.X[d];
+  double secs[2];
   const bool fused = fusedEnabled();
-  LoopArg arg;
-  memset(&arg, 0, sizeof(arg));
-  std::vector<void *> ghosts;
-  ChainFields F;
-  memset(&F, 0, sizeof(F));
   if (fused) {
+    LoopArg arg;
+    memset(&arg, 0, sizeof(arg));
     arg.x[0] = (const double *)x.Even().V(); arg.x[1] = (const double *)x.Odd().V();
     arg.phi[0] = (const double *)phi.Even().V(); arg.phi[1] = (const double *)phi.Odd().V();
     arg.sp_stride = x.Stride();
     if (phi.Stride() != x.Stride()) errorQuda("loop contraction: stride mismatch");
-    arg.gauge[0] = (const char *)gaugePrecise->parityBase(0); arg.gauge[1] = (const char *)gaugePrecise->parityBase(1);
-    arg.link_bytes = gaugePrecise->link_bytes; arg.g_stride = gaugePrecise->stride;
-    arg.X0 = g.X[0]; arg.Y = g.X[1]; arg.Z = g.X[2]; arg.T = g.X[3];
-    const bool anti = gaugePrecise->reconstruct != QUDA_RECONSTRUCT_NO && gaugePrecise->t_boundary == QUDA_ANTI_PERIODIC_T;
-    arg.tsign_fwd = (anti && cg.coords[3] == cg.dims[3] - 1) ? -1.0 : 1.0;
-    arg.tsign_bwd = (anti && cg.coords[3] == 0) ? -1.0 : 1.0;
-    for (int mu = 0; mu < 4; mu++) {
-      arg.faceCB[mu] = g.faceCB[mu];
-      if (!cg.partitioned(mu)) continue;
-      for (int f = 0; f < 2; f++)
-        for (int parity = 0; parity < 2; parity++)
-          for (int d = 0; d < 2; d++) {
-            void *gh = nullptr;
-            HIP_CHECK(hipMalloc(&gh, (size_t)g.faceCB[mu] * 24 * sizeof(double)));
-            ghosts.push_back(gh);
-            const ColorSpinorField &fld = f ? phi : x;
-            const ColorSpinorField &other = parity ? fld.Even() : fld.Odd();
-            exchangeFullFace(gh, (const double *)other.V(), g, other.Stride(), parity, 2 * mu + d);
-            arg.ghost[f][parity][2 * mu + d] = (const double *)gh;
-          }
-    }
-    arg.cs = cs;
+    fillStencilGeom(arg, *gaugePrecise, g, cg);
+    GhostZones ghosts(arg, {&x, &phi}, g, cg);
+    HIP_CHECK(hipEventRecord(ev[2], st));
+    stageAndProject(A, gx, tchunk, [&](int t0, int nt, double2 *cs) {
+      arg.t0 = t0; arg.S = (long)nt * Vs; arg.cs = cs;
+      launchByRecon((int)gaugePrecise->reconstruct, loop_fused_kernel<18>, loop_fused_kernel<12>, loop_fused_kernel<8>, dim3((unsigned)((arg.S + 31) / 32)), dim3(256), arg);
+    }, secs);
   } else {
+    ChainFields F;
     for (int mu = 0; mu < 4; mu++) {
       F.Fx[mu] = new ColorSpinorField(x); F.Bx[mu] = new ColorSpinorField(x); F.Fp[mu] = new ColorSpinorField(x); F.Bp[mu] = new ColorSpinorField(x);
       shiftFull(*F.Fx[mu], x, 2 * mu); shiftFull(*F.Bx[mu], x, 2 * mu + 1);
       shiftFull(*F.Fp[mu], phi, 2 * mu); shiftFull(*F.Bp[mu], phi, 2 * mu + 1);
     }
+    HIP_CHECK(hipEventRecord(ev[2], st));
+    stageAndProject(A, gx, tchunk, [&](int t0, int nt, double2 *cs) { chainChunk(cs, (long)nt * Vs, t0, x, phi, F, g); }, secs);
+    for (int mu = 0; mu < 4; mu++) { delete F.Fx[mu]; delete F.Bx[mu]; delete F.Fp[mu]; delete F.Bp[mu]; }
   }
-  int gx[3], L[3];
-  for (int d = 0; d < 3; d++) { gx[d] = cg.coords[d] * g.X[d]; L[d] = g.X[d] * cg.dims[d]; }
-  for (int t0 = 0; t0 < Lt; t0 += tc) {
-    const int nt = std::min(tc, Lt - t0);
-    const long S = (long)nt * Vs;
-    mark();
-    if (fused) {
-      arg.t0 = t0; arg.S = S;
-      launchFused(arg, (int)gaugePrecise->reconstruct);
-    } else {
-      chainChunk(cs, S, t0, x, phi, F, g);
-    }
-    mark();
-    momentumProject(A.d, cs, NBLK, t0, nt, Lt, A.d_moms, A.Nm, g.X, gx, L);
-    mark();
-  }
-  HIP_CHECK(hipStreamSynchronize(st));
   p2pCheck("loopContractAdd");
-  float ms = 0;
-  HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-  g_loopSecs[0] = ms * 1e-3; g_loopSecs[1] = 0; g_loopSecs[2] = 0;
-  for (size_t i = 0; i + 2 < marks.size(); i += 3) {
-    HIP_CHECK(hipEventElapsedTime(&ms, marks[i], marks[i + 1])); g_loopSecs[1] += ms * 1e-3;
-    HIP_CHECK(hipEventElapsedTime(&ms, marks[i + 1], marks[i + 2])); g_loopSecs[2] += ms * 1e-3;
-  }
-  HIP_CHECK(hipEventElapsedTime(&ms, ev[0], marks.back()));
-  g_loopSecs[3] = ms * 1e-3;
-  if (!fused) g_loopSecs[1] = g_loopSecs[3] - g_loopSecs[0] - g_loopSecs[2];   // the covariant shifts of the chain run before the first chunk
-  for (hipEvent_t e : marks) (void)hipEventDestroy(e);
-  for (int i = 0; i < 2; i++) (void)hipEventDestroy(ev[i]);
-  for (void *gh : ghosts) (void)hipFree(gh);
-  for (int mu = 0; mu < 4; mu++) { delete F.Fx[mu]; delete F.Bx[mu]; delete F.Fp[mu]; delete F.Bp[mu]; }
-  (void)hipFree(cs);
+  // total: up to the first chunk, then the chunks; the covariant shifts of the chain run before the first chunk and count as its stencil
+  g_loopSecs[0] = elapsedSecs(ev[0], ev[1]); g_loopSecs[2] = secs[1];
+  g_loopSecs[3] = elapsedSecs(ev[0], ev[2]) + secs[0] + secs[1];
+  g_loopSecs[1] = fused ? secs[0] : g_loopSecs[3] - g_loopSecs[0] - g_loopSecs[2];
+  for (int i = 0; i < 3; i++) (void)hipEventDestroy(ev[i]);
 }
-
-// out[18][T global][Nmoms][16][re, im], the same numbers on every rank
-void loopAccumGet(const LoopAccum &A, double *out) { gatherTimeBlocks(out, (const double *)A.d, loop::NBLK, A.Lt, (size_t)A.Nm * loop::NGM * 2); }
 
 static const char *const loopTypeName[6] = {"Scalar", "dOp", "Loops", "LoopsCv", "LpsDw", "LpsDwCv"};
 static const bool loopTypeOneD[6] = {false, false, true, true, true, true};
@@ -483,7 +356,7 @@ void loopWriteAscii(const LoopAccum &A, const char *pref, const char *tsmTag, in
   const CommGrid &cg = commGrid();
   const int Lt = A.Lt, nT = cg.dims[3], T = Lt * nT, Nm = A.Nm;
   std::vector<double> glob((size_t)loop::NBLK * T * Nm * loop::NGM * 2);
-  loopAccumGet(A, glob.data());   // collective
+  A.get(glob.data());   // collective: [18][T global][Nmoms][16][re, im], the same numbers on every rank
   if (cg.rank != 0) return;
   for (int type = 0; type < 6; type++)
     for (int r = 0; r < nT; r++) {
@@ -537,8 +410,8 @@ void qudaAmdContractLoop(double *out, const void *h_solution, QudaInvertParam *p
   lexToDevice(v, (const double *)h_solution, g, true);
   LoopAccum *A = loopAccumCreate(Q_sq);
   loopContractAdd(*A, v, param);
-  loopAccumGet(*A, out);
-  loopAccumDestroy(A);
+  A->get(out);
+  delete A;
 }
 
 void qudaAmdLoopLastTimings(double secs[4]) {

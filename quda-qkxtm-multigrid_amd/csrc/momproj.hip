@@ -1,9 +1,10 @@
-// momproj.hip — the tail that the two-point (contract.hip) and the loop (loop.hip) contractions share: momentum projection of
-// staged per-site blocks of 16 complex numbers with a fixed summation order, and the sum over ranks.  The contract is stated at
-// the declarations in qkxtm_internal.h.
+// momproj.hip — the tail that the two-point (contract.hip), loop (loop.hip) and three-point (threep.hip) contractions share: the
+// momentum-space accumulator, the chunked stage-and-project driver, momentum projection of staged per-site blocks of 16 complex
+// numbers with a fixed summation order, and the sum over ranks.  The contract is stated at the declarations in qkxtm_internal.h.
 //
 // Reference: performFFT (lib/qudaQKXTM_Kepler_utils.cpp:300-357), the Fourier transform of the two-point functions
 // (lib/qudaQKXTM_Contraction_Kepler.cpp), both followed by an MPI reduction over the spatial ranks.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -129,6 +130,55 @@ void gatherTimeBlocks(double *out, const double *d_loc, int nblk, int Lt, size_t
     for (int r = 0; r < cg.size; r++) v += all[(size_t)r * total + i];
     out[i] = v;
   }
+}
+
+MomAccum::MomAccum(int nblk_, std::vector<int> moms_) : nblk(nblk_), Lt(residentGeom().X[3]), Nm((int)moms_.size() / 3), moms(std::move(moms_)) {
+  HIP_CHECK(hipMalloc(&d, (size_t)nblk * Lt * per() * sizeof(double)));
+  HIP_CHECK(hipMalloc(&d_moms, moms.size() * sizeof(int)));
+  HIP_CHECK(hipMemcpyAsync(d_moms, moms.data(), moms.size() * sizeof(int), hipMemcpyHostToDevice, computeStream()));
+  zero();
+}
+MomAccum::~MomAccum() { (void)hipFree(d); (void)hipFree(d_moms); }
+void MomAccum::zero() { HIP_CHECK(hipMemsetAsync(d, 0, (size_t)nblk * Lt * per() * sizeof(double), computeStream())); }
+void MomAccum::get(double *out) const { gatherTimeBlocks(out, (const double *)d, nblk, Lt, per()); }
+
+double elapsedSecs(hipEvent_t a, hipEvent_t b) {
+  float ms = 0;
+  HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+  return ms * 1e-3;
+}
+
+void stageAndProject(MomAccum &A, const int gx[3], int maxSlicesPerChunk, const std::function<void(int t0, int nt, double2 *cs)> &stage, double secs[2]) {
+  const LatticeGeom &g = residentGeom();
+  const CommGrid &cg = commGrid();
+  if (A.Lt != g.X[3]) errorQuda("contraction: the accumulator belongs to another lattice");
+  hipStream_t st = computeStream();
+  const int Vs = g.X[0] * g.X[1] * g.X[2], Lt = A.Lt;
+  const int L[3] = {g.X[0] * cg.dims[0], g.X[1] * cg.dims[1], g.X[2] * cg.dims[2]};
+  // time slices per chunk: the staged blocks stay below 2 GiB
+  const size_t perSlice = (size_t)Vs * A.nblk * momproj::NGM * sizeof(double2);
+  int tc = (int)std::max<size_t>(1, std::min<size_t>((size_t)Lt, ((size_t)2 << 30) / perSlice));
+  if (maxSlicesPerChunk > 0) tc = std::min(tc, maxSlicesPerChunk);
+  double2 *cs = nullptr;
+  HIP_CHECK(hipMalloc(&cs, perSlice * tc));
+  std::vector<hipEvent_t> marks;   // per chunk: before the staging kernels, after them, after the projection
+  auto mark = [&]() { if (!secs) return; hipEvent_t e; HIP_CHECK(hipEventCreate(&e)); HIP_CHECK(hipEventRecord(e, st)); marks.push_back(e); };
+  for (int t0 = 0; t0 < Lt; t0 += tc) {
+    const int nt = std::min(tc, Lt - t0);
+    mark();
+    stage(t0, nt, cs);
+    mark();
+    momentumProject(A.d, cs, A.nblk, t0, nt, Lt, A.d_moms, A.Nm, g.X, gx, L);
+    mark();
+  }
+  HIP_CHECK(hipStreamSynchronize(st));
+  if (secs) secs[0] = secs[1] = 0;
+  for (size_t i = 0; i < marks.size(); i += 3) {
+    secs[0] += elapsedSecs(marks[i], marks[i + 1]);
+    secs[1] += elapsedSecs(marks[i + 1], marks[i + 2]);
+  }
+  for (hipEvent_t e : marks) (void)hipEventDestroy(e);
+  (void)hipFree(cs);
 }
 
 int copyMomenta(const std::vector<int> &m, int *moms, int max_moms, const char *fname) {

@@ -612,7 +612,7 @@ static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInf
   // bias correction of the truncated solver method: TSM_NHP fresh sources solved to both precisions (:9170-9230)
   if (useTSM) {
     if (writeLoops) {   // :9164-9410: fresh accumulators, the high- and the low-precision sums side by side, both dumped every TSM_NdumpHP
-      loopAccumZero(*acc[0]);
+      acc[0]->zero();
       pref[0] = std::string(loopInfo.loop_fname) + "_stoch_TSM_MG_HighPrec";
       pref[1] = std::string(loopInfo.loop_fname) + "_stoch_TSM_MG_LowPrec";
       tsmTag = "NHP";
@@ -624,7 +624,7 @@ static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInf
       solve(true, "loop_HP_LP", is, 1);
     }
   }
-  loopAccumDestroy(acc[0]); loopAccumDestroy(acc[1]);
+  delete acc[0]; delete acc[1];
   param->secs = secs; param->gflops = gflops; param->iter = iters;
   delete d; delete dSloppy; delete dPre;
 }

@@ -1,7 +1,9 @@
 // qkxtm_internal.h — what the translation units of the QKXTM drivers (qkxtm.hip, contract.hip, loop.hip, threep.hip, momproj.hip) call across
-// each other.  No .hip file declares another file's function itself.
+// each other.  No .hip file declares another file's function itself.  The device code and the stencil argument that the contractions
+// share are contract_stencil.h.
 #pragma once
 
+#include <functional>
 #include <vector>
 
 #include "interface_internal.h"
@@ -37,14 +39,12 @@ void twopContract(TwopProps &props, const LatticeGeom &g, const int src[4], int 
 void twopWriteAscii(const char *fname_twop, const int src[4], int Q_sq, int T, const double *h_mes, const double *h_bar);
 
 // ---- loop.hip: one-end-trick loops ----
-struct LoopAccum;
+struct MomAccum;
+typedef MomAccum LoopAccum;   // [18][T_local][Nmoms][16], summed over the noise vectors
 bool loopOutputEnabled();
 std::vector<int> loopMomenta(const int L[3], int Q_sq);
 LoopAccum *loopAccumCreate(int Q_sq);
-void loopAccumZero(LoopAccum &A);
-void loopAccumDestroy(LoopAccum *A);
 void loopContractAdd(LoopAccum &A, ColorSpinorField &x, QudaInvertParam *param);
-void loopAccumGet(const LoopAccum &A, double *out);
 void loopWriteAscii(const LoopAccum &A, const char *pref, const char *tsmTag, int nnnn);
 
 // ---- threep.hip: three-point functions by the fixed-sink method ----
@@ -57,7 +57,28 @@ void threepSeqSource(double *h_out, const double *h_up, const double *h_dn, cons
 void threepContract(double *h_local, double *h_noether, double *h_oneD, ColorSpinorField *const y[12], ColorSpinorField *const F[12], const GaugeField &U,
                     const QudaAmdThreepParam *p);
 
-// ---- momproj.hip: the tail both contractions share ----
+// ---- momproj.hip: the tail that the two-point, loop and three-point contractions share ----
+// The momentum-space accumulator d[nblk][Lt][Nm][16] (complex, device, zero at first) of this rank's Lt time slices with its momentum
+// list on the host and the device.
+struct MomAccum {
+  const int nblk, Lt, Nm;
+  const std::vector<int> moms;   // [Nm][3]
+  int *d_moms = nullptr;
+  double2 *d = nullptr;
+  MomAccum(int nblk, std::vector<int> moms);
+  ~MomAccum();
+  MomAccum(const MomAccum &) = delete;
+  MomAccum &operator=(const MomAccum &) = delete;
+  size_t per() const { return (size_t)Nm * 32; }   // doubles per (block, time slice)
+  void zero();
+  void get(double *out) const;   // gatherTimeBlocks: out[nblk][T global][Nm][16][re, im]
+};
+// A.d += the projection of the caller's blocks, staged chunk by chunk: stage(t0, nt, cs) launches the kernels that write
+// cs[nblk][nt * Vs][16] for the local time slices [t0, t0 + nt).  A chunk holds as many slices as keep cs below 2 GiB, and at most
+// maxSlicesPerChunk if that is positive.  gx as for momentumProject.  secs (may be NULL): the device-event seconds of the staging
+// kernels and of the projections, summed over the chunks.  Synchronises the stream.
+void stageAndProject(MomAccum &A, const int gx[3], int maxSlicesPerChunk, const std::function<void(int t0, int nt, double2 *cs)> &stage, double secs[2]);
+double elapsedSecs(hipEvent_t a, hipEvent_t b);   // between two completed events
 // Project the staged blocks cs[nblk][nt * Vs][16] (complex; Vs = X[0] X[1] X[2] sites per slice, x fastest) of the local time slices
 // [t0, t0 + nt) onto the momenta d_moms[Nm][3] (device) and ADD the result into acc[nblk][Lt][Nm][16] (device):
 //      acc[k][t0 + tl][m][e] += sum_s exp(-2 pi i sum_d n_d (x_d(s) + gx[d]) / L[d]) cs[k][tl * Vs + s][e],

@@ -34,6 +34,7 @@
 #include "basis.h"
 #include "blas.h"
 #include "comm_quda.h"
+#include "contract_stencil.h"
 #include "device_io.h"
 #include "gamma_host.h"
 #include "interface_internal.h"
@@ -58,13 +59,6 @@ struct SeqArg {
   double2 G[4][4];    // G_tm[n][k]
   int part;           // 1: both slots of the doubly present flavour open, 2: the slot of the other flavour
 };
-
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-
-__constant__ int c_perm[6][3] = {{0, 1, 2}, {1, 2, 0}, {2, 0, 1}, {0, 2, 1}, {2, 1, 0}, {1, 0, 2}};
-__constant__ double c_perm_sign[6] = {1, 1, 1, -1, -1, -1};
-
-#define PR(p, s, t, c, d) (p)[(((s) * 4 + (t)) * 9 + (c) * 3 + (d)) * V + site]
 
 // out[column nu' c'][site][nu, c] = (g5 conj(sigma))[nu, c] on the sites of the local time slice tl; P2 the flavour that occurs twice
 // (slots 0 and 2), P1 the other (slot 1).  One thread per (site of the slice, column).
@@ -92,10 +86,10 @@ __global__ void __launch_bounds__(64) seq_source_kernel(double *out, const doubl
           const int llo = q == 0 ? nup : (q == 1 ? ainv[nup] : 0), lhi = q == 2 ? 3 : llo;
           const int nlo = q == 2 ? nup : 0, nhi = q == 2 ? nup : 3;
           for (int e1 = 0; e1 < 6; e1++) {
-            if (c_perm[e1][r] != c) continue;
+            if (c_eps[e1][r] != c) continue;
             for (int e2 = 0; e2 < 6; e2++) {
-              if (c_perm[e2][q] != cp) continue;
-              const double w = (term ? -1.0 : 1.0) * c_perm_sign[e1] * c_perm_sign[e2];
+              if (c_eps[e2][q] != cp) continue;
+              const double w = (term ? -1.0 : 1.0) * c_eps_sign[e1] * c_eps_sign[e2];
               for (int i = ilo; i <= ihi; i++)
                 for (int k = klo; k <= khi; k++)
                   for (int l = llo; l <= lhi; l++)
@@ -107,7 +101,7 @@ __global__ void __launch_bounds__(64) seq_source_kernel(double *out, const doubl
                       for (int sl = 0; sl < 3; sl++) {
                         if (sl == r) continue;
                         const double2 *P = sl == 1 ? P1 : P2;
-                        v = cmul(v, PR(P, ss[sl], ts[pi[sl]], c_perm[e1][sl], c_perm[e2][pi[sl]]));
+                        v = cmul(v, P[prop_index(ss[sl], ts[pi[sl]], c_eps[e1][sl], c_eps[e2][pi[sl]], V, site)]);
                       }
                       res.x += w * v.x; res.y += w * v.y;
                     }
@@ -118,48 +112,18 @@ __global__ void __launch_bounds__(64) seq_source_kernel(double *out, const doubl
       o[(nu ^ 2) * 3 + c] = make_double2(res.x, -res.y);   // g5 conj: spin nu of sigma goes to spin nu ^ 2
     }
 }
-#undef PR
 
 // ================================ the contraction stencil ================================
-struct ThreepArg {
-  const double *y[NCOL][2], *F[NCOL][2];   // parity blocks of the twelve columns (12 double2 planes of stride sp_stride), UKQCD basis
-  int sp_stride;
-  const char *gauge[2];                    // parityBase of the links
-  size_t link_bytes;
-  int g_stride;
-  int X0, Y, Z, T;                         // local extents
-  int t0;                                  // first time slice of the chunk
-  long S;                                  // sites of the chunk
-  double tsign_fwd, tsign_bwd;             // boundary sign where the links do not carry it
-  // ghost zones of a partitioned direction mu: ghost + ghostOff[mu] + ((((field * 12 + column) * 2 + parity of the reading site) * 2 + fwd / bwd) * faceCB[mu] * 24
-  const double *ghost;
-  long ghostOff[4];                        // -1: not partitioned
-  int faceCB[4];
-  double2 *cs;                             // [9][S][16]
+struct ThreepArg : StencilGeom {
+  const double *y[NCOL][2], *F[NCOL][2];   // parity blocks of the twelve columns, UKQCD basis: fields col and 12 + col of the ghost zones
 };
 
 // acc[4 kappa + lambda] += sum_c conj(u[(kappa + 2) mod 4, c]) v[lambda, c]
 __device__ __forceinline__ void accumulate(double *acc, const double *u, const double *v) {
 #pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const double *p = u + 6 * ((k + 2) & 3);
+  for (int k = 0; k < 4; k++)
 #pragma unroll
-    for (int l = 0; l < 4; l++) {
-      const double *r = v + 6 * l;
-      double re = acc[2 * (4 * k + l)], im = acc[2 * (4 * k + l) + 1];
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        re += p[2 * c] * r[2 * c] + p[2 * c + 1] * r[2 * c + 1];
-        im += p[2 * c] * r[2 * c + 1] - p[2 * c + 1] * r[2 * c];
-      }
-      acc[2 * (4 * k + l)] = re; acc[2 * (4 * k + l) + 1] = im;
-    }
-  }
-}
-
-__device__ __forceinline__ void load_site(double *psi, const double *blk, int stride, int idx, const double *ghost, int faceCB, int face, bool cross) {
-  if (ghost && cross) Planar<double, 24>::load(psi, ghost, faceCB, face, nullptr, face);
-  else Planar<double, 24>::load(psi, blk, stride, idx, nullptr, idx);
+    for (int l = 0; l < 4; l++) spin_dot(acc[2 * (4 * k + l)], acc[2 * (4 * k + l) + 1], u + 6 * ((k + 2) & 3), v + 6 * l);
 }
 
 // A work-group holds 128 sites of one parity and ONE task, so the field pointers, the links' block and the direction are uniform: task 8
@@ -190,33 +154,18 @@ template <int R> __global__ void __launch_bounds__(128) threep_stencil_kernel(co
     }
   } else {
     const int mu = j >> 1, bc = j & 1;
-    int xf = xc, yf = y, zf = z, tf = t, xb = xc, yb = y, zb = z, tb = t, face;
-    bool crossF, crossB;
-    double signF = 1.0, signB = 1.0;
-    switch (mu) {
-      case 0: crossF = xc == X0 - 1; crossB = xc == 0; xf = crossF ? 0 : xc + 1; xb = crossB ? X0 - 1 : xc - 1; face = (y + Y * (z + Z * t)) >> 1; break;
-      case 1: crossF = y == Y - 1; crossB = y == 0; yf = crossF ? 0 : y + 1; yb = crossB ? Y - 1 : y - 1; face = (xc + X0 * (z + Z * t)) >> 1; break;
-      case 2: crossF = z == Z - 1; crossB = z == 0; zf = crossF ? 0 : z + 1; zb = crossB ? Z - 1 : z - 1; face = (xc + X0 * (y + Y * t)) >> 1; break;
-      default:
-        crossF = t == T - 1; crossB = t == 0; tf = crossF ? 0 : t + 1; tb = crossB ? T - 1 : t - 1; face = (xc + X0 * (y + Y * z)) >> 1;
-        if (crossF) signF = a.tsign_fwd;
-        if (crossB) signB = a.tsign_bwd;
-        break;
-    }
-    const int idxF = (((tf * Z + zf) * Y + yf) * X0 + xf) >> 1, idxB = (((tb * Z + zb) * Y + yb) * X0 + xb) >> 1;
+    const HopNeighbours h = hop_neighbours(mu, xc, y, z, t, X0, Y, Z, T, a.tsign_fwd, a.tsign_bwd);
     // the neighbour that F comes from (forward for A, backward for B) and the one that y comes from (the opposite)
     const int dF = bc, dQ = 1 - bc;
-    const int idxFn = bc ? idxB : idxF, idxQn = bc ? idxF : idxB;
-    const bool crossFn = bc ? crossB : crossF, crossQn = bc ? crossF : crossB;
+    const int idxFn = bc ? h.idxB : h.idxF, idxQn = bc ? h.idxF : h.idxB, face = h.face;
+    const bool crossFn = bc ? h.crossB : h.crossF, crossQn = bc ? h.crossF : h.crossB;
     const int fcb = a.faceCB[mu];
-    const long goff = a.ghostOff[mu];
-    const size_t gzone = (size_t)fcb * 24;
     double U[18];
     // first pass over the columns: C[y, U F(x +- mu)]
-    Link<double, R>::load(U, a.gauge[parity] + (size_t)(2 * mu + dF) * a.link_bytes, a.g_stride, idx, bc ? signB : signF);
+    Link<double, R>::load(U, a.gauge[parity] + (size_t)(2 * mu + dF) * a.link_bytes, a.g_stride, idx, bc ? h.signB : h.signF);
 #pragma unroll 1
     for (int col = 0; col < NCOL; col++) {
-      const double *gF = goff >= 0 ? a.ghost + goff + (size_t)((((NCOL + col) * 2 + parity) * 2) + dF) * gzone : nullptr;
+      const double *gF = ghost_zone(a, mu, NCOL + col, parity, dF);
       load_site(psi, a.F[col][op], a.sp_stride, idxFn, gF, fcb, face, crossFn);
 #pragma unroll
       for (int sp = 0; sp < 4; sp++) su3_mv(v + 6 * sp, U, psi + 6 * sp);
@@ -224,10 +173,10 @@ template <int R> __global__ void __launch_bounds__(128) threep_stencil_kernel(co
       accumulate(acc, psi, v);
     }
     // second pass: C[U y(x -+ mu), F]
-    Link<double, R>::load(U, a.gauge[parity] + (size_t)(2 * mu + dQ) * a.link_bytes, a.g_stride, idx, bc ? signF : signB);
+    Link<double, R>::load(U, a.gauge[parity] + (size_t)(2 * mu + dQ) * a.link_bytes, a.g_stride, idx, bc ? h.signF : h.signB);
 #pragma unroll 1
     for (int col = 0; col < NCOL; col++) {
-      const double *gQ = goff >= 0 ? a.ghost + goff + (size_t)(((col * 2 + parity) * 2) + dQ) * gzone : nullptr;
+      const double *gQ = ghost_zone(a, mu, col, parity, dQ);
       load_site(psi, a.y[col][op], a.sp_stride, idxQn, gQ, fcb, face, crossQn);
 #pragma unroll
       for (int sp = 0; sp < 4; sp++) su3_mv(v + 6 * sp, U, psi + 6 * sp);
@@ -281,12 +230,6 @@ static void checkParam(const QudaAmdThreepParam *p, const char *fname) {
 
 static double g_threepSecs[4] = {0, 0, 0, 0};   // source construction, ghost exchange, stencil, projection
 
-static float elapsedMs(hipEvent_t a, hipEvent_t b) {
-  float ms = 0;
-  HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-  return ms;
-}
-
 }  // namespace threep
 
 // +1 where the operator is inserted on the up quark, -1 on the down quark
@@ -330,13 +273,9 @@ void threepSeqSourceDevice(ColorSpinorField *const src[12], TwopProps &props, co
     HIP_CHECK(hipMemsetAsync(d_seq, 0, NCOL * vec * sizeof(double), st));
     SeqArg a;
     const M4 Cg5 = gammaU(4) * gammaU(2) * gammaU(5), G = projectorMatrix(p->projector, p->particle);
-    for (int i = 0; i < 4; i++) {
-      int n = 0;
-      for (int c = 0; c < 4; c++)
-        if (std::abs(Cg5.a[i][c]) > 1e-12) { a.acol[i] = c; a.aval[i] = make_double2(Cg5.a[i][c].real(), Cg5.a[i][c].imag()); n++; }
-      if (n != 1) errorQuda("threep: C g5 is not a signed permutation");
+    toSPerm(Cg5, a.acol, a.aval);
+    for (int i = 0; i < 4; i++)
       for (int c = 0; c < 4; c++) a.G[i][c] = make_double2(G.a[i][c].real(), G.a[i][c].imag());
-    }
     a.part = p->part;
     const int twice = p->particle == PROTON ? 0 : 1;   // the flavour in slots 0 and 2
     hipLaunchKernelGGL(seq_source_kernel, dim3((Vs + 63) / 64, NCOL), dim3(64), 0, st, d_seq, twopPropsData(props, twice), twopPropsData(props, 1 - twice), (long)g.V, Vs, tg % Lt, a);
@@ -375,16 +314,8 @@ void threepSeqSource(double *h_out, const double *h_up, const double *h_dn, cons
   for (int c = 0; c < NCOL; c++) { deviceToLex(h_out + c * vec, *src[c], g, true, 1.0); delete src[c]; }
   HIP_CHECK(hipEventRecord(ev[1], st));
   HIP_CHECK(hipStreamSynchronize(st));
-  g_threepSecs[0] = elapsedMs(ev[0], ev[1]) * 1e-3;
+  g_threepSecs[0] = elapsedSecs(ev[0], ev[1]);
   for (int i = 0; i < 2; i++) (void)hipEventDestroy(ev[i]);
-}
-
-static void launchStencil(const threep::ThreepArg &arg, int recon) {
-  const dim3 grid((unsigned)((arg.S / 2 + 127) / 128) * 9, 2), block(128);
-  if (recon == 12) hipLaunchKernelGGL((threep::threep_stencil_kernel<12>), grid, block, 0, computeStream(), arg);
-  else if (recon == 8) hipLaunchKernelGGL((threep::threep_stencil_kernel<8>), grid, block, 0, computeStream(), arg);
-  else hipLaunchKernelGGL((threep::threep_stencil_kernel<18>), grid, block, 0, computeStream(), arg);
-  HIP_CHECK(hipGetLastError());
 }
 
 // y[12], F[12]: full fp64 device fields holding the columns in the UKQCD basis.  Outputs (host, any may be NULL): local [T][Nm][16],
@@ -396,93 +327,41 @@ void threepContract(double *h_local, double *h_noether, double *h_oneD, ColorSpi
   const LatticeGeom &g = residentGeom();
   const CommGrid &cg = commGrid();
   hipStream_t st = computeStream();
-  std::vector<hipEvent_t> marks;
-  auto mark = [&]() { hipEvent_t e; HIP_CHECK(hipEventCreate(&e)); HIP_CHECK(hipEventRecord(e, st)); marks.push_back(e); };
+  hipEvent_t ev[2];
+  for (int i = 0; i < 2; i++) HIP_CHECK(hipEventCreate(&ev[i]));
 
   ThreepArg arg;
   memset(&arg, 0, sizeof(arg));
   arg.sp_stride = y[0]->Stride();
+  std::vector<const ColorSpinorField *> fields(2 * NCOL);
   for (int c = 0; c < NCOL; c++) {
     if (y[c]->Stride() != arg.sp_stride || F[c]->Stride() != arg.sp_stride) errorQuda("threep contraction: stride mismatch");
     arg.y[c][0] = (const double *)y[c]->Even().V(); arg.y[c][1] = (const double *)y[c]->Odd().V();
     arg.F[c][0] = (const double *)F[c]->Even().V(); arg.F[c][1] = (const double *)F[c]->Odd().V();
+    fields[c] = y[c]; fields[NCOL + c] = F[c];
   }
-  arg.gauge[0] = (const char *)U.parityBase(0); arg.gauge[1] = (const char *)U.parityBase(1);
-  arg.link_bytes = U.link_bytes; arg.g_stride = U.stride;
-  arg.X0 = g.X[0]; arg.Y = g.X[1]; arg.Z = g.X[2]; arg.T = g.X[3];
-  const bool anti = U.reconstruct != QUDA_RECONSTRUCT_NO && U.t_boundary == QUDA_ANTI_PERIODIC_T;
-  arg.tsign_fwd = (anti && cg.coords[3] == cg.dims[3] - 1) ? -1.0 : 1.0;
-  arg.tsign_bwd = (anti && cg.coords[3] == 0) ? -1.0 : 1.0;
-
-  // ghost zones of the partitioned directions, column by column
-  mark();
-  size_t ghostDoubles = 0;
-  for (int mu = 0; mu < 4; mu++) {
-    arg.faceCB[mu] = g.faceCB[mu];
-    arg.ghostOff[mu] = -1;
-    if (!cg.partitioned(mu)) continue;
-    arg.ghostOff[mu] = (long)ghostDoubles;
-    ghostDoubles += (size_t)2 * NCOL * 2 * 2 * g.faceCB[mu] * 24;
-  }
-  double *ghost = nullptr;
-  if (ghostDoubles) {
-    HIP_CHECK(hipMalloc(&ghost, ghostDoubles * sizeof(double)));
-    for (int mu = 0; mu < 4; mu++) {
-      if (arg.ghostOff[mu] < 0) continue;
-      const size_t zone = (size_t)g.faceCB[mu] * 24;
-      for (int f = 0; f < 2; f++)
-        for (int c = 0; c < NCOL; c++)
-          for (int parity = 0; parity < 2; parity++)
-            for (int d = 0; d < 2; d++) {
-              const ColorSpinorField &fld = f ? *F[c] : *y[c];
-              const ColorSpinorField &other = parity ? fld.Even() : fld.Odd();
-              exchangeFullFace(ghost + arg.ghostOff[mu] + (size_t)((((f * NCOL + c) * 2 + parity) * 2) + d) * zone, (const double *)other.V(), g, other.Stride(), parity, 2 * mu + d);
-            }
-    }
-  }
-  arg.ghost = ghost;
-  mark();
+  fillStencilGeom(arg, U, g, cg);
+  HIP_CHECK(hipEventRecord(ev[0], st));
+  GhostZones ghosts(arg, fields, g, cg);   // column by column
+  HIP_CHECK(hipEventRecord(ev[1], st));
 
   // the '+' phase of the three-point functions: the shared projection with the negated momenta
   std::vector<int> moms = twopMomenta(p->Q_sq);
-  const int Nm = (int)moms.size() / 3;
   for (int &n : moms) n = -n;
-  const int Vs = g.X[0] * g.X[1] * g.X[2], Lt = g.X[3], T = Lt * cg.dims[3];
-  const size_t per = (size_t)Nm * NGM * 2;   // doubles per (block, time slice)
-  // time slices per chunk: the staged blocks stay below 2 GiB
-  const size_t perSlice = (size_t)Vs * NBLK * NGM * sizeof(double2);
-  const int tc = (int)std::max<size_t>(1, std::min<size_t>((size_t)Lt, ((size_t)2 << 30) / perSlice));
-  double2 *cs = nullptr, *acc = nullptr;
-  int *d_moms = nullptr;
-  HIP_CHECK(hipMalloc(&cs, perSlice * tc));
-  HIP_CHECK(hipMalloc(&acc, (size_t)NBLK * Lt * per * sizeof(double)));
-  HIP_CHECK(hipMemsetAsync(acc, 0, (size_t)NBLK * Lt * per * sizeof(double), st));
-  HIP_CHECK(hipMalloc(&d_moms, moms.size() * sizeof(int)));
-  HIP_CHECK(hipMemcpyAsync(d_moms, moms.data(), moms.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  arg.cs = cs;
-  int gx[3], L[3];
-  for (int d = 0; d < 3; d++) { gx[d] = cg.coords[d] * g.X[d] - p->sourcePosition[d]; L[d] = g.X[d] * cg.dims[d]; }
-  for (int t0 = 0; t0 < Lt; t0 += tc) {
-    const int nt = std::min(tc, Lt - t0);
-    arg.t0 = t0; arg.S = (long)nt * Vs;
-    mark();
-    launchStencil(arg, (int)U.reconstruct);
-    mark();
-    momentumProject(acc, cs, NBLK, t0, nt, Lt, d_moms, Nm, g.X, gx, L);
-    mark();
-  }
+  MomAccum A(NBLK, std::move(moms));
+  const int Nm = A.Nm, Vs = g.X[0] * g.X[1] * g.X[2], T = g.X[3] * cg.dims[3];
+  const size_t per = A.per();
+  int gx[3];
+  for (int d = 0; d < 3; d++) gx[d] = cg.coords[d] * g.X[d] - p->sourcePosition[d];
+  stageAndProject(A, gx, 0, [&](int t0, int nt, double2 *cs) {
+    arg.t0 = t0; arg.S = (long)nt * Vs; arg.cs = cs;
+    launchByRecon((int)U.reconstruct, threep_stencil_kernel<18>, threep_stencil_kernel<12>, threep_stencil_kernel<8>, dim3((unsigned)((arg.S / 2 + 127) / 128) * 9, 2), dim3(128), arg);
+  }, g_threepSecs + 2);
   std::vector<double> glob((size_t)NBLK * T * per);
-  gatherTimeBlocks(glob.data(), (const double *)acc, NBLK, Lt, per);   // synchronises
+  A.get(glob.data());
   p2pCheck("threepContract");
-  g_threepSecs[1] = elapsedMs(marks[0], marks[1]) * 1e-3;
-  g_threepSecs[2] = g_threepSecs[3] = 0;
-  for (size_t i = 2; i + 2 < marks.size(); i += 3) {
-    g_threepSecs[2] += elapsedMs(marks[i], marks[i + 1]) * 1e-3;
-    g_threepSecs[3] += elapsedMs(marks[i + 1], marks[i + 2]) * 1e-3;
-  }
-  for (hipEvent_t e : marks) (void)hipEventDestroy(e);
-  (void)hipFree(cs); (void)hipFree(acc); (void)hipFree(d_moms);
-  if (ghost) (void)hipFree(ghost);
+  g_threepSecs[1] = elapsedSecs(ev[0], ev[1]);
+  for (int i = 0; i < 2; i++) (void)hipEventDestroy(ev[i]);
 
   // operators, currents, the factor 1/4, source-relative time and the wrap sign on the projected matrices
   const int s = threepInsertedFlavor(p->particle, p->part);
