@@ -233,6 +233,58 @@ void qudaAmdSetLoopOutput(int enable);
 /* seconds of the last loop contraction on this rank (device events): phi, stencil (or the unfused chain), projection, all of it */
 void qudaAmdLoopLastTimings(double secs[4]);
 
+/* ---- exact deflation of the quark loops (reference QKXTM_Deflation_Kepler, lib/qudaQKXTM_Deflation_Kepler.cpp; ARPACK is replaced by a
+ * thick-restart Lanczos process on the device) ----
+ * A = M^dag M of the FULL (not even-odd) twisted-mass or twisted-clover operator made from `param` (dslash_type, kappa, mu,
+ * twist_flavor; cuda_prec must be fp64), in the normalisation of the operator the solver inverts (no mass normalisation applied).
+ * isACC != 0: the Lanczos process runs on the reference's Chebyshev filter p(A) of degree PolyDeg that is small on [amin, amax] and
+ * takes its largest Ritz values; isACC = 0: it runs on A and takes the smallest.  nKv basis vectors (nEv < nKv <= 256) stay on the
+ * device, every step orthogonalises against all of them (classical Gram-Schmidt, twice); at nKv vectors a Ritz pair counts as
+ * converged when |beta_m s_(m,i)| <= tol |theta_i|; otherwise the basis is compressed to nEv + (nKv - nEv) / 2 Ritz vectors plus the
+ * residual vector, at most maxRestarts times.  The start vector is Z4 noise keyed by the global site index.  For every returned
+ * vector lambda_i = Re (v_i, A v_i) and the residual |A v_i - lambda_i v_i| with A itself; the pairs are sorted by ASCENDING lambda
+ * (the reference keeps ARPACK's order), so the first n vectors are the n lowest modes.  nKv + 4 full fp64 fields must fit into the
+ * free device memory. */
+typedef struct { int nEv, nKv, PolyDeg, isACC, maxRestarts; double amin, amax, tol; } QudaAmdEigParam;
+/* runs the eigensolver on the resident fields and keeps the nEv eigenvectors U on the device */
+void *qudaAmdNewDeflation(QudaInvertParam *param, const QudaAmdEigParam *eig);
+void qudaAmdDestroyDeflation(void *defl);
+/* returns nEv; evals[nEv], residuals[nEv], the number of restarts and of applications of A (any of them may be NULL) */
+int qudaAmdDeflationInfo(void *defl, double *evals, double *residuals, int *restarts, int *matvecs);
+/* seconds the eigensolver spent on this rank (device events): filter (operator applications and recurrence), dots, updates, basis
+ * rotations.  QUDA_AMD_EIG_PANEL=0 in the environment runs the eigensolver on blas::multiDot / multiCaxpy in chunks of 20 fields
+ * and rotates with k multiCaxpy sweeps into spare fields instead of the panel kernels (tools/eig_timing.py compares the two). */
+void qudaAmdDeflationTimings(void *defl, double secs[4]);
+/* eigenvector i in the host layout and basis that MatQuda takes for the `param` of qudaAmdNewDeflation with a full-field solution
+ * type (cpu_prec, gamma_basis, dirac_order; even sites then odd) */
+void qudaAmdDeflationGetVector(void *defl, int i, void *h_vec);
+/* h_out = (1 - U_n U_n^+) h_in with the first n vectors, on the device (the reference: zgemv on the host); layout of
+ * qudaAmdDeflationGetVector */
+void qudaAmdDeflationProject(void *defl, int n, void *h_out, const void *h_in);
+/* the exact part of the loops, out = sum_{i<n} L[v_i] / lambda_i, L the 18 blocks of qudaAmdContractLoop with v_i in place of the
+ * solution (the reference's +1/lambda on the generalised and -1/lambda on the standard blocks, lib/qudaQKXTM_Loops_Kepler.cpp:178-281,
+ * sit in the blocks' definitions); out[18][T global][Nmoms][16][re, im] as qudaAmdContractLoop */
+void qudaAmdDeflationExactLoop(void *defl, int n, double *out, int Q_sq);
+/* dense real symmetric eigenproblem on the host (cyclic Jacobi; what the eigensolver diagonalises its projected matrix with):
+ * a[n][n] row-major (the upper triangle is read), w[n] ascending, q[n][n] row-major with COLUMN i the eigenvector of w[i] */
+void qudaAmdHostSymmetricEig(int n, const double *a, double *w, double *q);
+/* test hooks onto the eigensolver's kernels; h_V: m <= 256 vectors of V * 24 doubles (V = X[0] X[1] X[2] X[3], even) seen as V * 12
+ * complex numbers or V * 24 real rows; no resident field is needed.
+ * qudaAmdRotateBasis: V[:, 0..k) <- V[:, 0..m) Q in place, Q real m x k row-major, the columns k .. m-1 are left alone (fp64 matrix cores);
+ * qudaAmdBlockDot: c[j] = (v_j, w) = sum conj(v_j) w as c[m][re, im], one launch;  qudaAmdBlockAxpy: w -= sum_j c[j] v_j */
+void qudaAmdRotateBasis(void *h_V, int m, int k, const double *Q, const int X[4]);
+void qudaAmdBlockDot(double *c, const void *h_V, int m, const void *h_w, const int X[4]);
+void qudaAmdBlockAxpy(void *h_w, const double *c, const void *h_V, int m, const int X[4]);
+/* calcMG_loop_wOneD_TSM_wExact with arpackInfo.nEv > 0 (isFullOp, spectrumPart = SR, nKv > nEv, deflStep ascending and <= nEv): the
+ * eigensolver above with nEv, nKv, PolyDeg, isACC, amin, amax, tolArpack, maxIterArpack (arpack_logfile is ignored with a notice);
+ * every eigenvector goes to the solution sink as kind "eigvec", index i (lexicographic UKQCD, no source), before the solves.  With
+ * the loop output on, rank 0 writes for every deflStep n the exact part <loop_fname>_exact_NeV<n>_<type>.loop.<nT>_<r>, and the
+ * stochastic part is contracted from the solutions projected with the first n vectors:
+ * <loop_fname>_stoch_NeV<n>_<type>.loop.<NNNN>.<nT>_<r>, under the truncated solver method <loop_fname>_stoch_TSM_NeV<n>_NLP<NNNN>_... and
+ * the _HighPrec / _LowPrec pair.  The sink receives the UNPROJECTED solutions.  qudaAmdLastEigenvalues copies up to n eigenvalues of
+ * the last such call and returns how many there are. */
+int qudaAmdLastEigenvalues(double *evals, int n);
+
 /* ---- nucleon three-point functions by the fixed-sink sequential method (reference lib/interface_quda.cpp:6560-6950) ----
  * UKQCD basis, fp64.  s = +1 where the operator is inserted on the up quark, -1 on the down quark: proton part 1 up, part 2 down;
  * neutron part 1 down, part 2 up.  Projectors (enum WHICHPROJECTOR of qudaQKXTM_Kepler_utils.h): G4 = (1 + g4)/4,

@@ -120,7 +120,9 @@ EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLo
                  "qudaAmdMultigridSetHalfStorage", "qudaAmdMultigridGetNullVector", "qudaAmdMultigridGetV", "qudaAmdMultigridGetCoarseLinks", "qudaAmdMultigridApply", "qudaAmdMultigridApplyBlock",
                  "qudaAmdMultigridTimeApply", "qudaAmdMultigridTimeTransfer", "qudaAmdSetExitLine", "qudaAmdDiracPrepare", "qudaAmdDiracReconstruct", "qudaAmdSpinorRawInfo", "qudaAmdGaugeRawInfo", "qudaAmdCloverRawInfo", "qudaAmdRawDeviceCopy",
                  "qudaAmdSetSolutionSink", "qudaAmdCommStats", "qudaAmdDescribeHaloError", "qudaAmdMultigridOrthoFallbackBlocks", "qudaAmdProfileMarker", "qudaAmdAccountStart", "qudaAmdAccountDump", "qudaAmdWriteSpinorFields", "qudaAmdReadSpinorFields", "qudaAmdMultigridRefine", "qudaAmdMultigridSetFused", "qudaAmdMultigridFusedStats", "qudaAmdMultiSrcStats", "qudaAmdTwopMomenta", "qudaAmdTwopTimeExtent", "qudaAmdContractTwop", "qudaAmdSetTwopOutput",
-                 "qudaAmdLoopMomenta", "qudaAmdContractLoop", "qudaAmdSetLoopOutput", "qudaAmdLoopLastTimings"]
+                 "qudaAmdLoopMomenta", "qudaAmdContractLoop", "qudaAmdSetLoopOutput", "qudaAmdLoopLastTimings",
+                 "qudaAmdNewDeflation", "qudaAmdDestroyDeflation", "qudaAmdDeflationInfo", "qudaAmdDeflationTimings", "qudaAmdDeflationGetVector", "qudaAmdDeflationProject",
+                 "qudaAmdDeflationExactLoop", "qudaAmdHostSymmetricEig", "qudaAmdRotateBasis", "qudaAmdBlockDot", "qudaAmdBlockAxpy", "qudaAmdLastEigenvalues"]
 
 _lib = None
 
@@ -139,6 +141,12 @@ class QudaAmdThreepParam(C.Structure):
     """include/quda_amd_ext.h: source, sink, projector and flavour assignment of the three-point functions"""
     _fields_ = [("sourcePosition", C.c_int * 4), ("Q_sq", C.c_int), ("tsinkSource", C.c_int), ("projector", C.c_int), ("particle", C.c_int),
                 ("part", C.c_int), ("nsmearGauss", C.c_int), ("alphaGauss", C.c_double)]
+
+
+class QudaAmdEigParam(C.Structure):
+    """include/quda_amd_ext.h: the thick-restart Lanczos eigensolver behind the exact deflation of the loops"""
+    _fields_ = [("nEv", C.c_int), ("nKv", C.c_int), ("PolyDeg", C.c_int), ("isACC", C.c_int), ("maxRestarts", C.c_int),
+                ("amin", C.c_double), ("amax", C.c_double), ("tol", C.c_double)]
 
 
 # include/qudaQKXTM_Kepler_utils.h: enum WHICHPARTICLE, enum WHICHPROJECTOR
@@ -264,6 +272,30 @@ def lib():
         L.qudaAmdSetLoopOutput.restype = None
         L.qudaAmdLoopLastTimings.argtypes = [C.POINTER(_d)]
         L.qudaAmdLoopLastTimings.restype = None
+        L.qudaAmdNewDeflation.argtypes = [C.POINTER(QudaInvertParam), C.POINTER(QudaAmdEigParam)]
+        L.qudaAmdNewDeflation.restype = _p
+        L.qudaAmdDestroyDeflation.argtypes = [_p]
+        L.qudaAmdDestroyDeflation.restype = None
+        L.qudaAmdDeflationInfo.argtypes = [_p, C.POINTER(_d), C.POINTER(_d), C.POINTER(_i), C.POINTER(_i)]
+        L.qudaAmdDeflationInfo.restype = _i
+        L.qudaAmdDeflationTimings.argtypes = [_p, C.POINTER(_d)]
+        L.qudaAmdDeflationTimings.restype = None
+        L.qudaAmdDeflationGetVector.argtypes = [_p, _i, _p]
+        L.qudaAmdDeflationGetVector.restype = None
+        L.qudaAmdDeflationProject.argtypes = [_p, _i, _p, _p]
+        L.qudaAmdDeflationProject.restype = None
+        L.qudaAmdDeflationExactLoop.argtypes = [_p, _i, _p, _i]
+        L.qudaAmdDeflationExactLoop.restype = None
+        L.qudaAmdHostSymmetricEig.argtypes = [_i, _p, _p, _p]
+        L.qudaAmdHostSymmetricEig.restype = None
+        L.qudaAmdRotateBasis.argtypes = [_p, _i, _i, _p, C.POINTER(_i)]
+        L.qudaAmdRotateBasis.restype = None
+        L.qudaAmdBlockDot.argtypes = [_p, _p, _i, _p, C.POINTER(_i)]
+        L.qudaAmdBlockDot.restype = None
+        L.qudaAmdBlockAxpy.argtypes = [_p, _p, _p, _i, C.POINTER(_i)]
+        L.qudaAmdBlockAxpy.restype = None
+        L.qudaAmdLastEigenvalues.argtypes = [C.POINTER(_d), _i]
+        L.qudaAmdLastEigenvalues.restype = _i
         L.qudaAmdThreepSeqSource.argtypes = [_p, _p, _p, C.POINTER(_p), C.POINTER(QudaAmdThreepParam)]
         L.qudaAmdThreepSeqSource.restype = None
         L.qudaAmdContractThreep.argtypes = [_p, _p, _p, _p, _p, C.POINTER(_p), C.POINTER(QudaAmdThreepParam)]
@@ -561,6 +593,100 @@ def contract_loop(solution, ip, Q_sq, L):
     out = np.zeros((18, T, nm, 16, 2))
     lib().qudaAmdContractLoop(_vp(out), _vp(sol), C.byref(ip), int(Q_sq))
     return out[..., 0] + 1j * out[..., 1]
+
+
+def host_symmetric_eig(a):
+    """qudaAmdHostSymmetricEig (cyclic Jacobi, host only): ascending eigenvalues w and the matrix q whose COLUMN i is the eigenvector of
+    w[i] of the real symmetric matrix a"""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    n = a.shape[0]
+    assert a.shape == (n, n)
+    w, q = np.zeros(n), np.zeros((n, n))
+    lib().qudaAmdHostSymmetricEig(n, _vp(a), _vp(w), _vp(q))
+    return w, q
+
+
+class Deflation:
+    """qudaAmdNewDeflation: the nEv lowest eigenpairs of M^dag M of the full operator of `ip` on the resident fields, ascending, kept
+    on the device until close().  Host vectors have the layout MatQuda takes for `ip` (even sites then odd, ip.gamma_basis)."""
+
+    def __init__(self, ip, nEv, nKv, PolyDeg, amin, amax, tol, isACC=True, maxRestarts=100):
+        ep = QudaAmdEigParam(int(nEv), int(nKv), int(PolyDeg), int(bool(isACC)), int(maxRestarts), float(amin), float(amax), float(tol))
+        self._h = lib().qudaAmdNewDeflation(C.byref(ip), C.byref(ep))
+        self.nEv = int(nEv)
+        ev, res = np.zeros(self.nEv), np.zeros(self.nEv)
+        r, mv = _i(0), _i(0)
+        n = lib().qudaAmdDeflationInfo(self._h, ev.ctypes.data_as(C.POINTER(_d)), res.ctypes.data_as(C.POINTER(_d)), C.byref(r), C.byref(mv))
+        assert n == self.nEv
+        self.evals, self.residuals, self.restarts, self.matvecs = ev, res, int(r.value), int(mv.value)
+        t = (_d * 4)()
+        lib().qudaAmdDeflationTimings(self._h, t)
+        self.timings = dict(zip(("filter", "dots", "updates", "rotations"), [float(v) for v in t]))
+
+    def close(self):
+        if self._h:
+            lib().qudaAmdDestroyDeflation(self._h)
+            self._h = None
+
+    def vector(self, i, local_volume):
+        out = np.zeros(int(local_volume) * 24)
+        lib().qudaAmdDeflationGetVector(self._h, int(i), _vp(out))
+        return out
+
+    def project(self, x, n):
+        """(1 - U_n U_n^+) x with the first n vectors, on the device"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        out = np.empty_like(x)
+        lib().qudaAmdDeflationProject(self._h, int(n), _vp(out), _vp(x))
+        return out
+
+    def exact_loop(self, n, Q_sq, L):
+        """sum_{i<n} L[v_i] / lambda_i in the layout of contract_loop"""
+        nm = len(loop_momenta(L, Q_sq))
+        T = lib().qudaAmdTwopTimeExtent()
+        out = np.zeros((18, T, nm, 16, 2))
+        lib().qudaAmdDeflationExactLoop(self._h, int(n), _vp(out), int(Q_sq))
+        return out[..., 0] + 1j * out[..., 1]
+
+
+def _ext4(X):
+    return (_i * 4)(*[int(v) for v in X])
+
+
+def rotate_basis(V, Q, X):
+    """qudaAmdRotateBasis: V (m, V*24) float64 -> V[:k] <- Q^T-combinations, i.e. new V[c] = sum_j Q[j, c] V[j] for c < k; rows k.. unchanged"""
+    V = np.array(V, dtype=np.float64, order="C")
+    Q = np.ascontiguousarray(Q, dtype=np.float64)
+    m, k = Q.shape
+    assert V.shape[0] == m
+    lib().qudaAmdRotateBasis(_vp(V), m, k, _vp(Q), _ext4(X))
+    return V
+
+
+def block_dot(V, w, X):
+    """qudaAmdBlockDot: c[j] = sum conj(v_j) w for the m rows of V ((m, V*24) float64 as V*12 complex numbers)"""
+    V = np.ascontiguousarray(V, dtype=np.float64)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    c = np.zeros((V.shape[0], 2))
+    lib().qudaAmdBlockDot(_vp(c), _vp(V), V.shape[0], _vp(w), _ext4(X))
+    return c[:, 0] + 1j * c[:, 1]
+
+
+def block_axpy(w, c, V, X):
+    """qudaAmdBlockAxpy: w - sum_j c[j] v_j"""
+    V = np.ascontiguousarray(V, dtype=np.float64)
+    w = np.array(w, dtype=np.float64, order="C")
+    cc = np.ascontiguousarray(np.stack([np.real(c), np.imag(c)], axis=-1), dtype=np.float64)
+    lib().qudaAmdBlockAxpy(_vp(w), _vp(cc), _vp(V), V.shape[0], _ext4(X))
+    return w
+
+
+def last_eigenvalues():
+    """qudaAmdLastEigenvalues: the eigenvalues of the last calcMG_loop_wOneD_TSM_wExact call with nEv > 0"""
+    n = lib().qudaAmdLastEigenvalues(None, 0)
+    out = np.zeros(n)
+    lib().qudaAmdLastEigenvalues(out.ctypes.data_as(C.POINTER(_d)), n)
+    return out
 
 
 def set_loop_output(enable):

@@ -8,6 +8,7 @@
 
 #include "blas.h"
 #include "dirac.h"
+#include "eig.h"
 #include "interface_internal.h"
 #include "tune.h"
 #include "halo.h"
@@ -156,6 +157,7 @@ void endQuda(void) {
   freeStagingBuffer();
   freeBlockTables();
   freeFineBlockDots();
+  eigKernelsEnd();
   poolDeviceFlush();
   blas::end();
   commFinalize();

@@ -177,6 +177,12 @@ __global__ void __launch_bounds__(256) gamma5_kernel(double *v, int stride, int 
   }
 }
 
+// acc += s * one over n doubles: a weighted vector joins a running sum (the exact part of the loops, weights 1 / lambda)
+__global__ void __launch_bounds__(256) accum_scaled_add_kernel(double *acc, const double *one, double s, long n) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) acc[i] += s * one[i];
+}
+
 }  // namespace loop
 
 // momenta of the loops (createLoopMomenta): pz outermost, py, px innermost, each component 0 .. L/2-1, -L/2 .. -1 over the GLOBAL extent
@@ -288,9 +294,18 @@ static void chainChunk(double2 *cs, long S, int t0, const ColorSpinorField &x, c
   }
 }
 
-// A += the 18 blocks of the vector x (full fp64 device field as the solver leaves it), projected onto A's momenta
-void loopContractAdd(LoopAccum &A, ColorSpinorField &x, QudaInvertParam *param) {
+// A += scale * the 18 blocks of the vector x (full fp64 device field as the solver leaves it), projected onto A's momenta
+void loopContractAdd(LoopAccum &A, ColorSpinorField &x, QudaInvertParam *param, double scale) {
   using namespace loop;
+  if (scale != 1.0) {   // the blocks of x alone in a second accumulator of the same shape, then one weighted add: the kernels below stay as they are
+    MomAccum one(A.nblk, A.moms);
+    loopContractAdd(one, x, param, 1.0);
+    const long n = (long)A.nblk * A.Lt * (long)A.per();
+    hipLaunchKernelGGL(accum_scaled_add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, computeStream(), (double *)A.d, (const double *)one.d, scale, n);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(computeStream()));
+    return;
+  }
   if (!gaugePrecise) errorQuda("loop contraction: Gauge field not allocated");
   if (x.Location() != QUDA_CUDA_FIELD_LOCATION || x.Precision() != QUDA_DOUBLE_PRECISION || x.SiteSubset() != QUDA_FULL_SITE_SUBSET || x.Nspin() != 4 || x.Ncolor() != 3)
     errorQuda("loop contraction: expected a full fp64 device spinor");
@@ -351,7 +366,7 @@ static const bool loopTypeOneD[6] = {false, false, true, true, true, true};
 static const int loopTypeFirst[6] = {0, 1, 2, 6, 10, 14};
 
 // writeLoops_ASCII: one file per loop type and time rank r, holding that rank's time slices; rank 0 writes them all.
-// tsmTag = nullptr: <pref>_<type>.loop.<NNNN>.<nT>_<r>; "NLP" / "NHP": <pref>_<tag><NNNN>_<type>.loop.<nT>_<r>
+// tsmTag = nullptr: <pref>_<type>.loop.<NNNN>.<nT>_<r>; "NLP" / "NHP": <pref>_<tag><NNNN>_<type>.loop.<nT>_<r>; nnnn < 0 (the exact part): <pref>_<type>.loop.<nT>_<r>
 void loopWriteAscii(const LoopAccum &A, const char *pref, const char *tsmTag, int nnnn) {
   const CommGrid &cg = commGrid();
   const int Lt = A.Lt, nT = cg.dims[3], T = Lt * nT, Nm = A.Nm;
@@ -362,6 +377,7 @@ void loopWriteAscii(const LoopAccum &A, const char *pref, const char *tsmTag, in
     for (int r = 0; r < nT; r++) {
       char name[1024];
       if (tsmTag) snprintf(name, sizeof(name), "%s_%s%04d_%s.loop.%d_%d", pref, tsmTag, nnnn, loopTypeName[type], nT, r);
+      else if (nnnn < 0) snprintf(name, sizeof(name), "%s_%s.loop.%d_%d", pref, loopTypeName[type], nT, r);
       else snprintf(name, sizeof(name), "%s_%s.loop.%04d.%d_%d", pref, loopTypeName[type], nnnn, nT, r);
       for (int mu = 0; mu < (loopTypeOneD[type] ? 4 : 1); mu++) {
         FILE *f = fopen(name, mu == 0 ? "w" : "a");

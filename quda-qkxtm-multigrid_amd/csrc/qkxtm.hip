@@ -456,9 +456,7 @@ static void stochasticSource(double *h, size_t ncomplex, unsigned long seed, int
   const unsigned long long key = (unsigned long long)seed * 0x9E3779B97F4A7C15ull + (unsigned long long)commGrid().rank * 0xD1B54A32D192ED03ull + (unsigned long long)isrc * 0x94D049BB133111EBull;
   for (size_t i = 0; i < ncomplex; i++) {
     if (type == UNITY) { h[2 * i] = 1.0; h[2 * i + 1] = 0.0; continue; }
-    unsigned long long z = key + (unsigned long long)i * 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 27; z *= 0x94D049BB133111EBull; z ^= z >> 31;
-    const int r = (int)(z >> 62);
+    const int r = z4Draw(key, i);
     h[2 * i] = r == 0 ? 1.0 : (r == 1 ? -1.0 : 0.0);
     h[2 * i + 1] = r == 2 ? 1.0 : (r == 3 ? -1.0 : 0.0);
   }
@@ -466,8 +464,11 @@ static void stochasticSource(double *h, size_t ncomplex, unsigned long seed, int
 
 // the loop of calcMG_loop_wOneD_TSM_EvenOdd (reference lib/interface_quda.cpp:8535-9430).  writeLoops (the loop output switched on,
 // qudaAmdSetLoopOutput): every solution is contracted from the device-resident field after the reconstruction (loop.hip), the sums
-// over the noise vectors are cumulative and a snapshot goes to the reference's ASCII files whenever (is + 1) % Ndump == 0
-static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInfo, const qudaQKXTMinfo_Kepler &info, const char *fname, bool writeLoops) {
+// over the noise vectors are cumulative and a snapshot goes to the reference's ASCII files whenever (is + 1) % Ndump == 0.
+// defl (calcMG_loop_wOneD_TSM_wExact, reference :7940-8420): one set of accumulators per deflation step; before the contraction the
+// solution is projected off the first steps[s] eigenvectors, the sink still receives the solution itself
+static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInfo, const qudaQKXTMinfo_Kepler &info, const char *fname, bool writeLoops,
+                       Deflation *defl = nullptr, const std::vector<int> &steps = std::vector<int>()) {
   if (!gaugePrecise) errorQuda("%s: Gauge field not allocated", fname);
   if (!cloverPrecise && param->dslash_type == QUDA_TWISTED_CLOVER_DSLASH) errorQuda("%s: Clover field not allocated", fname);
   if (param->solve_type != QUDA_DIRECT_PC_SOLVE) errorQuda("%s: This function works only with Direct solve and even odd preconditioning", fname);
@@ -511,8 +512,14 @@ static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInf
   int iters = 0;
 
   // loop output: accumulator 0 the production run (then the high-precision solves of the bias run), 1 the low-precision solves of the bias run
-  LoopAccum *acc[2] = {nullptr, nullptr};
-  std::string pref[2];
+  std::vector<LoopAccum *> acc[2];
+  std::vector<std::string> pref[2];
+  const size_t nAcc = defl ? steps.size() : 1;
+  auto prefixOf = [&](size_t s) {   // :8050 with deflation, :9060 without
+    if (defl) return std::string(loopInfo.loop_fname) + (useTSM ? "_stoch_TSM_NeV" : "_stoch_NeV") + std::to_string(steps[s]);
+    return std::string(loopInfo.loop_fname) + (useTSM ? "_stoch_TSM_MG" : "_stoch_MG");
+  };
+  ColorSpinorField *deflated = nullptr;
   const char *tsmTag = nullptr;
   int Ndump = 0;
   if (writeLoops) {
@@ -521,22 +528,33 @@ static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInf
     if (loopInfo.HighMomForm) errorQuda("%s: the high-momenta form is written only as HDF5, which this library does not link; set HighMomForm = false", fname);
     if (loopInfo.FileFormat == HDF5_FORM) warningQuda("%s: HDF5 is not linked into this library; writing the loops in ASCII format", fname);
     if (info.Q_sq < 0) errorQuda("%s: Q_sq = %d", fname, info.Q_sq);
-    acc[0] = loopAccumCreate(info.Q_sq);
-    if (useTSM) acc[1] = loopAccumCreate(info.Q_sq);
+    for (size_t s = 0; s < nAcc; s++) {
+      acc[0].push_back(loopAccumCreate(info.Q_sq));
+      if (useTSM) acc[1].push_back(loopAccumCreate(info.Q_sq));
+      pref[0].push_back(prefixOf(s));
+      pref[1].push_back(std::string());
+    }
+    if (defl) deflated = new ColorSpinorField(cp64);
     int L[3];
     for (int k = 0; k < 3; k++) L[k] = g.X[k] * commGrid().dims[k];
     const int Nmoms = qudaAmdLoopMomenta(L, info.Q_sq, nullptr, 0);
     if (loopInfo.Nmoms != 0 && loopInfo.Nmoms != Nmoms) errorQuda("%s: loopInfo.Nmoms = %d, but Q_sq = %d holds %d momenta", fname, loopInfo.Nmoms, info.Q_sq, Nmoms);
     Ndump = useTSM ? loopInfo.TSM_NdumpLP : loopInfo.Ndump;
     if (Ndump <= 0 || (useTSM && loopInfo.TSM_NHP > 0 && loopInfo.TSM_NdumpHP <= 0)) errorQuda("%s: the dump interval must be positive", fname);
-    pref[0] = std::string(loopInfo.loop_fname) + (useTSM ? "_stoch_TSM_MG" : "_stoch_MG");
     tsmTag = useTSM ? "NLP" : nullptr;
   }
   // `stage` holds the reconstructed solution in the solver's normalisation (the reference contracts it without the 2 kappa rescale)
   auto absorb = [&](int which, int index) {
-    if (!acc[which]) return;
-    loopContractAdd(*acc[which], stage, param);
-    if ((index + 1) % Ndump == 0) loopWriteAscii(*acc[which], pref[which].c_str(), tsmTag, index + 1);
+    for (size_t s = 0; s < acc[which].size(); s++) {
+      ColorSpinorField *v = &stage;
+      if (defl) {
+        blas::copy(*deflated, stage);
+        deflationProject(defl, steps[s], *deflated);
+        v = deflated;
+      }
+      loopContractAdd(*acc[which][s], *v, param);
+      if ((index + 1) % Ndump == 0) loopWriteAscii(*acc[which][s], pref[which][s].c_str(), tsmTag, index + 1);
+    }
   };
 
   auto solve = [&](bool lowPrecision, const char *kind, int index, int which) {
@@ -612,9 +630,11 @@ static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInf
   // bias correction of the truncated solver method: TSM_NHP fresh sources solved to both precisions (:9170-9230)
   if (useTSM) {
     if (writeLoops) {   // :9164-9410: fresh accumulators, the high- and the low-precision sums side by side, both dumped every TSM_NdumpHP
-      acc[0]->zero();
-      pref[0] = std::string(loopInfo.loop_fname) + "_stoch_TSM_MG_HighPrec";
-      pref[1] = std::string(loopInfo.loop_fname) + "_stoch_TSM_MG_LowPrec";
+      for (size_t s = 0; s < nAcc; s++) {
+        acc[0][s]->zero();
+        pref[0][s] = prefixOf(s) + "_HighPrec";
+        pref[1][s] = prefixOf(s) + "_LowPrec";
+      }
       tsmTag = "NHP";
       Ndump = loopInfo.TSM_NdumpHP;
     }
@@ -624,7 +644,9 @@ static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInf
       solve(true, "loop_HP_LP", is, 1);
     }
   }
-  delete acc[0]; delete acc[1];
+  for (int which = 0; which < 2; which++)
+    for (LoopAccum *a : acc[which]) delete a;
+  delete deflated;
   param->secs = secs; param->gflops = gflops; param->iter = iters;
   delete d; delete dSloppy; delete dPre;
 }
@@ -777,14 +799,72 @@ void calcMG_loop_wOneD_TSM_EvenOdd(void **gaugeToPlaquette, QudaInvertParam *par
   quda::loopSolves(param, loopInfo, info, "calcMG_loop_wOneD_TSM_EvenOdd", quda::loopOutputEnabled());
 }
 
+static std::vector<double> g_lastEvals;
+extern "C" int qudaAmdLastEigenvalues(double *evals, int n) {
+  if (evals) for (int i = 0; i < n && i < (int)g_lastEvals.size(); i++) evals[i] = g_lastEvals[i];
+  return (int)g_lastEvals.size();
+}
+
 void calcMG_loop_wOneD_TSM_wExact(void **gaugeToPlaquette, QudaInvertParam *EVparam, QudaInvertParam *param, QudaGaugeParam *gauge_param,
                                   quda::qudaQKXTM_arpackInfo arpackInfo, quda::qudaQKXTM_loopInfo loopInfo, quda::qudaQKXTMinfo_Kepler info) {
-  (void)gaugeToPlaquette; (void)gauge_param; (void)EVparam;
-  if (arpackInfo.nEv != 0) errorQuda("calcMG_loop_wOneD_TSM_wExact: exact deflation with %d eigenvectors needs ARPACK, which this library does not link; nEv = 0 runs the undeflated loop", arpackInfo.nEv);
-  if (quda::loopOutputEnabled()) {
-    static bool warned = false;
-    if (!warned) warningQuda("calcMG_loop_wOneD_TSM_wExact: the exact part of the loops needs ARPACK, which this library does not link; the solves run, no loop files are written");
-    warned = true;
+  (void)gaugeToPlaquette; (void)gauge_param;
+  const char *fname = "calcMG_loop_wOneD_TSM_wExact";
+  if (arpackInfo.nEv == 0) {   // the undeflated loop: the solves run, no file is written
+    if (quda::loopOutputEnabled()) {
+      static bool warned = false;
+      if (!warned) warningQuda("%s: nEv = 0, there is no exact part of the loops; the solves run, no loop files are written", fname);
+      warned = true;
+    }
+    quda::loopSolves(param, loopInfo, info, fname, false);
+    return;
   }
-  quda::loopSolves(param, loopInfo, info, "calcMG_loop_wOneD_TSM_wExact", false);
+  // reference :7118-7126, then what its exact-loop and projection functions and this eigensolver require
+  if (!EVparam) errorQuda("%s: EVparam is NULL", fname);
+  if (EVparam->matpc_type != QUDA_MATPC_EVEN_EVEN_ASYMMETRIC && EVparam->matpc_type != QUDA_MATPC_ODD_ODD_ASYMMETRIC)
+    errorQuda("%s: EVparam->matpc_type: only asymmetric operators are supported in deflation", fname);
+  if (arpackInfo.isEven != (EVparam->matpc_type == QUDA_MATPC_EVEN_EVEN_ASYMMETRIC)) errorQuda("%s: EVparam->matpc_type: inconsistency between operator types (arpackInfo.isEven)", fname);
+  if (!arpackInfo.isFullOp) errorQuda("%s: arpackInfo.isFullOp must be set: the exact part and the projection work with the full operator", fname);
+  if (arpackInfo.nEv < 0) errorQuda("%s: arpackInfo.nEv = %d", fname, arpackInfo.nEv);
+  if (arpackInfo.spectrumPart != quda::SR) errorQuda("%s: arpackInfo.spectrumPart = %d, only SR (the smallest eigenvalues) is supported", fname, (int)arpackInfo.spectrumPart);
+  if (arpackInfo.nKv <= arpackInfo.nEv) errorQuda("%s: arpackInfo.nKv = %d must exceed nEv = %d", fname, arpackInfo.nKv, arpackInfo.nEv);
+  if (loopInfo.nSteps_defl < 1 || loopInfo.nSteps_defl > MAX_DEFLSTEPS) errorQuda("%s: loopInfo.nSteps_defl = %d (1 .. %d)", fname, loopInfo.nSteps_defl, MAX_DEFLSTEPS);
+  std::vector<int> steps(loopInfo.deflStep, loopInfo.deflStep + loopInfo.nSteps_defl);
+  for (size_t s = 0; s < steps.size(); s++)
+    if (steps[s] < 1 || steps[s] > arpackInfo.nEv || (s > 0 && steps[s] <= steps[s - 1]))
+      errorQuda("%s: loopInfo.deflStep[%d] = %d (ascending, 1 .. nEv = %d)", fname, (int)s, steps[s], arpackInfo.nEv);
+  const bool output = quda::loopOutputEnabled();
+  if (output) {
+    if (loopInfo.HighMomForm) errorQuda("%s: the high-momenta form is written only as HDF5, which this library does not link; set HighMomForm = false", fname);
+    if (info.Q_sq < 0) errorQuda("%s: Q_sq = %d", fname, info.Q_sq);
+  }
+  if (arpackInfo.arpack_logfile[0]) printfQuda("%s: arpack_logfile is ignored (the eigensolver of this library is not ARPACK)\n", fname);
+
+  QudaAmdEigParam ep;
+  ep.nEv = arpackInfo.nEv; ep.nKv = arpackInfo.nKv; ep.PolyDeg = arpackInfo.PolyDeg; ep.isACC = arpackInfo.isACC ? 1 : 0; ep.maxRestarts = arpackInfo.maxIterArpack;
+  ep.amin = arpackInfo.amin; ep.amax = arpackInfo.amax; ep.tol = arpackInfo.tolArpack;
+  quda::Deflation *defl = quda::deflationCreate(param, &ep);
+  const int nEv = quda::deflationSize(defl);
+  g_lastEvals.assign(quda::deflationEigenvalues(defl), quda::deflationEigenvalues(defl) + nEv);
+  {
+    const quda::LatticeGeom &g = quda::residentGeom();
+    const size_t vec = (size_t)g.V * 24;
+    std::vector<double> h(vec);
+    for (int i = 0; i < nEv; i++) {
+      quda::deviceToLex(h.data(), quda::deflationVector(defl, i), g, true, 1.0);
+      quda::toSink("eigvec", i, (int)param->twist_flavor, nullptr, h.data(), vec);
+    }
+  }
+  if (output) {   // reference :7643-7743: the exact part for every deflation step, one print, no dump number in the name
+    quda::LoopAccum *A = quda::loopAccumCreate(info.Q_sq);
+    int done = 0;
+    for (int n : steps) {
+      quda::deflationExactLoopAdd(defl, *A, done, n);
+      done = n;
+      const std::string pref = std::string(loopInfo.loop_fname) + "_exact_NeV" + std::to_string(n);
+      quda::loopWriteAscii(*A, pref.c_str(), nullptr, -1);
+    }
+    delete A;
+  }
+  quda::loopSolves(param, loopInfo, info, fname, output, defl, steps);
+  quda::deflationDestroy(defl);
 }

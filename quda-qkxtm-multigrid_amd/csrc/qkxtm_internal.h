@@ -26,6 +26,12 @@ GaugeField *loadLexGauge(void **gauge_lex, const LatticeGeom &g);
 void gaussianSmear(ColorSpinorField &v, const GaugeField &U, double alpha, int nsmear);
 void solveTwelveEach(QudaInvertParam *param, int flavorSign, ColorSpinorField *const sources[12], const char *fname,
                      void (*done)(void *ctx, int isc, ColorSpinorField &result, double scale), void *ctx);
+// the counter-based generator of the noise vectors: draw number `counter` of the stream `key`, one of 0 .. 3 (1, -1, i, -i)
+inline int z4Draw(unsigned long long key, unsigned long long counter) {
+  unsigned long long z = key + counter * 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 27; z *= 0x94D049BB133111EBull; z ^= z >> 31;
+  return (int)(z >> 62);
+}
 
 // ---- contract.hip: two-point functions ----
 struct TwopProps;
@@ -44,8 +50,18 @@ typedef MomAccum LoopAccum;   // [18][T_local][Nmoms][16], summed over the noise
 bool loopOutputEnabled();
 std::vector<int> loopMomenta(const int L[3], int Q_sq);
 LoopAccum *loopAccumCreate(int Q_sq);
-void loopContractAdd(LoopAccum &A, ColorSpinorField &x, QudaInvertParam *param);
+void loopContractAdd(LoopAccum &A, ColorSpinorField &x, QudaInvertParam *param, double scale = 1.0);   // A += scale * (the 18 blocks of x)
 void loopWriteAscii(const LoopAccum &A, const char *pref, const char *tsmTag, int nnnn);
+
+// ---- eigensolver.cpp: exact deflation of the loops ----
+struct Deflation;   // the lowest eigenpairs of M^dag M of the full operator, ascending, resident on the device
+Deflation *deflationCreate(QudaInvertParam *param, const QudaAmdEigParam *eig);   // runs the eigensolver
+void deflationDestroy(Deflation *d);
+int deflationSize(const Deflation *d);
+const double *deflationEigenvalues(const Deflation *d);
+ColorSpinorField &deflationVector(Deflation *d, int i);
+void deflationProject(Deflation *d, int n, ColorSpinorField &x);                  // x <- (1 - U_n U_n^+) x, the first n vectors
+void deflationExactLoopAdd(Deflation *d, LoopAccum &A, int first, int last);      // A += sum_{first <= i < last} L[v_i] / lambda_i
 
 // ---- threep.hip: three-point functions by the fixed-sink method ----
 bool threepOutputEnabled();
