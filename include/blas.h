@@ -64,6 +64,16 @@ Complex caxpyDotzy(const Complex &a, const ColorSpinorField &x, ColorSpinorField
 void caxpbypzYmbw(const Complex &a, const ColorSpinorField &x, const Complex &b, ColorSpinorField &y, ColorSpinorField &z,
                   const ColorSpinorField &w);                                         // z += a x + b y ; y -= b w
 double3_t HeavyQuarkResidualNorm(const ColorSpinorField &x, const ColorSpinorField &r);
+// the fused sweeps of CG (reference include/blas_quda.h: axpyCGNorm, axpyZpbx, tripleCGReduction, axpyReDot).  On 16-bit fields the sums of
+// axpyCGNorm / axpyReDot run over the values y holds after the store
+Complex axpyCGNorm(const double &a, const ColorSpinorField &x, ColorSpinorField &y);   // y += a x ; (|y|^2, (y_new, y_new - y_old))
+void axpyZpbx(const double &a, ColorSpinorField &x, ColorSpinorField &y, const ColorSpinorField &z, const double &b);   // y += a x ; x = z + b x
+double3_t tripleCGReduction(const ColorSpinorField &x, const ColorSpinorField &y, const ColorSpinorField &z);          // (|x|^2, |y|^2, (y, z))
+double axpyReDot(const double &a, const ColorSpinorField &x, ColorSpinorField &y);      // y += a x ; (x, y)
+// multi-shift CG: x_i += alpha_i p_i ; p_i = zeta_i r + beta_i p_i for i < k in sweeps of at most multiShiftChunk() shifts, each reading r once
+int multiShiftChunk();
+void multiShiftUpdate(int k, const std::vector<ColorSpinorField *> &x, const std::vector<ColorSpinorField *> &p, const ColorSpinorField &r, const double *alpha,
+                      const double *beta, const double *zeta);
 // multi-field forms for the blocked orthogonalisation of GCR (reference lib/inv_gcr_quda.cpp:53-84, :103-121: N dots / N caxpys per pass),
 // k <= 20 fields of fp64 / fp32 (multiSupported):
 //   multiDot:            beta[i] = (f_i, y) for i < k, yr = (y, r), ynorm = |y|^2                       — one sweep

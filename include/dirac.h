@@ -196,7 +196,8 @@ class DiracM : public DiracMatrix {
 class DiracMdagM : public DiracMatrix {
  public:
   using DiracMatrix::DiracMatrix;
-  void operator()(ColorSpinorField &out, const ColorSpinorField &in) const override { dirac->MdagM(out, in); }
+  double shift = 0.0;   // out = (M^dag M + shift) in (reference include/dirac_quda.h DiracMdagM::shift); 0: M^dag M alone, no extra sweep
+  void operator()(ColorSpinorField &out, const ColorSpinorField &in) const override;
 };
 class DiracMdag : public DiracMatrix {
  public:

@@ -181,6 +181,9 @@ void invertQuda(void *h_x, void *h_b, QudaInvertParam *param);       /* ref quda
 /* param->num_src sources through ONE lockstep solve (GCR, optionally MG-preconditioned: the cycle below the fine level runs on block fields
  * through the multi-right-hand-side MFMA coarse operator); ref quda.h:647, whose own implementation "cannot work" (interface_quda.cpp:2546-2549) */
 void invertMultiSrcQuda(void **_hp_x, void **_hp_b, QudaInvertParam *param);
+/* Solve for multiple shifts (e.g., masses): (A + offset[i]) x_i = b, A = M^dag M, for param->num_offset ascending offsets with multi-shift CG,
+ * each shift refined by CG where its true residual misses tol_offset[i]; ref quda.h:657; interface_quda.cpp:2913 */
+void invertMultiShiftQuda(void **_hp_x, void *_hp_b, QudaInvertParam *param);
 void *newMultigridQuda(QudaMultigridParam *param);                   /* ref quda.h:666; interface_quda.cpp:2257 */
 void destroyMultigridQuda(void *mg_instance);                        /* ref quda.h:671 */
 

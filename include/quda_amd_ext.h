@@ -57,6 +57,29 @@ double qudaAmdBlasNorm2(const void *field);
 void qudaAmdBlasCDot(const void *x, const void *y, double result[2]);
 void qudaAmdBlasAxpy(double a, const void *x, void *y);
 double qudaAmdTimeAxpy(double a, const void *x, void *y, int niter);   /* seconds per y += a x, device-event timed */
+/* the fused sweeps of CG and multi-shift CG (include/blas.h) on qudaAmdSpinor handles of one precision and geometry:
+ *   AxpyCGNorm          y += a x ; result = (|y|^2, (y_new, y_new - y_old))
+ *   AxpyZpbx            y += a x ; x = z + b x
+ *   TripleCGReduction   result = (|x|^2, |y|^2, (y, z))
+ *   AxpyReDot           y += a x ; returns (x, y)
+ *   MultiShiftUpdate    x[i] += alpha[i] p[i] ; p[i] = zeta[i] r + beta[i] p[i] for i < k, r read once per sweep of at most
+ *                       qudaAmdBlasMultiShiftChunk() shifts */
+void qudaAmdBlasAxpyCGNorm(double a, const void *x, void *y, double result[2]);
+void qudaAmdBlasAxpyZpbx(double a, void *x, void *y, const void *z, double b);
+void qudaAmdBlasTripleCGReduction(const void *x, const void *y, const void *z, double result[3]);
+double qudaAmdBlasAxpyReDot(double a, const void *x, void *y);
+void qudaAmdBlasMultiShiftUpdate(int k, void *x[], void *p[], const void *r, const double *alpha, const double *beta, const double *zeta);
+int qudaAmdBlasMultiShiftChunk(void);
+/* out = (M^dag M + shift) in through the DiracMdagM functor the solvers use; shift = 0 launches exactly what qudaAmdDiracMdagM does */
+void qudaAmdDiracMdagMShift(void *dirac, void *out, const void *in, double shift);
+/* device-event timed loops for tools/cg_timing.py, seconds per pass:
+ *   TimeMdagM          out = M^dag M in
+ *   TimeCGBlas         the vector work of ONE CG iteration on four fields; fused != 0: reDotProduct, axpyCGNorm, axpyZpbx (three sweeps);
+ *                      fused == 0: the same update from reDotProduct, axpy, norm2, reDotProduct, axpy, xpay (the calls it replaces)
+ *   TimeMultiShift     fused != 0: MultiShiftUpdate of k shifts; fused == 0: per shift axpy then axpby (the calls it replaces) */
+double qudaAmdTimeMdagM(void *dirac, void *out, const void *in, int niter);
+double qudaAmdTimeCGBlas(int fused, void *x, void *r, void *p, void *Ap, int niter);
+double qudaAmdTimeMultiShift(int fused, int k, void *x[], void *p[], const void *r, int niter);
 
 /* algorithmic work model of the stencil kernel behind Dirac::Dslash */
 long long qudaAmdDslashBytesPerSite(QudaInvertParam *inv_param, int which, int xpay);

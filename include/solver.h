@@ -1,7 +1,8 @@
 // solver.h — Krylov layer of the MG-GCR path: GCR (outer solver, K-cycle coarse solver), MR (smoother),
 // BiCGstab (null-vector setup).  Interface mirrors the reference (include/invert_quda.h:15-331: SolverParam,
 // Solver::create, operator()(x, b)); algorithms restated from lib/inv_gcr_quda.cpp:53-516,
-// lib/inv_mr_quda.cpp:40-200, lib/inv_bicgstab_quda.cpp:40-354, lib/solver.cpp:13-150.
+// lib/inv_mr_quda.cpp:40-200, lib/inv_bicgstab_quda.cpp:40-354, lib/solver.cpp:13-150.  CG and multi-shift CG on Hermitian positive
+// definite operators (M^dag M): lib/inv_cg_quda.cpp:40-360, lib/inv_multi_cg_quda.cpp:115-527.
 #pragma once
 
 #include <vector>
@@ -37,9 +38,14 @@ struct SolverParam {
   bool is_preconditioner = false;
   bool global_reduction = true;
   bool compute_true_res = true;
+  // multi-shift solves (reference include/invert_quda.h:108-130)
+  int num_offset = 0;
+  double offset[QUDA_MAX_MULTI_SHIFT] = {}, tol_offset[QUDA_MAX_MULTI_SHIFT] = {}, true_res_offset[QUDA_MAX_MULTI_SHIFT] = {},
+         iter_res_offset[QUDA_MAX_MULTI_SHIFT] = {};
   SolverParam() {}
   explicit SolverParam(const QudaInvertParam &p);   // reference include/invert_quda.h:197-255
   void updateInvertParam(QudaInvertParam &p) const; // reference :262-300
+  void updateMultiShiftParam(QudaInvertParam &p) const;   // true_res_offset[], iter_res_offset[] of a multi-shift solve (reference :278-290)
 };
 
 class Solver {
@@ -98,6 +104,26 @@ class GCR : public Solver {
   GCR(DiracMatrix &mat, Solver &K, DiracMatrix &matSloppy, DiracMatrix &matPrecon, SolverParam &param);
   ~GCR() override;
   void operator()(ColorSpinorField &out, ColorSpinorField &in) override;
+};
+
+// CG on a Hermitian positive definite operator (mat = matSloppy in another precision).  Equal precisions: the textbook recurrence in that
+// precision.  Lower sloppy precision: x, r, p, Ap of the iteration are sloppy fields, a precise y accumulates x and the true residual
+// replaces the iterated one whenever the latter has dropped by param.delta since the last such reliable update.
+class CG : public Solver {
+  const DiracMatrix &mat, &matSloppy;
+ public:
+  CG(DiracMatrix &mat, DiracMatrix &matSloppy, SolverParam &param);
+  void operator()(ColorSpinorField &out, ColorSpinorField &in) override;
+};
+
+// (A + offset_i) x_i = b for param.num_offset ascending offsets with the Krylov space of the smallest one; fills param.true_res_offset[],
+// param.iter_res_offset[] (precise operator / recurrence).  Not a Solver: it has as many solutions as shifts (reference MultiShiftSolver).
+class MultiShiftCG {
+  SolverParam &param;
+  const DiracMatrix &mat, &matSloppy;
+ public:
+  MultiShiftCG(DiracMatrix &mat, DiracMatrix &matSloppy, SolverParam &param);
+  void operator()(std::vector<ColorSpinorField *> &x, ColorSpinorField &b);
 };
 
 void fillInnerSolveParam(SolverParam &inner, const SolverParam &outer);  // reference lib/inv_gcr_quda.cpp:17-50

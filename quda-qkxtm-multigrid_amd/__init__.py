@@ -107,7 +107,7 @@ class QudaMultigridParam(C.Structure):
 # every extern "C" symbol include/quda.h and include/quda_amd_ext.h declare
 QUDA_H_SYMBOLS = ["setVerbosityQuda", "initCommsGridQuda", "initQudaDevice", "initQudaMemory", "initQuda", "endQuda",
                   "newQudaGaugeParam", "newQudaInvertParam", "newQudaMultigridParam", "printQudaGaugeParam", "printQudaInvertParam",
-                  "printQudaMultigridParam", "loadGaugeQuda", "freeGaugeQuda", "loadCloverQuda", "freeCloverQuda", "invertQuda", "invertMultiSrcQuda",
+                  "printQudaMultigridParam", "loadGaugeQuda", "freeGaugeQuda", "loadCloverQuda", "freeCloverQuda", "invertQuda", "invertMultiSrcQuda", "invertMultiShiftQuda",
                   "newMultigridQuda", "destroyMultigridQuda", "dslashQuda", "cloverQuda", "MatQuda", "MatDagMatQuda", "openMagma",
                   "closeMagma"]
 EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLoad", "qudaAmdSpinorSave", "qudaAmdSpinorCopy",
@@ -122,7 +122,9 @@ EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLo
                  "qudaAmdSetSolutionSink", "qudaAmdCommStats", "qudaAmdDescribeHaloError", "qudaAmdMultigridOrthoFallbackBlocks", "qudaAmdProfileMarker", "qudaAmdAccountStart", "qudaAmdAccountDump", "qudaAmdWriteSpinorFields", "qudaAmdReadSpinorFields", "qudaAmdMultigridRefine", "qudaAmdMultigridSetFused", "qudaAmdMultigridFusedStats", "qudaAmdMultiSrcStats", "qudaAmdTwopMomenta", "qudaAmdTwopTimeExtent", "qudaAmdContractTwop", "qudaAmdSetTwopOutput",
                  "qudaAmdLoopMomenta", "qudaAmdContractLoop", "qudaAmdSetLoopOutput", "qudaAmdLoopLastTimings",
                  "qudaAmdNewDeflation", "qudaAmdDestroyDeflation", "qudaAmdDeflationInfo", "qudaAmdDeflationTimings", "qudaAmdDeflationGetVector", "qudaAmdDeflationProject",
-                 "qudaAmdDeflationExactLoop", "qudaAmdHostSymmetricEig", "qudaAmdRotateBasis", "qudaAmdBlockDot", "qudaAmdBlockAxpy", "qudaAmdLastEigenvalues"]
+                 "qudaAmdDeflationExactLoop", "qudaAmdHostSymmetricEig", "qudaAmdRotateBasis", "qudaAmdBlockDot", "qudaAmdBlockAxpy", "qudaAmdLastEigenvalues",
+                 "qudaAmdBlasAxpyCGNorm", "qudaAmdBlasAxpyZpbx", "qudaAmdBlasTripleCGReduction", "qudaAmdBlasAxpyReDot", "qudaAmdBlasMultiShiftUpdate",
+                 "qudaAmdBlasMultiShiftChunk", "qudaAmdDiracMdagMShift", "qudaAmdTimeMdagM", "qudaAmdTimeCGBlas", "qudaAmdTimeMultiShift"]
 
 _lib = None
 
@@ -202,6 +204,28 @@ def lib():
         L.invertQuda.argtypes = [_p, _p, C.POINTER(QudaInvertParam)]
         L.invertMultiSrcQuda.argtypes = [_p, _p, C.POINTER(QudaInvertParam)]
         L.invertMultiSrcQuda.restype = None
+        L.invertMultiShiftQuda.argtypes = [_p, _p, C.POINTER(QudaInvertParam)]
+        L.invertMultiShiftQuda.restype = None
+        L.qudaAmdBlasAxpyCGNorm.argtypes = [_d, _p, _p, C.POINTER(_d)]
+        L.qudaAmdBlasAxpyCGNorm.restype = None
+        L.qudaAmdBlasAxpyZpbx.argtypes = [_d, _p, _p, _p, _d]
+        L.qudaAmdBlasAxpyZpbx.restype = None
+        L.qudaAmdBlasTripleCGReduction.argtypes = [_p, _p, _p, C.POINTER(_d)]
+        L.qudaAmdBlasTripleCGReduction.restype = None
+        L.qudaAmdBlasAxpyReDot.argtypes = [_d, _p, _p]
+        L.qudaAmdBlasAxpyReDot.restype = _d
+        L.qudaAmdBlasMultiShiftUpdate.argtypes = [_i, C.POINTER(_p), C.POINTER(_p), _p, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]
+        L.qudaAmdBlasMultiShiftUpdate.restype = None
+        L.qudaAmdBlasMultiShiftChunk.argtypes = []
+        L.qudaAmdBlasMultiShiftChunk.restype = _i
+        L.qudaAmdDiracMdagMShift.argtypes = [_p, _p, _p, _d]
+        L.qudaAmdDiracMdagMShift.restype = None
+        L.qudaAmdTimeMdagM.argtypes = [_p, _p, _p, _i]
+        L.qudaAmdTimeMdagM.restype = _d
+        L.qudaAmdTimeCGBlas.argtypes = [_i, _p, _p, _p, _p, _i]
+        L.qudaAmdTimeCGBlas.restype = _d
+        L.qudaAmdTimeMultiShift.argtypes = [_i, _i, C.POINTER(_p), C.POINTER(_p), _p, _i]
+        L.qudaAmdTimeMultiShift.restype = _d
         L.cloverQuda.argtypes = [_p, _p, C.POINTER(QudaInvertParam), C.POINTER(_i), _i]
         L.loadGaugeQuda.argtypes = [_p, C.POINTER(QudaGaugeParam)]
         L.loadCloverQuda.argtypes = [_p, _p, C.POINTER(QudaInvertParam)]
@@ -444,6 +468,40 @@ def invert(h_b, ip, out=None):
     x = np.zeros_like(h_b) if out is None else out
     lib().invertQuda(_vp(x), _vp(h_b), C.byref(ip))
     return x
+
+
+def invert_multi_shift(h_b, ip, offsets, tols, out=None):
+    """invertMultiShiftQuda: (A + offsets[i]) x_i = h_b, A = M^dag M of ip (NORMOP solve types, CG), for ascending offsets with the
+    tolerances tols[i]; returns the list of solutions.  ip.num_offset, ip.offset[] and ip.tol_offset[] are set here; the per-shift
+    residuals are left in ip.true_res_offset[] / ip.iter_res_offset[], the total iteration count in ip.iter"""
+    n = len(offsets)
+    if len(tols) != n or not 1 <= n <= QUDA_MAX_MULTI_SHIFT:
+        raise ValueError("one tolerance per offset, 1 <= number of offsets <= %d" % QUDA_MAX_MULTI_SHIFT)
+    b = np.ascontiguousarray(h_b)
+    xs = out if out is not None else [np.zeros_like(b) for _ in range(n)]
+    if len(xs) != n or any(x.shape != b.shape or x.dtype != b.dtype or not x.flags.c_contiguous for x in xs):
+        raise ValueError("out must hold one contiguous array per offset, of the source's shape and type")
+    ip.num_offset = n
+    for i in range(n):
+        ip.offset[i], ip.tol_offset[i] = float(offsets[i]), float(tols[i])
+    px = (_p * n)(*[_vp(x) for x in xs])
+    lib().invertMultiShiftQuda(px, _vp(b), C.byref(ip))
+    return xs
+
+
+def multi_shift_chunk():
+    """qudaAmdBlasMultiShiftChunk: shifts one sweep of Spinor.multi_shift_update covers"""
+    return int(lib().qudaAmdBlasMultiShiftChunk())
+
+
+def multi_shift_update(x, p, r, alpha, beta, zeta):
+    """qudaAmdBlasMultiShiftUpdate on lists of Spinor: x[i] += alpha[i] p[i] ; p[i] = zeta[i] r + beta[i] p[i]"""
+    k = len(x)
+    if not (len(p) == len(alpha) == len(beta) == len(zeta) == k):
+        raise ValueError("x, p, alpha, beta, zeta must have one entry per shift")
+    hx, hp = (_p * max(k, 1))(*[f.h for f in x]), (_p * max(k, 1))(*[f.h for f in p])
+    a, b, z = [(_d * max(k, 1))(*[float(v) for v in c]) for c in (alpha, beta, zeta)]
+    lib().qudaAmdBlasMultiShiftUpdate(k, hx, hp, r.h, a, b, z)
 
 
 def multi_src_stats():
@@ -789,6 +847,27 @@ class Spinor:
     def norm2(self):
         return lib().qudaAmdBlasNorm2(self.h)
 
+    # the fused sweeps of CG (include/blas.h); self is the field called y there
+    def axpy_cg_norm(self, a, x):
+        """self += a x; returns (|self|^2, (self_new, self_new - self_old))"""
+        r = (_d * 2)()
+        lib().qudaAmdBlasAxpyCGNorm(float(a), x.h, self.h, r)
+        return r[0], r[1]
+
+    def axpy_zpbx(self, a, x, z, b):
+        """self += a x; x = z + b x"""
+        lib().qudaAmdBlasAxpyZpbx(float(a), x.h, self.h, z.h, float(b))
+
+    def axpy_re_dot(self, a, x):
+        """self += a x; returns (x, self)"""
+        return lib().qudaAmdBlasAxpyReDot(float(a), x.h, self.h)
+
+    def triple_cg_reduction(self, y, z):
+        """(|self|^2, |y|^2, (y, z))"""
+        r = (_d * 3)()
+        lib().qudaAmdBlasTripleCGReduction(self.h, y.h, z.h, r)
+        return r[0], r[1], r[2]
+
     def raw_info(self):
         """qudaAmdSpinorRawInfo as a dict"""
         a = (C.c_longlong * 20)()
@@ -842,6 +921,13 @@ class Dirac:
 
     def MdagM(self, out, inp):
         lib().qudaAmdDiracMdagM(self.h, out.h, inp.h)
+
+    def MdagM_shift(self, out, inp, shift):
+        """out = (M^dag M + shift) inp through the DiracMdagM functor of the solvers"""
+        lib().qudaAmdDiracMdagMShift(self.h, out.h, inp.h, float(shift))
+
+    def time_MdagM(self, out, inp, niter):
+        return lib().qudaAmdTimeMdagM(self.h, out.h, inp.h, int(niter))
 
     def prepare(self, src_out, x, b, solution_type):
         """Dirac::prepare on resident full fields; the source of the (preconditioned) system is copied into src_out"""

@@ -385,6 +385,86 @@ struct CaxpbypzYmbwF { double ar, ai, br, bi; QA_FLAGS(1, 1, 1, 1, 0, 1, 1, 0, 0
     }
   } };
 
+// ---- CG (reference lib/inv_cg_quda.cpp:196-227, lib/inv_multi_cg_quda.cpp:325-356): the four fused sweeps of an iteration.
+// The functors that update a field AND sum over the updated values have a second form, site(), for the 16-bit fields: there the sums
+// run over the values the field HOLDS after the store (int16 times the new per-site scale, storedImage), not over the fp32 registers
+// the store rounds.  |r|^2 and (r_new, r_new - r_old) then describe the residual the next iteration reads back, which is what the
+// reliable-update logic compares against; for fp64 / fp32 fields the registers are what is stored and the two forms coincide. ----
+template <typename T, int M> __device__ __forceinline__ void storedImage(typename Store<T>::real *out, const typename Store<T>::real *v) {
+  if constexpr (Store<T>::fixed) {   // Planar<short, M>::store followed by ::load, operation by operation
+    float m = 0.f;
+#pragma unroll
+    for (int k = 0; k < M; k++) m = fmaxf(m, fabsf(v[k]));
+    const float s = m > 0.f ? kShortMax / m : 0.f, back = m * kShortInv;
+#pragma unroll
+    for (int k = 0; k < M; k++) out[k] = Planar<short, M>::q16(v[k] * s) * back;
+  } else {
+#pragma unroll
+    for (int k = 0; k < M; k++) out[k] = v[k];
+  }
+}
+// y += a x ; (|y|^2, (y_new, y_new - y_old))
+struct AxpyCGNormF { double a; QA_FLAGS(1, 1, 0, 0, 0, 1, 0, 0, 2)
+  template <typename real, int M> __device__ void operator()(real *x, real *y, real *, real *, double *r) const {
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+      const double yo = y[i];
+      y[i] = (real)a * x[i] + y[i];
+      const double yn = y[i];
+      r[0] += yn * yn;
+      r[1] += yn * (yn - yo);
+    }
+  }
+  template <typename T, typename real, int M> __device__ void site(real *x, real *y, real *, real *, double *r) const {
+    real yo[M], img[M];
+#pragma unroll
+    for (int i = 0; i < M; i++) { yo[i] = y[i]; y[i] = (real)a * x[i] + y[i]; }
+    storedImage<T, M>(img, y);
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+      const double yn = img[i];
+      r[0] += yn * yn;
+      r[1] += yn * (yn - (double)yo[i]);
+    }
+  } };
+// y += a x ; x = z + b x
+struct AxpyZpbxF { double a, b; QA_FLAGS(1, 1, 1, 0, 1, 1, 0, 0, 0)
+  template <typename real, int M> __device__ void operator()(real *x, real *y, real *z, real *, double *) const {
+#pragma unroll
+    for (int i = 0; i < M; i++) { y[i] += (real)a * x[i]; x[i] = z[i] + (real)b * x[i]; }
+  } };
+// (|x|^2, |y|^2, (y, z))
+struct TripleCGF { QA_FLAGS(1, 1, 1, 0, 0, 0, 0, 0, 3)
+  template <typename real, int M> __device__ void operator()(real *x, real *y, real *z, real *, double *r) const {
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+      const double xv = x[i], yv = y[i], zv = z[i];
+      r[0] += xv * xv; r[1] += yv * yv; r[2] += yv * zv;
+    }
+  } };
+// y += a x ; (x, y)
+struct AxpyReDotF { double a; QA_FLAGS(1, 1, 0, 0, 0, 1, 0, 0, 1)
+  template <typename real, int M> __device__ void operator()(real *x, real *y, real *, real *, double *r) const {
+#pragma unroll
+    for (int i = 0; i < M; i++) { y[i] += (real)a * x[i]; r[0] += (double)x[i] * (double)y[i]; }
+  }
+  template <typename T, typename real, int M> __device__ void site(real *x, real *y, real *, real *, double *r) const {
+    real img[M];
+#pragma unroll
+    for (int i = 0; i < M; i++) y[i] += (real)a * x[i];
+    storedImage<T, M>(img, y);
+#pragma unroll
+    for (int i = 0; i < M; i++) r[0] += (double)x[i] * (double)img[i];
+  } };
+// site-by-site (16-bit) call of a functor: its site() form where it has one
+template <typename T, typename real, int M, typename F>
+__device__ __forceinline__ auto blas_site(const F &f, real *x, real *y, real *z, real *w, double *r, int) -> decltype(f.template site<T, real, M>(x, y, z, w, r), void()) {
+  f.template site<T, real, M>(x, y, z, w, r);
+}
+template <typename T, typename real, int M, typename F> __device__ __forceinline__ void blas_site(const F &f, real *x, real *y, real *z, real *w, double *r, long) {
+  f.template operator()<real, M>(x, y, z, w, r);
+}
+
 // ---- the tail of every reducing kernel: wave shuffles -> LDS -> per-block partial -> the LAST block (completion counter) adds the
 // partials in block order (bit-reproducible), optionally does the all-reduce over ranks through the peer windows, and writes the
 // sums to device and pinned host memory.  NRED sums per thread come in, every thread of the block must call it. ----
@@ -530,7 +610,7 @@ __global__ void __launch_bounds__(256) blas_kernel(BlasArg<F> arg) {
     if (F::ry) Planar<T, M>::load(y, arg.y.v[seg], arg.stride, (int)j, arg.y.norm[seg], (int)j);
     if (F::rz) Planar<T, M>::load(z, arg.z.v[seg], arg.stride, (int)j, arg.z.norm[seg], (int)j);
     if (F::rw) Planar<T, M>::load(w, arg.w.v[seg], arg.stride, (int)j, arg.w.norm[seg], (int)j);
-    f.template operator()<real, M>(x, y, z, w, red);
+    blas_site<T, real, M>(f, x, y, z, w, red, 0);
     if (F::wx) Planar<T, M>::store(x, arg.x.v[seg], arg.stride, (int)j, arg.x.norm[seg], (int)j);
     if (F::wy) Planar<T, M>::store(y, arg.y.v[seg], arg.stride, (int)j, arg.y.norm[seg], (int)j);
     if (F::wz) Planar<T, M>::store(z, arg.z.v[seg], arg.stride, (int)j, arg.z.norm[seg], (int)j);
@@ -641,6 +721,72 @@ template <typename real, int M, bool RES, int KB> __global__ void __launch_bound
     }
   }
   if (RES) finish_reduction<2>(red, arg.c);
+}
+
+// ================================================================================================
+// Shifted update of multi-shift CG (reference lib/inv_multi_cg_quda.cpp:88-104: axpyBzpcx once per shift):
+//   x_i += alpha_i p_i ; p_i = zeta_i r + beta_i p_i      for the K active shifts of a chunk, K <= kShiftKB
+// in ONE sweep that reads r once: 4 K + 1 field passes where the per-shift form has 5 K.  K is a template parameter (no surplus slots:
+// every slot is written), the coefficients sit in the kernel argument.  fp64 / fp32 fields are flat arrays of 16-byte chunks, all
+// 2 K + 1 loads of a chunk issued before the first use; 16-bit fields go site by site and shift by shift (24 fp32 registers per
+// operand), the coefficients and field addresses then read from the argument with a wave-uniform index.
+// ================================================================================================
+constexpr int kShiftKB = 8;
+struct ShiftArg {
+  Seg x[kShiftKB], p[kShiftKB], r;
+  double alpha[kShiftKB], beta[kShiftKB], zeta[kShiftKB];
+  int nseg, stride;   // stride: the plane stride of the site path
+  long n;             // chunks (sites) per segment
+};
+template <typename T, int M, bool SITE, int K> __global__ void __launch_bounds__(256) multi_shift_update_kernel(const ShiftArg arg) {
+  using real = typename Store<T>::real;
+  const long total = arg.n * arg.nseg;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int seg = i >= arg.n ? 1 : 0;
+    const long j = i - seg * arg.n;
+    if constexpr (!SITE) {
+      using V = Chunk<real, M>;
+      V xv[K], pv[K];
+      const V r = reinterpret_cast<const V *>(arg.r.v[seg])[j];
+#pragma unroll
+      for (int d = 0; d < K; d++) {
+        xv[d] = reinterpret_cast<const V *>(arg.x[d].v[seg])[j];
+        pv[d] = reinterpret_cast<const V *>(arg.p[d].v[seg])[j];
+      }
+#pragma unroll
+      for (int d = 0; d < K; d++) {
+        const real al = (real)arg.alpha[d], be = (real)arg.beta[d], ze = (real)arg.zeta[d];
+#pragma unroll
+        for (int e = 0; e < M; e++) {
+          xv[d].v[e] += al * pv[d].v[e];
+          pv[d].v[e] = ze * r.v[e] + be * pv[d].v[e];
+        }
+        reinterpret_cast<V *>(arg.x[d].v[seg])[j] = xv[d];
+        reinterpret_cast<V *>(arg.p[d].v[seg])[j] = pv[d];
+      }
+    } else {
+      alignas(16) real r[M];
+      Planar<T, M>::load(r, arg.r.v[seg], arg.stride, (int)j, arg.r.norm[seg], (int)j);
+#pragma unroll 1
+      for (int d = 0; d < K; d++) {
+        // d is wave-uniform (scalar loads from the argument), seg is not: both segments' addresses, then a select
+        void *xb = seg ? arg.x[d].v[1] : arg.x[d].v[0], *pb = seg ? arg.p[d].v[1] : arg.p[d].v[0];
+        float *xn = seg ? arg.x[d].norm[1] : arg.x[d].norm[0], *pn = seg ? arg.p[d].norm[1] : arg.p[d].norm[0];
+        alignas(16) real x[M];
+        alignas(16) real p[M];
+        Planar<T, M>::load(x, xb, arg.stride, (int)j, xn, (int)j);
+        Planar<T, M>::load(p, pb, arg.stride, (int)j, pn, (int)j);
+        const real al = (real)arg.alpha[d], be = (real)arg.beta[d], ze = (real)arg.zeta[d];
+#pragma unroll
+        for (int e = 0; e < M; e++) {
+          x[e] += al * p[e];
+          p[e] = ze * r[e] + be * p[e];
+        }
+        Planar<T, M>::store(x, xb, arg.stride, (int)j, xn, (int)j);
+        Planar<T, M>::store(p, pb, arg.stride, (int)j, pn, (int)j);
+      }
+    }
+  }
 }
 
 static Seg segOf(const ColorSpinorField &f) {
@@ -859,6 +1005,52 @@ void multiCaxpy(const Complex *c, const std::vector<ColorSpinorField *> &f, int 
   flops += (unsigned long long)(8 * k) * (y.RealLength() / 2);
 }
 
+int multiShiftChunk() { return kShiftKB; }
+void multiShiftUpdate(int k, const std::vector<ColorSpinorField *> &x, const std::vector<ColorSpinorField *> &p, const ColorSpinorField &r, const double *alpha,
+                      const double *beta, const double *zeta) {
+  if (k < 0 || (int)x.size() < k || (int)p.size() < k) errorQuda("multiShiftUpdate: %d shifts wanted, %zu / %zu fields given", k, x.size(), p.size());
+  for (int i = 0; i < k; i++) {
+    checkSame(r, *x[i]);
+    checkSame(r, *p[i]);
+    if (x[i] == &r || p[i] == &r || x[i] == p[i]) errorQuda("multiShiftUpdate: x_%d, p_%d and r must be three fields", i, i);
+  }
+  hipStream_t s = computeStream();
+  for (int k0 = 0; k0 < k; k0 += kShiftKB) {   // chunks of at most kShiftKB shifts; r is read once per chunk
+    const int kk = k - k0 < kShiftKB ? k - k0 : kShiftKB;
+    ShiftArg a;
+    a.r = segOf(r);
+    for (int d = 0; d < kShiftKB; d++) {
+      const int i = k0 + (d < kk ? d : 0);   // slots past kk are not touched by the K = kk kernel; keep them defined
+      a.x[d] = segOf(*x[i]); a.p[d] = segOf(*p[i]);
+      a.alpha[d] = alpha[i]; a.beta[d] = beta[i]; a.zeta[d] = zeta[i];
+    }
+    a.nseg = r.SiteSubset() == QUDA_FULL_SITE_SUBSET ? 2 : 1;
+    a.stride = r.Stride();
+    const long nreal = (long)r.Stride() * r.Nspin() * r.Ncolor() * 2;
+#define QA_MS(T, M, SITE, K) hipLaunchKernelGGL((multi_shift_update_kernel<T, M, SITE, K>), dim3(multiGrid(a.n * a.nseg, 2048)), dim3(256), 0, s, a)
+#define QA_MSK(T, M, SITE) \
+  switch (kk) { case 1: QA_MS(T, M, SITE, 1); break; case 2: QA_MS(T, M, SITE, 2); break; case 3: QA_MS(T, M, SITE, 3); break; case 4: QA_MS(T, M, SITE, 4); break; \
+                case 5: QA_MS(T, M, SITE, 5); break; case 6: QA_MS(T, M, SITE, 6); break; case 7: QA_MS(T, M, SITE, 7); break; default: QA_MS(T, M, SITE, 8); break; }
+    static_assert(kShiftKB == 8, "the dispatch above lists K = 1..8");
+    switch (r.Precision()) {
+      case QUDA_DOUBLE_PRECISION: a.n = nreal / 2; QA_MSK(double, 2, false) break;
+      case QUDA_SINGLE_PRECISION:
+        if (nreal % 4) errorQuda("field length %ld not a multiple of 4", nreal);
+        a.n = nreal / 4; QA_MSK(float, 4, false) break;
+      case QUDA_HALF_PRECISION:
+        if (r.Nspin() != 4 || r.Ncolor() != 3) errorQuda("16-bit blas only for fine-grid spinors");
+        a.n = r.VolumeCB(); QA_MSK(short, 24, true) break;
+      default: errorQuda("bad precision %d", r.Precision());
+    }
+#undef QA_MSK
+#undef QA_MS
+    HIP_CHECK(hipGetLastError());
+    acct("multi_shift_update_kernel", (double)(4 * kk + 1) * r.RealLength() * r.Precision(), r.Nspin() == 4 ? "level 0" : "coarse");
+    bytes += (unsigned long long)(4 * kk + 1) * r.RealLength() * r.Precision();
+    flops += (unsigned long long)(5 * kk) * r.RealLength();
+  }
+}
+
 void zero(ColorSpinorField &a) { a.zero(); }
 void copy(ColorSpinorField &dst, const ColorSpinorField &src) { copyColorSpinor(dst, src); }
 
@@ -934,6 +1126,19 @@ Complex caxpyDotzy(const Complex &a, const ColorSpinorField &x, ColorSpinorField
 void caxpbypzYmbw(const Complex &a, const ColorSpinorField &x, const Complex &b, ColorSpinorField &y, ColorSpinorField &z, const ColorSpinorField &w) {
   CaxpbypzYmbwF f; f.ar = a.real(); f.ai = a.imag(); f.br = b.real(); f.bi = b.imag();
   launch(f, x, &y, &z, &w, nullptr);
+}
+
+Complex axpyCGNorm(const double &a, const ColorSpinorField &x, ColorSpinorField &y) {
+  AxpyCGNormF f; f.a = a; double r[2]; launch(f, x, &y, nullptr, nullptr, r); return Complex(r[0], r[1]);
+}
+void axpyZpbx(const double &a, ColorSpinorField &x, ColorSpinorField &y, const ColorSpinorField &z, const double &b) {
+  AxpyZpbxF f; f.a = a; f.b = b; launch(f, x, &y, &z, nullptr, nullptr);
+}
+double3_t tripleCGReduction(const ColorSpinorField &x, const ColorSpinorField &y, const ColorSpinorField &z) {
+  double r[3]; launch(TripleCGF(), x, &y, &z, nullptr, r); return {r[0], r[1], r[2]};
+}
+double axpyReDot(const double &a, const ColorSpinorField &x, ColorSpinorField &y) {
+  AxpyReDotF f; f.a = a; double r[1]; launch(f, x, &y, nullptr, nullptr, r); return r[0];
 }
 
 // heavy-quark residual: sum_sites |r(x)|^2 / |x(x)|^2 — needs the site structure (reference lib/blas_cpu.cpp:311-352)

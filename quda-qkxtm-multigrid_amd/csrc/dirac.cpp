@@ -55,6 +55,11 @@ void Dirac::MMdag(ColorSpinorField &out, const ColorSpinorField &in) const {
   flipDagger();
 }
 
+void DiracMdagM::operator()(ColorSpinorField &out, const ColorSpinorField &in) const {
+  dirac->MdagM(out, in);
+  if (shift != 0.0) blas::axpy(shift, in, out);
+}
+
 void Dirac::hopDir(ColorSpinorField &, const ColorSpinorField &, int) const { errorQuda("hopDir not available for Dirac type %d", type); }
 void Dirac::localTerm(ColorSpinorField &, const ColorSpinorField &) const { errorQuda("localTerm not available for Dirac type %d", type); }
 void Dirac::localTermParity(ColorSpinorField &, const ColorSpinorField &, int) const { errorQuda("localTermParity not available for Dirac type %d", type); }

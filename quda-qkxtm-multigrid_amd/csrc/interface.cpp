@@ -589,6 +589,77 @@ void qudaAmdBlasCDot(const void *x, const void *y, double r[2]) {
   r[0] = c.real(); r[1] = c.imag();
 }
 void qudaAmdBlasAxpy(double a, const void *x, void *y) { blas::axpy(a, *(const ColorSpinorField *)x, *(ColorSpinorField *)y); }
+void qudaAmdBlasAxpyCGNorm(double a, const void *x, void *y, double r[2]) {
+  const Complex c = blas::axpyCGNorm(a, *(const ColorSpinorField *)x, *(ColorSpinorField *)y);
+  r[0] = c.real(); r[1] = c.imag();
+}
+void qudaAmdBlasAxpyZpbx(double a, void *x, void *y, const void *z, double b) {
+  blas::axpyZpbx(a, *(ColorSpinorField *)x, *(ColorSpinorField *)y, *(const ColorSpinorField *)z, b);
+}
+void qudaAmdBlasTripleCGReduction(const void *x, const void *y, const void *z, double r[3]) {
+  const double3_t t = blas::tripleCGReduction(*(const ColorSpinorField *)x, *(const ColorSpinorField *)y, *(const ColorSpinorField *)z);
+  r[0] = t.x; r[1] = t.y; r[2] = t.z;
+}
+double qudaAmdBlasAxpyReDot(double a, const void *x, void *y) { return blas::axpyReDot(a, *(const ColorSpinorField *)x, *(ColorSpinorField *)y); }
+static std::vector<ColorSpinorField *> fieldList(void *f[], int k) {
+  std::vector<ColorSpinorField *> v(k > 0 ? k : 0);
+  for (int i = 0; i < k; i++) v[i] = (ColorSpinorField *)f[i];
+  return v;
+}
+void qudaAmdBlasMultiShiftUpdate(int k, void *x[], void *p[], const void *r, const double *alpha, const double *beta, const double *zeta) {
+  blas::multiShiftUpdate(k, fieldList(x, k), fieldList(p, k), *(const ColorSpinorField *)r, alpha, beta, zeta);
+}
+int qudaAmdBlasMultiShiftChunk(void) { return blas::multiShiftChunk(); }
+void qudaAmdDiracMdagMShift(void *d, void *out, const void *in, double shift) {
+  DiracMdagM m((const Dirac *)d);
+  m.shift = shift;
+  m(*(ColorSpinorField *)out, *(const ColorSpinorField *)in);
+}
+// device-event timed loops behind tools/cg_timing.py
+extern "C++" template <typename Body> static double timeLoop(int niter, const char *who, Body body) {
+  hipEvent_t e0, e1;
+  HIP_CHECK(hipEventCreate(&e0));
+  HIP_CHECK(hipEventCreate(&e1));
+  HIP_CHECK(hipEventRecord(e0, computeStream()));
+  for (int i = 0; i < niter; i++) body();
+  HIP_CHECK(hipEventRecord(e1, computeStream()));
+  HIP_CHECK(hipEventSynchronize(e1));
+  p2pCheck(who);
+  float ms = 0;
+  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  HIP_CHECK(hipEventDestroy(e0));
+  HIP_CHECK(hipEventDestroy(e1));
+  return 1e-3 * ms / niter;
+}
+double qudaAmdTimeMdagM(void *d, void *out, const void *in, int niter) {
+  return timeLoop(niter, __func__, [&] { ((Dirac *)d)->MdagM(*(ColorSpinorField *)out, *(const ColorSpinorField *)in); });
+}
+double qudaAmdTimeCGBlas(int fused, void *x_, void *r_, void *p_, void *Ap_, int niter) {
+  ColorSpinorField &x = *(ColorSpinorField *)x_, &r = *(ColorSpinorField *)r_, &p = *(ColorSpinorField *)p_, &Ap = *(ColorSpinorField *)Ap_;
+  const double alpha = 1e-3, beta = 0.5;   // fixed coefficients: the fields stay bounded over the loop, the traffic is that of an iteration
+  if (fused) return timeLoop(niter, __func__, [&] {
+    (void)blas::reDotProduct(p, Ap);
+    (void)blas::axpyCGNorm(-alpha, Ap, r);
+    blas::axpyZpbx(alpha, p, x, r, beta);
+  });
+  return timeLoop(niter, __func__, [&] {
+    (void)blas::reDotProduct(p, Ap);
+    blas::axpy(-alpha, Ap, r);
+    (void)blas::norm2(r);
+    (void)blas::reDotProduct(r, Ap);   // stands for the second sum of axpyCGNorm
+    blas::axpy(alpha, p, x);
+    blas::xpay(r, beta, p);
+  });
+}
+double qudaAmdTimeMultiShift(int fused, int k, void *x[], void *p[], const void *r_, int niter) {
+  const ColorSpinorField &r = *(const ColorSpinorField *)r_;
+  const std::vector<ColorSpinorField *> xv = fieldList(x, k), pv = fieldList(p, k);
+  std::vector<double> alpha(k > 0 ? k : 1, 1e-3), beta(k > 0 ? k : 1, 0.5), zeta(k > 0 ? k : 1, 0.25);
+  if (fused) return timeLoop(niter, __func__, [&] { blas::multiShiftUpdate(k, xv, pv, r, alpha.data(), beta.data(), zeta.data()); });
+  return timeLoop(niter, __func__, [&] {
+    for (int i = 0; i < k; i++) { blas::axpy(alpha[i], *pv[i], *xv[i]); blas::axpby(zeta[i], r, beta[i], *pv[i]); }
+  });
+}
 // device-event timed y += a x loop: the streaming-bandwidth yardstick printed beside the stencil numbers
 double qudaAmdTimeAxpy(double a, const void *x, void *y, int niter) {
   hipEvent_t e0, e1;

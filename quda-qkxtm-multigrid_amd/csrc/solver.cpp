@@ -26,6 +26,12 @@ SolverParam::SolverParam(const QudaInvertParam &p)
       omega(p.omega), schwarz_type(p.schwarz_type), secs(p.secs), gflops(p.gflops), verbosity_precondition(p.verbosity_precondition) {
   if (precondition_cycle < 1) precondition_cycle = 1;
   if ((int)residual_type == QUDA_INVALID_ENUM || residual_type == 0) residual_type = QUDA_L2_RELATIVE_RESIDUAL;
+  num_offset = (p.num_offset > 0 && p.num_offset <= QUDA_MAX_MULTI_SHIFT) ? p.num_offset : 0;   // single solves leave it unset
+  for (int i = 0; i < num_offset; i++) { offset[i] = p.offset[i]; tol_offset[i] = p.tol_offset[i]; }
+}
+
+void SolverParam::updateMultiShiftParam(QudaInvertParam &p) const {
+  for (int i = 0; i < num_offset; i++) { p.true_res_offset[i] = true_res_offset[i]; p.iter_res_offset[i] = iter_res_offset[i]; }
 }
 
 void SolverParam::updateInvertParam(QudaInvertParam &p) const {
@@ -82,7 +88,8 @@ Solver *Solver::create(SolverParam &param, DiracMatrix &mat, DiracMatrix &matSlo
       return new GCR(mat, matSloppy, matPrecon, param);
     case QUDA_MR_INVERTER: return new MR(mat, matSloppy, param);
     case QUDA_BICGSTAB_INVERTER: return new BiCGstab(mat, matSloppy, matPrecon, param);
-    default: errorQuda("Invalid solver type %d (GCR, MR and BiCGstab are on the MG-GCR path)", param.inv_type);
+    case QUDA_CG_INVERTER: return new CG(mat, matSloppy, param);
+    default: errorQuda("Invalid solver type %d (CG, GCR, MR and BiCGstab are available)", param.inv_type);
   }
   return nullptr;
 }
