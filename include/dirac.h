@@ -105,15 +105,30 @@ class DiracWilsonPC : public DiracWilson {
   void reconstruct(ColorSpinorField &x, const ColorSpinorField &b, const QudaSolutionType) const override;
 };
 
-// ---- twisted mass (degenerate; the non-degenerate doublet is out of scope) ----
+// ---- twisted mass: the degenerate flavours +-1 and the non-degenerate doublet 1 + i a g5 tau3 + b tau1 on two-flavour fields
+// (reference lib/dirac_twisted_mass.cpp:47-79, :266-286).  The doublet operators run the fused doublet stencil (both flavours per link
+// load) where no direction is partitioned, and otherwise — or with the tune key "ndeg_fused" = 0 — are composed of the single-flavour
+// stencil on the two Flavor() views and the flavour-mixing site kernel (applyNdegTwist).  Multigrid (hopDir / localTerm*), twisted clover, multi-source
+// solves and the QKXTM drivers remain out of scope for the doublet ----
 class DiracTwistedMass : public DiracWilson {
  protected:
   double mu, epsilon;
+  mutable ColorSpinorField *tmp3 = nullptr;   // doublet: pre-twisted input of D^dag A^-1^dag, site term of the asymmetric operator
+  mutable bool own3 = false;
   void twistedApply(ColorSpinorField &out, const ColorSpinorField &in, QudaTwistGamma5Type twistType) const;
   void checkFlavor(const ColorSpinorField &out, const ColorSpinorField &in) const;
+  static bool doublet(const ColorSpinorField &f) { return f.TwistFlavor() == QUDA_TWIST_NONDEG_DOUBLET; }
+  // out = t, or out = x + k t, with t = A in (direct) or A^-1 in (inverse) on one parity doublet, dagger taken from the operator
+  void ndegTwist(ColorSpinorField &out, const ColorSpinorField &in, QudaTwistGamma5Type twistType, const ColorSpinorField *x = nullptr, double k = 0.0) const;
+  void ndegCoefficients(QudaTwistGamma5Type twistType, double &a, double &b, double &d) const;
+  // one launch of the fused doublet stencil (unpartitioned lattice): inverse twist: out = A^-1 D in, or x + k A^-1 D in; direct: out = k D in + A x
+  void ndegFused(ColorSpinorField &out, const ColorSpinorField &in, QudaParity parity, QudaTwistGamma5Type twistType, const ColorSpinorField *x = nullptr,
+                 double k = 0.0) const;
 
  public:
   explicit DiracTwistedMass(const DiracParam &p) : DiracWilson(p), mu(p.mu), epsilon(p.epsilon) {}
+  ~DiracTwistedMass() override { if (own3) delete tmp3; }
+  double Epsilon() const { return epsilon; }
   double Mu() const override { return mu; }
   void Twist(ColorSpinorField &out, const ColorSpinorField &in) const;
   void localTerm(ColorSpinorField &out, const ColorSpinorField &in) const override;

@@ -28,6 +28,11 @@ struct DslashParam {
   const ColorSpinorField *x = nullptr;  // xpay field or nullptr
   const CloverField *clover = nullptr;
   int kernel_type = 0;  // 0 interior(+all if unpartitioned), 1 exterior
+  // fused doublet stencil (unpartitioned lattice): out, in and x are parity DOUBLETS, one launch computes both flavours and reads every
+  // link once.  mode DSLASH_PLAIN: D on both flavours [xpay]; DSLASH_TWIST_INV: out = b (1 + i a g5 tau3 + nb tau1) acc [x + ...], i.e.
+  // A^-1 D with b = d (times k); DSLASH_TWIST_XPAY: out = k acc + (1 + i a g5 tau3 + nb tau1) x
+  int ndeg = 0;
+  double nb = 0;
 };
 
 // out(parity) = stencil(in(other parity)); fields must be device parity fields of equal precision.
@@ -86,6 +91,13 @@ enum SiteOp {
 void applySite(ColorSpinorField &out, const ColorSpinorField &in, SiteOp op, double a, double b, const CloverField *clover,
                int parity, bool inverse);
 
+// flavour mixing of the non-degenerate twisted-mass doublet on a device parity doublet (ColorSpinorField::Nflavor() == 2):
+//   t1 = d (in1 + i a g5 in1 + b in2),  t2 = d (in2 - i a g5 in2 + b in1);  out = t, or out = x + k t with a doublet x.  out may be in or x
+// its coefficients (reference setTwistParam): direct a = 2 kappa mu, b = -2 kappa epsilon, d = 1; inverse a = -2 kappa mu, b = +2 kappa epsilon,
+// d = 1 / (1 + a^2 - b^2), an error unless that is positive; dagger flips a
+void ndegTwistCoefficients(double kappa, double mu, double epsilon, bool inverse, bool dagger, double &a, double &b, double &d);
+void applyNdegTwist(ColorSpinorField &out, const ColorSpinorField &in, double a, double b, double d, const ColorSpinorField *x = nullptr, double k = 0.0);
+
 // launch geometry of the stencil kernel (block size, XCD mapping, block order); see launchDslash
 struct DslashTune {
   int block = 0;       // threads per block; 0: the largest of 256/192/128/64 that divides an (x, y) plane
@@ -105,12 +117,16 @@ struct DslashTune {
   // the same on every rank
   int halo_format = -1;
   int edge_first = 1;  // peer-store launch, plane-tiled order: every XCD starts with its boundary planes
+  int ndeg_fused = -1; // non-degenerate doublet: 1 / -1 the fused doublet stencil where no direction is partitioned, 0 the composed operators (QUDA_AMD_NDEG_FUSED).
+                       // The fused launch honours block, remap, order, tiled / nxz / tz / tt / ygroups, store_aux, link_aux and lds_pad; it does not use the launch-parameter cache
 };
 DslashTune &dslashTune();
+bool ndegFusedSelected();   // the doublet operators use the fused stencil: asked for (or automatic) and no direction partitioned
 void setDslashTune(const char *key, int value);
 
 // analytic work model per checkerboard site
 long long dslashFlopsPerSite(DslashMode mode, bool xpay);
 long long dslashBytesPerSite(QudaPrecision prec, int recon, DslashMode mode, bool xpay);
+long long ndegDslashBytesPerSite(QudaPrecision prec, int recon, bool xpay);   // fused doublet stencil, per checkerboard site of the 4-d lattice
 
 }  // namespace quda

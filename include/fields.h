@@ -27,6 +27,9 @@ struct ColorSpinorParam {
   QudaFieldLocation location = QUDA_CUDA_FIELD_LOCATION;
   int nColor = 3, nSpin = 4, nDim = 4;
   int x[QUDA_MAX_DIM] = {0, 0, 0, 0, 0, 0};  // x[0] already halved for parity fields (reference convention)
+  // non-degenerate twisted-mass doublet: nDim = 5 and x[4] = 2, the reference's flavour dimension (tests/invert_test.cpp:461-473)
+  void setFlavors(int n) { if (n == 2) { nDim = 5; x[4] = 2; } else { nDim = 4; x[4] = 0; } }
+  int flavors() const { return nDim == 5 && x[4] == 2 ? 2 : 1; }
   QudaPrecision precision = QUDA_DOUBLE_PRECISION;
   int pad = 0;
   bool planePad = true;  // device spin-4 fields: add the library's plane padding (fieldPadSites) to pad; false in the param() of an existing field, whose pad already holds it
@@ -48,7 +51,8 @@ class ColorSpinorField {
   QudaFieldLocation location;
   int nColor, nSpin, nDim;
   int x[4];            // x[0] halved for parity fields
-  int volume, volumeCB, stride, pad;
+  int nFlavor;         // 2: flavour doublet (nDim = 5).  Every plane holds flavour 1's sites, then flavour 2's: checkerboard index f * Vh + i
+  int volume, volumeCB, stride, pad;   // volume, volumeCB and stride count both flavours of a doublet: BLAS and the solvers see a longer parity field
   QudaPrecision precision;
   QudaSiteSubset siteSubset;
   QudaSiteOrder siteOrder;
@@ -59,7 +63,7 @@ class ColorSpinorField {
   void *v_;
   void *norm_;
   bool owns;
-  ColorSpinorField *even_, *odd_;
+  ColorSpinorField *even_, *odd_, *flavor_[2];
 
   explicit ColorSpinorField(const ColorSpinorParam &param);
   ColorSpinorField(const ColorSpinorField &src);  // deep copy, same location/layout
@@ -79,7 +83,9 @@ class ColorSpinorField {
   QudaPrecision Precision() const { return precision; }
   QudaSiteSubset SiteSubset() const { return siteSubset; }
   QudaTwistFlavorType TwistFlavor() const { return twistFlavor; }
-  void changeTwist(QudaTwistFlavorType f) { twistFlavor = f; if (even_) even_->twistFlavor = f; if (odd_) odd_->twistFlavor = f; }
+  int Nflavor() const { return nFlavor; }
+  int VolumeCB4() const { return volumeCB / nFlavor; }   // checkerboard sites of the 4-d lattice
+  void changeTwist(QudaTwistFlavorType f);   // to or from the doublet: an error, the flavour count of a field is fixed
   QudaFieldLocation Location() const { return location; }
   size_t Bytes() const { return bytes; }
   long Length() const { return (long)(siteSubset == QUDA_FULL_SITE_SUBSET ? 2 : 1) * stride * nColor * nSpin * 2; }
@@ -89,6 +95,10 @@ class ColorSpinorField {
   ColorSpinorField &Odd();
   const ColorSpinorField &Even() const { return const_cast<ColorSpinorField *>(this)->Even(); }
   const ColorSpinorField &Odd() const { return const_cast<ColorSpinorField *>(this)->Odd(); }
+  // one flavour (0, 1) of a device parity doublet as a 4-d field of the same stride, twist flavour +1 / -1.  Stencil and site kernels
+  // only: the flat BLAS kernels run over whole planes and must not see a view
+  ColorSpinorField &Flavor(int f);
+  const ColorSpinorField &Flavor(int f) const { return const_cast<ColorSpinorField *>(this)->Flavor(f); }
 
   void zero();
   // full local lattice dims (x[0] un-halved)

@@ -22,5 +22,6 @@ void setDiracParam(DiracParam &dp, QudaInvertParam *inv, const bool pc);
 void setDiracSloppyParam(DiracParam &dp, QudaInvertParam *inv, const bool pc);
 void setDiracPreParam(DiracParam &dp, QudaInvertParam *inv, const bool pc);
 ColorSpinorParam deviceSpinorParam(QudaPrecision prec, QudaSiteSubset subset, QudaTwistFlavorType flavor);
+QudaTwistFlavorType fieldTwistFlavor(const QudaInvertParam &inv);   // inv.twist_flavor, except that only the twisted-mass operator has a doublet
 
 }  // namespace quda

@@ -32,6 +32,10 @@ void qudaAmdSpinorLoad(void *field, const void *h_src, const QudaInvertParam *in
 void qudaAmdSpinorSave(const void *field, void *h_dst, const QudaInvertParam *inv_param);
 void qudaAmdSpinorCopy(void *dst, const void *src);   /* device-device, any precision pair */
 void qudaAmdSpinorSetTwist(void *field, QudaTwistFlavorType flavor);
+/* flavour mixing of the non-degenerate twisted-mass doublet on resident doublet fields (created with QUDA_TWIST_NONDEG_DOUBLET: two flavours,
+   [flavour 1][flavour 2] per parity); out may be in.  direct: 1 + i a g5 tau3 + b tau1 with a = 2 kappa mu, b = -2 kappa epsilon; inverse != 0:
+   its inverse; dagger != 0 flips the sign of a */
+void qudaAmdNdegTwist(void *out, const void *in, double kappa, double mu, double epsilon, int dagger, int inverse);
 
 /* operator object built from the resident gauge/clover fields.
  * pc != 0: even-odd preconditioned type (Dirac::create of *PC_DIRAC); which: 0 precise, 1 sloppy, 2 precondition */

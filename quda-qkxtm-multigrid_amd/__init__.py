@@ -45,6 +45,7 @@ QUDA_EVEN_PARITY, QUDA_ODD_PARITY = 0, 1
 QUDA_PARITY_SITE_SUBSET, QUDA_FULL_SITE_SUBSET = 1, 2
 QUDA_DEGRAND_ROSSI_GAMMA_BASIS, QUDA_UKQCD_GAMMA_BASIS = 0, 1
 QUDA_TWIST_MINUS, QUDA_TWIST_PLUS, QUDA_TWIST_NO = -1, 1, 0
+QUDA_TWIST_NONDEG_DOUBLET = 2   # two-flavour fields, host layout [flavour 1][flavour 2] per parity
 QUDA_USE_INIT_GUESS_NO, QUDA_USE_INIT_GUESS_YES = 0, 1
 QUDA_COMPUTE_NULL_VECTOR_NO, QUDA_COMPUTE_NULL_VECTOR_YES = 0, 1
 QUDA_BOOLEAN_NO, QUDA_BOOLEAN_YES = 0, 1
@@ -124,7 +125,8 @@ EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLo
                  "qudaAmdNewDeflation", "qudaAmdDestroyDeflation", "qudaAmdDeflationInfo", "qudaAmdDeflationTimings", "qudaAmdDeflationGetVector", "qudaAmdDeflationProject",
                  "qudaAmdDeflationExactLoop", "qudaAmdHostSymmetricEig", "qudaAmdRotateBasis", "qudaAmdBlockDot", "qudaAmdBlockAxpy", "qudaAmdLastEigenvalues",
                  "qudaAmdBlasAxpyCGNorm", "qudaAmdBlasAxpyZpbx", "qudaAmdBlasTripleCGReduction", "qudaAmdBlasAxpyReDot", "qudaAmdBlasMultiShiftUpdate",
-                 "qudaAmdBlasMultiShiftChunk", "qudaAmdDiracMdagMShift", "qudaAmdTimeMdagM", "qudaAmdTimeCGBlas", "qudaAmdTimeMultiShift"]
+                 "qudaAmdBlasMultiShiftChunk", "qudaAmdDiracMdagMShift", "qudaAmdTimeMdagM", "qudaAmdTimeCGBlas", "qudaAmdTimeMultiShift",
+                 "qudaAmdNdegTwist"]
 
 _lib = None
 
@@ -178,6 +180,9 @@ def lib():
         L.qudaAmdSpinorSave.argtypes = [_p, _p, C.POINTER(QudaInvertParam)]
         L.qudaAmdSpinorCopy.argtypes = [_p, _p]
         L.qudaAmdSpinorSetTwist.argtypes = [_p, _i]
+        if hasattr(L, "qudaAmdNdegTwist"):   # absent from a build of an earlier commit loaded through QUDA_AMD_LIBRARY (tools/ndeg_timing.py --parent-lib)
+            L.qudaAmdNdegTwist.argtypes = [_p, _p, _d, _d, _d, _i, _i]
+            L.qudaAmdNdegTwist.restype = None
         L.qudaAmdDiracCreate.argtypes = [C.POINTER(QudaInvertParam), _i, _i]
         L.qudaAmdDiracDestroy.argtypes = [_p]
         L.qudaAmdDiracDslash.argtypes = [_p, _p, _p, _i]
@@ -364,12 +369,12 @@ def gauge_param(X, cpu_prec=QUDA_DOUBLE_PRECISION, cuda_prec=QUDA_DOUBLE_PRECISI
 
 def invert_param(dslash_type=QUDA_TWISTED_MASS_DSLASH, kappa=0.1, mu=0.01, flavor=QUDA_TWIST_PLUS, matpc="ee", dagger=0,
                  cpu_prec=QUDA_DOUBLE_PRECISION, cuda_prec=QUDA_DOUBLE_PRECISION, prec_sloppy=None, prec_precondition=None,
-                 solution_type=QUDA_MATPC_SOLUTION, gamma_basis=QUDA_DEGRAND_ROSSI_GAMMA_BASIS, dirac_order=QUDA_DIRAC_ORDER):
+                 solution_type=QUDA_MATPC_SOLUTION, gamma_basis=QUDA_DEGRAND_ROSSI_GAMMA_BASIS, dirac_order=QUDA_DIRAC_ORDER, epsilon=0.0):
     ip = lib().newQudaInvertParam()
     ip.dslash_type = dslash_type
     ip.kappa = kappa
     ip.mu = mu
-    ip.epsilon = 0.0
+    ip.epsilon = epsilon   # flavour splitting of the non-degenerate doublet (flavor=QUDA_TWIST_NONDEG_DOUBLET)
     ip.mass = 0.5 / kappa - 4.0
     ip.twist_flavor = flavor if dslash_type != QUDA_WILSON_DSLASH else QUDA_TWIST_NO
     ip.matpc_type = MATPC[matpc] if isinstance(matpc, str) else matpc
@@ -832,6 +837,7 @@ class Spinor:
     """Device-resident ColorSpinorField handle (quda_amd_ext.h)."""
 
     def __init__(self, prec, subset=QUDA_PARITY_SITE_SUBSET, flavor=QUDA_TWIST_PLUS):
+        """flavor=QUDA_TWIST_NONDEG_DOUBLET: a two-flavour field, loaded from / saved to host arrays of twice the size"""
         self.h = lib().qudaAmdSpinorCreate(int(prec), int(subset), int(flavor))
         self.prec, self.subset = prec, subset
 
@@ -880,6 +886,16 @@ class Spinor:
         if self.h:
             lib().qudaAmdSpinorDestroy(self.h)
             self.h = None
+
+
+def ndeg_twist(out, inp, kappa, mu, epsilon, dagger=0, inverse=0):
+    """qudaAmdNdegTwist on resident doublet Spinors: out = (1 + i a g5 tau3 + b tau1) inp with a = 2 kappa mu, b = -2 kappa epsilon, or
+    its inverse; dagger flips a; out may be inp"""
+    L = lib()
+    if not hasattr(L, "qudaAmdNdegTwist"):
+        raise RuntimeError("%s does not export qudaAmdNdegTwist: it was built before the non-degenerate doublet" % LIB_PATH)
+    L.qudaAmdNdegTwist(out.h, inp.h, float(kappa), float(mu), float(epsilon), int(dagger), int(inverse))
+    return out
 
 
 def raw_device_copy(address, nbytes):

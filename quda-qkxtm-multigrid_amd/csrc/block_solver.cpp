@@ -981,6 +981,7 @@ void qudaAmdMultiSrcStats(long long out[4]) { for (int i = 0; i < 4; i++) out[i]
 // are those of the lockstep solve, true_res the worst source's.
 void invertMultiSrcQuda(void **_hp_x, void **_hp_b, QudaInvertParam *param) {
   if (!gaugePrecise) errorQuda("Gauge field not allocated");
+  if (param->twist_flavor == QUDA_TWIST_NONDEG_DOUBLET) errorQuda("invertMultiSrcQuda: the multi-source solver is not available for the non-degenerate doublet");
   if (param->tune == QUDA_TUNE_YES || param->tune == QUDA_TUNE_NO) setTuning(param->tune);
   if (!cloverPrecise && param->dslash_type == QUDA_TWISTED_CLOVER_DSLASH) errorQuda("Clover field not allocated");
   const int ns = param->num_src;

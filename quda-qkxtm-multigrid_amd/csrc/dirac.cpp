@@ -21,7 +21,7 @@ Dirac::~Dirac() {
 
 ColorSpinorField *Dirac::getTmp(ColorSpinorField *&slot, bool &own, const ColorSpinorField &like) const {
   if (slot && (slot->VolumeCB() != like.VolumeCB() || slot->Precision() != like.Precision() || slot->SiteSubset() != like.SiteSubset() ||
-               slot->Ncolor() != like.Ncolor() || slot->Nspin() != like.Nspin())) {
+               slot->Ncolor() != like.Ncolor() || slot->Nspin() != like.Nspin() || slot->Nflavor() != like.Nflavor())) {
     if (own) { delete slot; slot = nullptr; own = false; }
     else errorQuda("caller-supplied temporary does not match the operand geometry");
   }
@@ -32,7 +32,7 @@ ColorSpinorField *Dirac::getTmp(ColorSpinorField *&slot, bool &own, const ColorS
     slot = new ColorSpinorField(p);
     own = true;
   }
-  slot->twistFlavor = like.twistFlavor;
+  slot->changeTwist(like.twistFlavor);
   return slot;
 }
 
@@ -90,7 +90,13 @@ void DiracWilson::Dslash(ColorSpinorField &out, const ColorSpinorField &in, cons
   checkParitySpinor(in, out);
   DslashParam p;
   p.mode = DSLASH_PLAIN; p.parity = parity; p.dagger = dagger == QUDA_DAG_YES;
-  applyDslash(out, in, *gauge, p);
+  if (in.Nflavor() == 2) {   // the hop is flavour-diagonal: one fused launch for both flavours, or one application per flavour view (Volume() counts both)
+    if (out.Nflavor() != 2) errorQuda("doublet input, single-flavour output");
+    if (ndegFusedSelected()) { p.ndeg = 1; applyDslash(out, in, *gauge, p); }
+    else for (int f = 0; f < 2; f++) applyDslash(out.Flavor(f), in.Flavor(f), *gauge, p);
+  } else {
+    applyDslash(out, in, *gauge, p);
+  }
   flops += 1320ll * in.Volume();
 }
 
@@ -99,7 +105,13 @@ void DiracWilson::DslashXpay(ColorSpinorField &out, const ColorSpinorField &in, 
   checkParitySpinor(in, out);
   DslashParam p;
   p.mode = DSLASH_PLAIN; p.parity = parity; p.dagger = dagger == QUDA_DAG_YES; p.x = &x; p.k = k;
-  applyDslash(out, in, *gauge, p);
+  if (in.Nflavor() == 2) {
+    if (out.Nflavor() != 2 || x.Nflavor() != 2) errorQuda("doublet input, single-flavour output or xpay field");
+    if (ndegFusedSelected()) { p.ndeg = 1; applyDslash(out, in, *gauge, p); }
+    else for (int f = 0; f < 2; f++) { p.x = &x.Flavor(f); applyDslash(out.Flavor(f), in.Flavor(f), *gauge, p); }
+  } else {
+    applyDslash(out, in, *gauge, p);
+  }
   flops += 1368ll * in.Volume();
 }
 
@@ -118,6 +130,7 @@ void DiracWilson::MdagM(ColorSpinorField &out, const ColorSpinorField &in) const
 // M = 1 - kappa D: H_d = -kappa (1 -+ gamma_mu) U, L = 1
 void DiracWilson::hopDir(ColorSpinorField &out, const ColorSpinorField &in, int dir) const {
   checkFullSpinor(out, in);
+  if (in.Nflavor() == 2) errorQuda("hopDir: the multigrid construction is not available for the non-degenerate doublet");
   applyHopDir(out.Odd(), in.Even(), *gauge, QUDA_ODD_PARITY, dir, -kappa);
   applyHopDir(out.Even(), in.Odd(), *gauge, QUDA_EVEN_PARITY, dir, -kappa);
 }
@@ -178,13 +191,45 @@ void DiracWilsonPC::reconstruct(ColorSpinorField &x, const ColorSpinorField &b, 
 // ================================================================================================
 void DiracTwistedMass::checkFlavor(const ColorSpinorField &out, const ColorSpinorField &in) const {
   if (in.TwistFlavor() != out.TwistFlavor()) errorQuda("Twist flavors %d %d don't match", in.TwistFlavor(), out.TwistFlavor());
+  if (doublet(in)) {
+    if (in.Nflavor() != 2 || out.Nflavor() != 2) errorQuda("the non-degenerate doublet needs two-flavour fields (got %d, %d flavours)", in.Nflavor(), out.Nflavor());
+    return;
+  }
   if (in.TwistFlavor() != QUDA_TWIST_PLUS && in.TwistFlavor() != QUDA_TWIST_MINUS)
-    errorQuda("Twist flavor %d not supported (degenerate +-1 only)", in.TwistFlavor());
+    errorQuda("Twist flavor %d not supported (degenerate +-1 or the non-degenerate doublet)", in.TwistFlavor());
+}
+
+// reference setTwistParam (lib/dslash_constants.h) / ndeg_twist_gamma5 (tests/wilson_dslash_reference.cpp:411-440):
+// direct a = 2 kappa mu, b = -2 kappa epsilon; inverse a = -2 kappa mu, b = +2 kappa epsilon, d = 1 / (1 + a^2 - b^2); dagger flips a
+void DiracTwistedMass::ndegCoefficients(QudaTwistGamma5Type twistType, double &a, double &b, double &d) const {
+  ndegTwistCoefficients(kappa, mu, epsilon, twistType == QUDA_TWIST_GAMMA5_INVERSE, dagger == QUDA_DAG_YES, a, b, d);
+}
+void DiracTwistedMass::ndegTwist(ColorSpinorField &out, const ColorSpinorField &in, QudaTwistGamma5Type twistType, const ColorSpinorField *x, double k) const {
+  double a, b, d;
+  ndegCoefficients(twistType, a, b, d);
+  applyNdegTwist(out, in, a, b, d, x, k);
+  flops += (96ll + (x ? 48ll : 0ll)) * in.Volume();
+}
+// the fused doublet stencil: out = A^-1 D in [x + k A^-1 D in] (inverse twist in the epilogue) or out = k D in + A x (direct twist on x)
+void DiracTwistedMass::ndegFused(ColorSpinorField &out, const ColorSpinorField &in, QudaParity parity, QudaTwistGamma5Type twistType, const ColorSpinorField *x, double k) const {
+  double a, b, d;
+  ndegCoefficients(twistType, a, b, d);
+  DslashParam p;
+  p.ndeg = 1; p.parity = parity; p.dagger = dagger == QUDA_DAG_YES; p.a = a; p.nb = b; p.x = x; p.k = k;
+  if (twistType == QUDA_TWIST_GAMMA5_INVERSE) { p.mode = DSLASH_TWIST_INV; p.b = x ? k * d : d; }
+  else p.mode = DSLASH_TWIST_XPAY;
+  applyDslash(out, in, *gauge, p);
+  flops += (1320ll + 96ll + (x ? 48ll : 0ll)) * in.Volume();
 }
 
 // reference lib/dirac_twisted_mass.cpp:47-79 + setTwistParam lib/dslash_constants.h:544-557
 void DiracTwistedMass::twistedApply(ColorSpinorField &out, const ColorSpinorField &in, QudaTwistGamma5Type twistType) const {
   checkFlavor(out, in);
+  if (doublet(in)) {
+    if (in.SiteSubset() == QUDA_FULL_SITE_SUBSET) { ndegTwist(out.Even(), in.Even(), twistType); ndegTwist(out.Odd(), in.Odd(), twistType); }
+    else ndegTwist(out, in, twistType);
+    return;
+  }
   const double fmu = in.TwistFlavor() * mu;
   double a, b;
   if (twistType == QUDA_TWIST_GAMMA5_DIRECT) { a = 2.0 * kappa * fmu; b = 1.0; }
@@ -199,8 +244,14 @@ void DiracTwistedMass::twistedApply(ColorSpinorField &out, const ColorSpinorFiel
   flops += 48ll * in.Volume();
 }
 void DiracTwistedMass::Twist(ColorSpinorField &out, const ColorSpinorField &in) const { twistedApply(out, in, QUDA_TWIST_GAMMA5_DIRECT); }
-void DiracTwistedMass::localTerm(ColorSpinorField &out, const ColorSpinorField &in) const { Twist(out, in); }  // L = 1 + i a gamma5
-void DiracTwistedMass::localTermParity(ColorSpinorField &out, const ColorSpinorField &in, int) const { Twist(out, in); }
+void DiracTwistedMass::localTerm(ColorSpinorField &out, const ColorSpinorField &in) const {  // L = 1 + i a gamma5
+  if (doublet(in)) errorQuda("localTerm: the multigrid construction is not available for the non-degenerate doublet");
+  Twist(out, in);
+}
+void DiracTwistedMass::localTermParity(ColorSpinorField &out, const ColorSpinorField &in, int) const {
+  if (doublet(in)) errorQuda("localTermParity: the multigrid construction is not available for the non-degenerate doublet");
+  Twist(out, in);
+}
 
 static DslashMode tmMode(QudaTwistDslashType t) {
   switch (t) {
@@ -232,6 +283,18 @@ void DiracTwistedMass::TwistedDslashXpay(ColorSpinorField &out, const ColorSpino
 void DiracTwistedMass::M(ColorSpinorField &out, const ColorSpinorField &in) const {
   checkFullSpinor(out, in);
   checkFlavor(out, in);
+  if (doublet(in)) {   // A in - kappa D in on both parities (reference tm_ndeg_mat): site term first, then the hop with xpay
+    if (ndegFusedSelected()) {
+      ndegFused(out.Odd(), in.Even(), QUDA_ODD_PARITY, QUDA_TWIST_GAMMA5_DIRECT, &in.Odd(), -kappa);
+      ndegFused(out.Even(), in.Odd(), QUDA_EVEN_PARITY, QUDA_TWIST_GAMMA5_DIRECT, &in.Even(), -kappa);
+      return;
+    }
+    ColorSpinorField *t = getTmp(tmp2, own2, in);
+    Twist(*t, in);
+    DiracWilson::DslashXpay(out.Odd(), in.Even(), QUDA_ODD_PARITY, t->Odd(), -kappa);
+    DiracWilson::DslashXpay(out.Even(), in.Odd(), QUDA_EVEN_PARITY, t->Even(), -kappa);
+    return;
+  }
   const double a = 2.0 * kappa * in.TwistFlavor() * mu;
   TwistedDslashXpay(out.Odd(), in.Even(), in.Odd(), QUDA_ODD_PARITY, QUDA_DEG_DSLASH_TWIST_XPAY, a, -kappa);
   TwistedDslashXpay(out.Even(), in.Odd(), in.Even(), QUDA_EVEN_PARITY, QUDA_DEG_DSLASH_TWIST_XPAY, a, -kappa);
@@ -257,6 +320,19 @@ void DiracTwistedMassPC::TwistInv(ColorSpinorField &out, const ColorSpinorField 
 void DiracTwistedMassPC::Dslash(ColorSpinorField &out, const ColorSpinorField &in, const QudaParity parity) const {
   checkParitySpinor(in, out);
   checkFlavor(out, in);
+  if (doublet(in)) {
+    const bool asymmetric = matpcType == QUDA_MATPC_EVEN_EVEN_ASYMMETRIC || matpcType == QUDA_MATPC_ODD_ODD_ASYMMETRIC;
+    if (dagger == QUDA_DAG_NO || asymmetric) {
+      if (ndegFusedSelected()) { ndegFused(out, in, parity, QUDA_TWIST_GAMMA5_INVERSE); return; }
+      DiracWilson::Dslash(out, in, parity);
+      ndegTwist(out, out, QUDA_TWIST_GAMMA5_INVERSE);
+    } else {   // the pre-twist of the neighbour doublet stays a site pass: in the stencil it would cost 24 or 48 lane swaps per hop
+      ColorSpinorField *t = getTmp(tmp3, own3, in);
+      ndegTwist(*t, in, QUDA_TWIST_GAMMA5_INVERSE);
+      DiracWilson::Dslash(out, *t, parity);
+    }
+    return;
+  }
   const double a = -2.0 * kappa * in.TwistFlavor() * mu;
   const double b = 1.0 / (1.0 + a * a);
   const bool asym = matpcType == QUDA_MATPC_EVEN_EVEN_ASYMMETRIC || matpcType == QUDA_MATPC_ODD_ODD_ASYMMETRIC;
@@ -269,6 +345,19 @@ void DiracTwistedMassPC::DslashXpay(ColorSpinorField &out, const ColorSpinorFiel
                                     const double &k) const {
   checkParitySpinor(in, out);
   checkFlavor(out, in);
+  if (doublet(in)) {
+    if (out.V() == x.V()) errorQuda("aliasing pointers");
+    if (dagger == QUDA_DAG_NO) {   // out = x + k A^-1 D in: in the fused stencil's epilogue, or the xpay rides on the site pass
+      if (ndegFusedSelected()) { ndegFused(out, in, parity, QUDA_TWIST_GAMMA5_INVERSE, &x, k); return; }
+      DiracWilson::Dslash(out, in, parity);
+      ndegTwist(out, out, QUDA_TWIST_GAMMA5_INVERSE, &x, k);
+    } else {                       // out = x + k D^dag A^-1^dag in
+      ColorSpinorField *t = getTmp(tmp3, own3, in);
+      ndegTwist(*t, in, QUDA_TWIST_GAMMA5_INVERSE);
+      DiracWilson::DslashXpay(out, *t, parity, x, k);
+    }
+    return;
+  }
   const double a = -2.0 * kappa * in.TwistFlavor() * mu;
   const double b = k / (1.0 + a * a);
   if (dagger == QUDA_DAG_NO) TwistedDslashXpay(out, in, x, parity, QUDA_DEG_DSLASH_TWIST_INV, a, b);
@@ -286,6 +375,14 @@ void DiracTwistedMassPC::M(ColorSpinorField &out, const ColorSpinorField &in) co
   } else if (matpcType == QUDA_MATPC_ODD_ODD) {
     Dslash(*t, in, QUDA_EVEN_PARITY);
     DslashXpay(out, *t, QUDA_ODD_PARITY, in, kappa2);
+  } else if (doublet(in)) {   // A in - kappa^2 D A^-1 D in (every factor daggered under dagger)
+    if (matpcType != QUDA_MATPC_EVEN_EVEN_ASYMMETRIC && matpcType != QUDA_MATPC_ODD_ODD_ASYMMETRIC) errorQuda("Invalid matpcType");
+    const bool even = matpcType == QUDA_MATPC_EVEN_EVEN_ASYMMETRIC;
+    Dslash(*t, in, even ? QUDA_ODD_PARITY : QUDA_EVEN_PARITY);
+    if (ndegFusedSelected()) { ndegFused(out, *t, even ? QUDA_EVEN_PARITY : QUDA_ODD_PARITY, QUDA_TWIST_GAMMA5_DIRECT, &in, kappa2); return; }
+    ColorSpinorField *s = getTmp(tmp3, own3, in);
+    ndegTwist(*s, in, QUDA_TWIST_GAMMA5_DIRECT);
+    DiracWilson::DslashXpay(out, *t, even ? QUDA_EVEN_PARITY : QUDA_ODD_PARITY, *s, kappa2);
   } else {
     const double a = 2.0 * kappa * in.TwistFlavor() * mu;
     if (matpcType == QUDA_MATPC_EVEN_EVEN_ASYMMETRIC) {

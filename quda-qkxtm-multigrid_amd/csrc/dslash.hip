@@ -98,6 +98,7 @@ template <typename real> struct DslashArg {
   int edgeFirst;   // plane-tiled order of a partitioned launch: boundary planes first in every XCD (dslash_kernel)
   PackArg<real> pack;
   unsigned long long *timeline;   // QUDA_AMD_TIMELINE=1: per-block wall_clock64 stamps (measurement aid), else nullptr
+  real nb;   // fused doublet stencil (ndeg_dslash_kernel): the flavour-mixing coefficient b of 1 + i a g5 tau3 + b tau1; a and the scale d travel in a, b
 };
 
 // ---- spin projection / reconstruction in the chiral basis; s = +1 selects projector[2 mu], -1 projector[2 mu + 1]
@@ -601,6 +602,58 @@ __device__ __forceinline__ void dslash_epilogue(real *acc, const DslashArg<real>
   Planar<T, 24>::template store<SAUX>(acc, arg.out, arg.sp_stride, idx, arg.outNorm, idx);
 }
 
+// ---- fused doublet stencil: epilogue ----
+// A wave of ndeg_dslash_kernel is 32 sites x 2 flavours: lane l < 32 holds flavour 1 of a site, lane l + 32 flavour 2 of the same site.
+// The value the partner half-wave holds in the same register, by v_permlane32_swap (CDNA4): swap(v, v) returns {lower half in both
+// halves, upper half in both halves}
+__device__ __forceinline__ float half_swap(float v, bool upper) {
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  return __builtin_bit_cast(float, upper ? r[0] : r[1]);
+}
+__device__ __forceinline__ double half_swap(double v, bool upper) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = (unsigned)u, hi = (unsigned)(u >> 32);
+  const auto rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+  const auto rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+  const unsigned long long w = ((unsigned long long)(upper ? rh[0] : rh[1]) << 32) | (upper ? rl[0] : rl[1]);
+  return __builtin_bit_cast(double, w);
+}
+// acc: the hop sum of this lane's flavour; site: its index in the doublet's planes (f Vh + idx); upper: flavour 2 (a -> -a).
+//   DSLASH_PLAIN      out = acc                                   [xpay: x + k acc]      both flavours of D in one launch
+//   DSLASH_TWIST_INV  out = b (acc + i a g5 acc + nb acc')         [xpay: x + b (...)]    A^-1 D, b = d (times k), acc' the partner's
+//   DSLASH_TWIST_XPAY out = k acc + (x + i a g5 x + nb x')                                k D + A x
+template <typename T, int SAUX, typename real>
+__device__ __forceinline__ void ndeg_epilogue(real *acc, const DslashArg<real> &arg, int site, bool upper) {
+  real xs[24], o[24];
+  if (arg.xpay) Planar<T, 24>::load(xs, arg.x, arg.sp_stride, site, arg.xNorm, site);
+  const real a = upper ? -arg.a : arg.a;
+  if (arg.mode == DSLASH_PLAIN) {
+    if (arg.xpay) {
+#pragma unroll
+      for (int k = 0; k < 24; k++) acc[k] = xs[k] + arg.k * acc[k];
+    }
+  } else if (arg.mode == DSLASH_TWIST_INV) {
+#pragma unroll
+    for (int k = 0; k < 24; k++) o[k] = half_swap(acc[k], upper);
+    twist_inplace(acc, a);
+    if (arg.xpay) {
+#pragma unroll
+      for (int k = 0; k < 24; k++) acc[k] = xs[k] + arg.b * (acc[k] + arg.nb * o[k]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 24; k++) acc[k] = arg.b * (acc[k] + arg.nb * o[k]);
+    }
+  } else {   // DSLASH_TWIST_XPAY
+#pragma unroll
+    for (int k = 0; k < 24; k++) o[k] = half_swap(xs[k], upper);
+    twist_inplace(xs, a);
+#pragma unroll
+    for (int k = 0; k < 24; k++) acc[k] = arg.k * acc[k] + (xs[k] + arg.nb * o[k]);
+  }
+  Planar<T, 24>::template store<SAUX>(acc, arg.out, arg.sp_stride, site, arg.outNorm, site);
+}
+
 // ---- face packing (reference packFaceWilsonKernel / packTwistedFaceWilsonKernel, lib/dslash_pack.cu:272, :610) ----
 // P2P: the send pointers are peer-mapped ghost zones — flag-in-data vectors, system-scope write-through stores (GhostLL)
 // Block `bid` packs the face sites [bid * chunk, (bid + 1) * chunk) of the concatenated (dim, dir) ranges, chunk <= blockDim.
@@ -672,8 +725,10 @@ template <typename T, bool PRETWIST, bool P2P, typename real> __device__ __force
 // grid-decomposed lattice (sites that touch a partitioned boundary are skipped); 2 = exterior pass (boundary site, off-node
 // neighbours from the ghost zone); 3 = single-launch peer-store path: local hops first, then the off-node hops once the
 // neighbours' faces have arrived.
-template <typename T, int R, int VARIANT, int GAUX, int KT, int SAUX, typename real>
-__device__ __forceinline__ void stencil_site(const DslashArg<real> &arg, const int idx) {
+// ND = 1 (fused doublet stencil): the lane works on flavour fo / Vh of site idx — spinor indices are offset by fo inside the doublet's planes,
+// the links are those of idx — and the epilogue mixes the flavours of the two half-waves (ndeg_epilogue)
+template <typename T, int R, int VARIANT, int GAUX, int KT, int SAUX, int ND = 0, typename real>
+__device__ __forceinline__ void stencil_site(const DslashArg<real> &arg, const int idx, const int fo = 0) {
   // checkerboard index -> coordinates (tests/test_util.cpp:419-443)
   const uint32_t za = arg.dXh.div((uint32_t)idx);
   const int xh = idx - (int)za * arg.Xh;
@@ -723,7 +778,7 @@ __device__ __forceinline__ void stencil_site(const DslashArg<real> &arg, const i
   // (aligned with an increasing sweep, so that the reads of one input site by different blocks fall closer together in time)
   // changed nothing at 32^4 or 48^3 x 96 in any precision (gpurun_out/sweep48b.log of round 2).
   constexpr int GH = KT == 2 ? 1 : (KT == 3 ? 2 : 0);
-  const int nb[8] = {n_xp, n_xm, n_yp, n_ym, n_zp, n_zm, n_tp, n_tm};
+  const int nb[8] = {n_xp + fo, n_xm + fo, n_yp + fo, n_ym + fo, n_zp + fo, n_zm + fo, n_tp + fo, n_tm + fo};
   const real sg[8] = {one, one, one, one, one, one, sg_tp, sg_tm};
   const bool of[8] = {o_xp, o_xm, o_yp, o_ym, o_zp, o_zm, o_tp, o_tm};
   const int fc[8] = {f_x, f_x, f_y, f_y, f_z, f_z, f_t, f_t};
@@ -796,31 +851,14 @@ __device__ __forceinline__ void stencil_site(const DslashArg<real> &arg, const i
       if (arg.timeline && (threadIdx.x & 63) == 0) arg.timeline[8192 + (blockIdx.x * 4 + (threadIdx.x >> 6))] = wall_clock64();
     }
   }
-  dslash_epilogue<T, VARIANT, GAUX, SAUX>(acc, arg, idx);
+  if constexpr (ND != 0) ndeg_epilogue<T, SAUX>(acc, arg, idx + fo, fo != 0);
+  else dslash_epilogue<T, VARIANT, GAUX, SAUX>(acc, arg, idx);
 }
 
-template <typename T, int R, int VARIANT, int GAUX, int KT, int SAUX = 0>
-__global__ void __launch_bounds__(256) dslash_kernel(const DslashArg<typename Store<T>::real> arg) {
-  if (KT == 2) {
-    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid >= arg.nboundary) return;
-    stencil_site<T, R, VARIANT, GAUX, 2, SAUX>(arg, arg.blist[tid]);
-    return;
-  }
-  int b = blockIdx.x;
-  if (KT == 3) {
-    // single-launch peer-store path: [pack blocks | every site]; boundary sites do their local hops first, then poll the
-    // ghost words they need and add the off-node hops (stencil_site, KT == 3)
-    if (b < arg.packBlocks) {
-      if (arg.packPrio) __builtin_amdgcn_s_setprio(3);
-      pack_body<T, VARIANT == 1, true>(arg.pack, b, arg.packChunk);
-      return;
-    }
-    b -= arg.packBlocks;
-    // the pack blocks' loads go first: a site wave keeps ~8 us worth of requests queued in its CU, and a pack wave that starts
-    // together with it needs 12 (up to 18) us for its two round trips instead of 4
-    for (int i = 0; i < arg.siteDelay; i++) __builtin_amdgcn_s_sleep(8);
-  }
+// physical block b -> logical block (a run of consecutive checkerboard sites): XCD-aware remap, plane-tiled order, y groups, time-slab
+// interleave (launchDslash sets the fields up for the number of SITES per block, which is blockDim.x in dslash_kernel and half of it
+// in ndeg_dslash_kernel)
+template <typename real> __device__ __forceinline__ int dslash_logical_block(const DslashArg<real> &arg, const int b) {
   // XCD-aware block remap: blocks b, b+8, b+16, ... share an XCD (round-robin dispatch); give each XCD a
   // contiguous range of logical blocks (a slab of time slices) so t/z neighbours hit its own L2.
   const int xcd = b & 7, within = b >> 3;
@@ -870,6 +908,32 @@ __global__ void __launch_bounds__(256) dslash_kernel(const DslashArg<typename St
       lb = (s * arg.ts + tt) * arg.bps + c;
     }
   }
+  return lb;
+}
+
+template <typename T, int R, int VARIANT, int GAUX, int KT, int SAUX = 0>
+__global__ void __launch_bounds__(256) dslash_kernel(const DslashArg<typename Store<T>::real> arg) {
+  if (KT == 2) {
+    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= arg.nboundary) return;
+    stencil_site<T, R, VARIANT, GAUX, 2, SAUX>(arg, arg.blist[tid]);
+    return;
+  }
+  int b = blockIdx.x;
+  if (KT == 3) {
+    // single-launch peer-store path: [pack blocks | every site]; boundary sites do their local hops first, then poll the
+    // ghost words they need and add the off-node hops (stencil_site, KT == 3)
+    if (b < arg.packBlocks) {
+      if (arg.packPrio) __builtin_amdgcn_s_setprio(3);
+      pack_body<T, VARIANT == 1, true>(arg.pack, b, arg.packChunk);
+      return;
+    }
+    b -= arg.packBlocks;
+    // the pack blocks' loads go first: a site wave keeps ~8 us worth of requests queued in its CU, and a pack wave that starts
+    // together with it needs 12 (up to 18) us for its two round trips instead of 4
+    for (int i = 0; i < arg.siteDelay; i++) __builtin_amdgcn_s_sleep(8);
+  }
+  const int lb = dslash_logical_block(arg, b);
   const int idx = lb * blockDim.x + threadIdx.x;
   if (idx >= arg.Vh) return;
   if (KT == 3 && arg.timeline && threadIdx.x == 0) {
@@ -878,6 +942,19 @@ __global__ void __launch_bounds__(256) dslash_kernel(const DslashArg<typename St
   }
   stencil_site<T, R, VARIANT, GAUX, KT, SAUX>(arg, idx);
   if (KT == 3 && arg.timeline && threadIdx.x == 0) arg.timeline[12288 + blockIdx.x] = wall_clock64();
+}
+
+// Fused doublet stencil (unpartitioned launches): one launch computes both flavours of the non-degenerate twisted-mass doublet and
+// requests every link once — the two half-waves of a wave run the hop pipeline of stencil_site on the same 32 sites, one flavour
+// each, so they ask for the same link addresses, and the flavours meet in the epilogue through v_permlane32_swap.  A block of
+// blockDim.x threads is blockDim.x / 2 consecutive sites; in, out and x are parity doublets (planes: flavour 1's Vh sites, then flavour 2's).
+template <typename T, int R, int GAUX, int SAUX>
+__global__ void __launch_bounds__(256) ndeg_dslash_kernel(const DslashArg<typename Store<T>::real> arg) {
+  const int lb = dslash_logical_block(arg, (int)blockIdx.x);
+  const int lane = threadIdx.x & 63;
+  const int idx = lb * (int)(blockDim.x >> 1) + (int)(threadIdx.x >> 6) * 32 + (lane & 31);
+  if (idx >= arg.Vh) return;   // both flavours of a site leave together: a live lane's partner is live
+  stencil_site<T, R, 0, GAUX, 0, SAUX, 1>(arg, idx, (lane >> 5) * arg.Vh);
 }
 
 // ================================================================================================
@@ -1663,6 +1740,86 @@ __global__ void __launch_bounds__(256) site_kernel(const SiteArg<typename Store<
   Planar<T, 24>::store(v, arg.out, arg.sp_stride, idx, arg.outNorm, idx);
 }
 
+// ---- flavour-doublet twist (reference ndeg twistGamma5Cuda, lib/dslash_quda.cu; host tests/wilson_dslash_reference.cpp:411-440) ----
+// t1 = d (in1 + i a g5 in1 + b in2), t2 = d (in2 - i a g5 in2 + b in1) on a parity doublet; out = t or, XPAY, out = x + k t.  One thread per
+// 4-d site holds both flavours (planes: flavour 1's Vh sites, then flavour 2's) and reads them before it writes, so out may be in (or x)
+template <typename real> struct NdegTwistArg {
+  void *out; float *outNorm;
+  const void *in; const float *inNorm;
+  const void *x; const float *xNorm;
+  int sp_stride, Vh;
+  real a, b, d, k;
+};
+
+template <typename T, bool XPAY>
+__global__ void __launch_bounds__(256) ndeg_twist_kernel(const NdegTwistArg<typename Store<T>::real> arg) {
+  using real = typename Store<T>::real;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= arg.Vh) return;
+  real u[24], v[24], o[24];
+  Planar<T, 24>::load(u, arg.in, arg.sp_stride, idx, arg.inNorm, idx);
+  Planar<T, 24>::load(v, arg.in, arg.sp_stride, arg.Vh + idx, arg.inNorm, arg.Vh + idx);
+#pragma unroll
+  for (int f = 0; f < 2; f++) {
+    const real *own = f ? v : u, *other = f ? u : v;
+    const int site = f * arg.Vh + idx;
+#pragma unroll
+    for (int k = 0; k < 24; k++) o[k] = own[k];
+    twist_inplace(o, f ? -arg.a : arg.a);
+#pragma unroll
+    for (int k = 0; k < 24; k++) o[k] = arg.d * (o[k] + arg.b * other[k]);
+    if (XPAY) {
+      real xv[24];
+      Planar<T, 24>::load(xv, arg.x, arg.sp_stride, site, arg.xNorm, site);
+#pragma unroll
+      for (int k = 0; k < 24; k++) o[k] = xv[k] + arg.k * o[k];
+    }
+    Planar<T, 24>::store(o, arg.out, arg.sp_stride, site, arg.outNorm, site);
+  }
+}
+
+template <typename T> static void launchNdegTwist(ColorSpinorField &out, const ColorSpinorField &in, double a, double b, double d, const ColorSpinorField *x, double k) {
+  using real = typename Store<T>::real;
+  NdegTwistArg<real> arg;
+  arg.out = out.V(); arg.outNorm = (float *)out.Norm();
+  arg.in = in.V(); arg.inNorm = (const float *)in.Norm();
+  arg.x = x ? x->V() : nullptr; arg.xNorm = x ? (const float *)x->Norm() : nullptr;
+  arg.sp_stride = in.Stride(); arg.Vh = in.VolumeCB4();
+  arg.a = (real)a; arg.b = (real)b; arg.d = (real)d; arg.k = (real)k;
+  const int bs = 256, nb = (arg.Vh + bs - 1) / bs;
+  if (x) hipLaunchKernelGGL((ndeg_twist_kernel<T, true>), dim3(nb), dim3(bs), 0, computeStream(), arg);
+  else hipLaunchKernelGGL((ndeg_twist_kernel<T, false>), dim3(nb), dim3(bs), 0, computeStream(), arg);
+  HIP_CHECK(hipGetLastError());
+}
+
+void ndegTwistCoefficients(double kappa, double mu, double epsilon, bool inverse, bool dagger, double &a, double &b, double &d) {
+  a = 2.0 * kappa * mu; b = -2.0 * kappa * epsilon; d = 1.0;
+  if (inverse) {
+    a = -a; b = -b;
+    const double det = 1.0 + a * a - b * b;
+    if (det <= 0.0) errorQuda("non-degenerate doublet: 1 + a^2 - b^2 = %g is not positive (kappa %g, mu %g, epsilon %g): the twist has no inverse", det, kappa, mu, epsilon);
+    d = 1.0 / det;
+  }
+  if (dagger) a = -a;
+}
+
+void applyNdegTwist(ColorSpinorField &out, const ColorSpinorField &in, double a, double b, double d, const ColorSpinorField *x, double k) {
+  if (out.Location() != QUDA_CUDA_FIELD_LOCATION || in.Location() != QUDA_CUDA_FIELD_LOCATION) errorQuda("device fields required");
+  if (in.Nflavor() != 2 || out.Nflavor() != 2 || (x && x->Nflavor() != 2)) errorQuda("the doublet twist needs two-flavour fields (got %d, %d flavours)", in.Nflavor(), out.Nflavor());
+  if (in.SiteSubset() != QUDA_PARITY_SITE_SUBSET || out.SiteSubset() != QUDA_PARITY_SITE_SUBSET) errorQuda("parity fields required");
+  if (in.Precision() != out.Precision() || (x && x->Precision() != in.Precision())) errorQuda("precision mismatch");
+  if (in.Nspin() != 4 || in.Ncolor() != 3) errorQuda("the doublet twist needs nSpin=4 nColor=3");
+  if (out.Stride() != in.Stride() || out.VolumeCB() != in.VolumeCB()) errorQuda("doublet twist: output stride %d / volume %d against input %d / %d", out.Stride(), out.VolumeCB(), in.Stride(), in.VolumeCB());
+  if (x && (x->Stride() != in.Stride() || x->VolumeCB() != in.VolumeCB() || x->SiteSubset() != QUDA_PARITY_SITE_SUBSET)) errorQuda("doublet twist: the xpay field does not match the input");
+  if (g_acctOn) acct("ndeg_twist_kernel", (x ? 72.0 : 48.0) * in.Precision() * in.VolumeCB(), "level 0");
+  switch (in.Precision()) {
+    case QUDA_DOUBLE_PRECISION: launchNdegTwist<double>(out, in, a, b, d, x, k); break;
+    case QUDA_SINGLE_PRECISION: launchNdegTwist<float>(out, in, a, b, d, x, k); break;
+    case QUDA_HALF_PRECISION: launchNdegTwist<short>(out, in, a, b, d, x, k); break;
+    default: errorQuda("bad precision %d", in.Precision());
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // launch-geometry knobs of the stencil (defaults from the environment, once; qudaAmdSetDslashTune changes them at run time so one
 // process can sweep them — tools/dslash_sweep.py)
@@ -1684,6 +1841,7 @@ DslashTune &dslashTune() {
     t.lds_pad = env("QUDA_AMD_DSLASH_LDS", 0);
     t.ygroups = env("QUDA_AMD_DSLASH_YGROUPS", -1);
     t.edge_first = env("QUDA_AMD_EDGE_FIRST", 1);
+    t.ndeg_fused = env("QUDA_AMD_NDEG_FUSED", -1);
     { const char *e = getenv("QUDA_AMD_HALO_FORMAT"); t.halo_format = !e ? -1 : ((!strcmp(e, "atom") || !strcmp(e, "atom16") || !strcmp(e, "sector") || !strcmp(e, "1")) ? 1 : 0); }
   }
   return t;
@@ -1697,6 +1855,11 @@ int haloWireFormat() {
   const int f = dslashTune().halo_format;
   if (f >= 0) return f ? 1 : 0;
   return (commGrid().size > 1 && !p2pDeviceShared()) ? 1 : 0;
+}
+// the fused doublet stencil has no halo path: a partitioned lattice takes the composed operators whatever was asked for
+bool ndegFusedSelected() {
+  for (int d = 0; d < 4; d++) if (commGrid().partitioned(d)) return false;
+  return dslashTune().ndeg_fused != 0;
 }
 void setDslashTune(const char *key, int value) {
   DslashTune &t = dslashTune();
@@ -1717,6 +1880,7 @@ void setDslashTune(const char *key, int value) {
   else if (k == "pack_prio") t.pack_prio = value;
   else if (k == "edge_first") t.edge_first = value;
   else if (k == "halo_format") t.halo_format = value;
+  else if (k == "ndeg_fused") t.ndeg_fused = value;
   else errorQuda("unknown stencil tuning key '%s'", key);
 }
 
@@ -1940,7 +2104,7 @@ static void launchDslash(ColorSpinorField &out, const ColorSpinorField &in, cons
   arg.dXh = g.dXh; arg.dY = g.dY; arg.dZ = g.dZ;
   arg.parity = p.parity; arg.mode = p.mode; arg.xpay = p.x ? 1 : 0;
   arg.sfwd = p.dagger ? -1 : 1;
-  arg.a = (real)p.a; arg.b = (real)p.b; arg.k = (real)p.k;
+  arg.a = (real)p.a; arg.b = (real)p.b; arg.k = (real)p.k; arg.nb = (real)p.nb;
   // recon-12: the reconstructed row of boundary t-links carries the (folded) boundary sign; recon-8: u0 of the reconstruction is that sign
   const bool first_t = commGrid().coords[3] == 0, last_t = commGrid().coords[3] == commGrid().dims[3] - 1;
   arg.tsign_fwd = (R != 18 && U.t_boundary == QUDA_ANTI_PERIODIC_T && last_t) ? -1 : 1;
@@ -1956,7 +2120,7 @@ static void launchDslash(ColorSpinorField &out, const ColorSpinorField &in, cons
       if (g_sweepTune->link_aux >= 0) tune.link_aux = g_sweepTune->link_aux;
       if (g_sweepTune->store_aux >= 0) tune.store_aux = g_sweepTune->store_aux;
       if (g_sweepTune->edge_first >= 0) tune.edge_first = g_sweepTune->edge_first;
-    } else if (tuningEnabled() || tuneCacheSize() > 0) {
+    } else if (!p.ndeg && (tuningEnabled() || tuneCacheSize() > 0)) {
       const TuneKey key = dslashTuneKey(g, (int)sizeof(T), R, VARIANT, p, pmask);
       const TuneParam *tp = tuneLookup(key);
       if (!tp && tuningEnabled() && !(pmask && haloBuffers(g, in.Precision()).verified == 0)) {   // (a partitioned launch is first verified, then tuned)
@@ -1973,11 +2137,13 @@ static void launchDslash(ColorSpinorField &out, const ColorSpinorField &in, cons
   }
   // block size: the largest of 256 / 192 / 128 / 64 threads that cuts an (x, y) plane into whole blocks (needed by the
   // plane-tiled order), 256 otherwise; QUDA_AMD_DSLASH_BLOCK overrides
+  // (fused doublet stencil: bs counts the SITES of a block, its threads are twice that — 128 / 96 / 64 / 32 sites)
   const int plane = g.Xh * g.X[1];
-  int bs = tune.block;
-  if (bs < 64 || bs > 256 || bs % 64) {
-    bs = 256;
-    for (int c : {256, 192, 128, 64}) if (plane % c == 0) { bs = c; break; }
+  const int fl = p.ndeg ? 2 : 1;
+  int bs = tune.block / fl;
+  if (bs * fl < 64 || bs * fl > 256 || (bs * fl) % 64) {
+    bs = 256 / fl;
+    for (int c : {256, 192, 128, 64}) if (plane % (c / fl) == 0) { bs = c / fl; break; }
   }
   const int nb = (g.Vh + bs - 1) / bs;
   setLastKernel(VARIANT == 2 ? "dslash_kernel (clover)" : "dslash_kernel", g.X, (int)sizeof(T), R, bs);
@@ -2036,6 +2202,30 @@ static void launchDslash(ColorSpinorField &out, const ColorSpinorField &in, cons
   int mask = 0;
   for (int d = 0; d < 4; d++) if (commGrid().partitioned(d)) mask |= 1 << d;
   hipStream_t cs = computeStream();
+  if (p.ndeg) {
+    if constexpr (VARIANT == 0) {
+      if (mask != 0) errorQuda("the fused doublet stencil has no halo path (partition mask %d): use the composed doublet operators", mask);
+      setLastKernel("ndeg_dslash_kernel", g.X, (int)sizeof(T), R, bs * fl);
+      const bool ntStore = tune.store_aux >= 0 ? tune.store_aux == 2 : 2 * g.Vh >= (1 << 18);   // as below, for the sites of both flavours
+      const size_t lds = tune.lds_pad > 0 ? (size_t)tune.lds_pad : 0;
+      if constexpr (sizeof(T) == 2 && GAUX == 0) {   // 16-bit links: nt once one application's working set exceeds the Infinity Cache, as below
+        const size_t working = (size_t)g.Vh * (size_t)ndegDslashBytesPerSite(in.Precision(), R, p.x != nullptr);
+        const bool ntLinks = tune.link_aux >= 0 ? tune.link_aux == 2 : working > ((size_t)256 << 20);
+        if (ntLinks) {
+          if (ntStore) hipLaunchKernelGGL((ndeg_dslash_kernel<T, R, 2, 2>), dim3(nb), dim3(bs * fl), lds, cs, arg);
+          else hipLaunchKernelGGL((ndeg_dslash_kernel<T, R, 2, 0>), dim3(nb), dim3(bs * fl), lds, cs, arg);
+          HIP_CHECK(hipGetLastError());
+          return;
+        }
+      }
+      if (ntStore) hipLaunchKernelGGL((ndeg_dslash_kernel<T, R, GAUX, 2>), dim3(nb), dim3(bs * fl), lds, cs, arg);
+      else hipLaunchKernelGGL((ndeg_dslash_kernel<T, R, GAUX, 0>), dim3(nb), dim3(bs * fl), lds, cs, arg);
+      HIP_CHECK(hipGetLastError());
+      return;
+    } else {
+      errorQuda("fused doublet stencil: plain, twist-inverse and twist-xpay epilogues only (mode %d)", (int)p.mode);
+    }
+  }
   if (mask == 0) {
     const size_t lds = tune.lds_pad > 0 ? (size_t)tune.lds_pad : 0;   // measurement aid: dynamic LDS only to cap the blocks per CU
     // output stores: nt from 2^18 checkerboard sites up (measured +1...+5 % at 32^4 and 48^3 x 96 in every precision and action,
@@ -2270,14 +2460,20 @@ void applyDslash(ColorSpinorField &out, const ColorSpinorField &in, const GaugeF
   if (in.SiteSubset() != QUDA_PARITY_SITE_SUBSET || out.SiteSubset() != QUDA_PARITY_SITE_SUBSET) errorQuda("parity fields required");
   if (in.Precision() != out.Precision() || in.Precision() != U.precision) errorQuda("precision mismatch: spinor %d/%d gauge %d", in.Precision(), out.Precision(), U.precision);
   if (p.x && p.x->Precision() != in.Precision()) errorQuda("xpay precision mismatch");
-  if (in.VolumeCB() != U.geom.Vh || out.VolumeCB() != U.geom.Vh) errorQuda("volume mismatch: spinor %d gauge %d", in.VolumeCB(), U.geom.Vh);
+  if (in.VolumeCB4() != U.geom.Vh || out.VolumeCB4() != U.geom.Vh) errorQuda("volume mismatch: spinor %d gauge %d", in.VolumeCB4(), U.geom.Vh);
+  const int nfl = p.ndeg ? 2 : 1;   // the fused doublet stencil works on whole doublets, everything else on one flavour (Flavor() views of a doublet)
+  if (in.Nflavor() != nfl || out.Nflavor() != nfl || (p.x && p.x->Nflavor() != nfl)) errorQuda("stencil on %d flavour(s): fields of %d / %d flavours", nfl, in.Nflavor(), out.Nflavor());
+  if (p.ndeg && (p.mode != DSLASH_PLAIN && p.mode != DSLASH_TWIST_INV && p.mode != DSLASH_TWIST_XPAY)) errorQuda("fused doublet stencil: plain, twist-inverse and twist-xpay epilogues only (mode %d)", (int)p.mode);
+  if (p.ndeg && p.mode == DSLASH_TWIST_XPAY && !p.x) errorQuda("fused doublet stencil: the twist-xpay epilogue needs x");
+  if (in.Stride() != out.Stride() || (p.x && p.x->Stride() != in.Stride())) errorQuda("stencil: the fields' strides differ (%d, %d)", in.Stride(), out.Stride());
   if (in.V() == out.V()) errorQuda("in and out must not alias");
   if (in.Nspin() != 4 || in.Ncolor() != 3) errorQuda("fine-grid dslash needs nSpin=4 nColor=3");
   if (p.clover && p.clover->precision != in.Precision()) errorQuda("clover precision mismatch");
   if (g_acctOn) {   // one dslash_kernel launch on an unpartitioned lattice (the case the profile tool measures)
     char tag[48];
     snprintf(tag, sizeof(tag), "level 0 prec %d mode %d%s", (int)in.Precision(), (int)p.mode, p.x ? " xpay" : "");
-    acct("dslash_kernel", (double)dslashBytesPerSite(in.Precision(), (int)U.reconstruct, p.mode, p.x != nullptr) * in.VolumeCB(), tag);
+    if (p.ndeg) acct("ndeg_dslash_kernel", (double)ndegDslashBytesPerSite(in.Precision(), (int)U.reconstruct, p.x != nullptr) * in.VolumeCB4(), tag);
+    else acct("dslash_kernel", (double)dslashBytesPerSite(in.Precision(), (int)U.reconstruct, p.mode, p.x != nullptr) * in.VolumeCB(), tag);
   }
   switch (in.Precision()) {
     case QUDA_DOUBLE_PRECISION: dispatchRecon<double>(out, in, U, p); break;
@@ -2639,6 +2835,14 @@ long long dslashFlopsPerSite(DslashMode mode, bool xpay) {
     case DSLASH_CLOVER_TWIST_INV: case DSLASH_CLOVER_TWIST_XPAY: f += 552 + (xpay ? 48 : 0); break;  // lib/dslash_twisted_clover.cu:213-230
   }
   return f;
+}
+
+// one fused doublet application per checkerboard site of the 4-d lattice: the 8 links once, in and out (and x) for both flavours
+long long ndegDslashBytesPerSite(QudaPrecision prec, int recon, bool xpay) {
+  const long long P = prec;
+  long long b = 8LL * recon * P + 2 * (24 * P + 24 * P + (xpay ? 24 * P : 0));
+  if (prec == QUDA_HALF_PRECISION) b += 2 * 4 * (2 + (xpay ? 1 : 0));
+  return b;
 }
 
 long long dslashBytesPerSite(QudaPrecision prec, int recon, DslashMode mode, bool xpay) {

@@ -27,6 +27,12 @@ ColorSpinorParam::ColorSpinorParam(void *V, const QudaInvertParam &inv, const in
   precision = inv.cpu_prec;
   pad = 0;
   twistFlavor = inv.twist_flavor;
+  // the doublet: [flavour 1][flavour 2] per parity, the reference's fifth dimension.  Only the twisted-mass operator has one: elsewhere
+  // (Wilson, where twist_flavor means nothing) the value does not make a two-flavour field
+  if (inv.twist_flavor == QUDA_TWIST_NONDEG_DOUBLET) {
+    if (inv.dslash_type == QUDA_TWISTED_MASS_DSLASH) setFlavors(2);
+    else twistFlavor = QUDA_TWIST_NO;
+  }
   siteOrder = QUDA_EVEN_ODD_SITE_ORDER;
   if (inv.dirac_order == QUDA_DIRAC_ORDER) fieldOrder = QUDA_SPACE_SPIN_COLOR_FIELD_ORDER;
   else if (inv.dirac_order == QUDA_QDP_DIRAC_ORDER) fieldOrder = QUDA_SPACE_COLOR_SPIN_FIELD_ORDER;
@@ -53,8 +59,11 @@ static int gaugePadSites() {
 ColorSpinorField::ColorSpinorField(const ColorSpinorParam &p)
     : location(p.location), nColor(p.nColor), nSpin(p.nSpin), nDim(p.nDim), pad(p.pad), precision(p.precision),
       siteSubset(p.siteSubset), siteOrder(p.siteOrder), fieldOrder(p.fieldOrder), gammaBasis(p.gammaBasis),
-      twistFlavor(p.twistFlavor), v_(nullptr), norm_(nullptr), owns(false), even_(nullptr), odd_(nullptr) {
-  volume = 1;
+      twistFlavor(p.twistFlavor), v_(nullptr), norm_(nullptr), owns(false), even_(nullptr), odd_(nullptr), flavor_{nullptr, nullptr} {
+  nFlavor = p.flavors();
+  nDim = nFlavor == 2 ? 5 : 4;
+  if ((nFlavor == 2) != (twistFlavor == QUDA_TWIST_NONDEG_DOUBLET)) errorQuda("twist flavour %d on a field of %d flavour(s): the non-degenerate doublet is a two-flavour field", twistFlavor, nFlavor);
+  volume = nFlavor;
   for (int d = 0; d < 4; d++) { x[d] = p.x[d]; volume *= p.x[d]; }
   if (volume <= 0) errorQuda("empty field: x = %d %d %d %d", x[0], x[1], x[2], x[3]);
   const int nsub = siteSubset == QUDA_FULL_SITE_SUBSET ? 2 : 1;
@@ -96,6 +105,7 @@ ColorSpinorParam ColorSpinorField::param() const {
   ColorSpinorParam p;
   p.location = location; p.nColor = nColor; p.nSpin = nSpin; p.nDim = nDim;
   for (int d = 0; d < 4; d++) p.x[d] = x[d];
+  p.setFlavors(nFlavor);
   p.precision = precision; p.pad = pad; p.planePad = false; p.twistFlavor = twistFlavor; p.siteSubset = siteSubset; p.siteOrder = siteOrder;
   p.fieldOrder = fieldOrder; p.gammaBasis = gammaBasis; p.create = QUDA_NULL_FIELD_CREATE;
   return p;
@@ -108,6 +118,8 @@ ColorSpinorField::ColorSpinorField(const ColorSpinorField &src) : ColorSpinorFie
 ColorSpinorField::~ColorSpinorField() {
   delete even_;
   delete odd_;
+  delete flavor_[0];
+  delete flavor_[1];
   if (owns) {
     if (location == QUDA_CUDA_FIELD_LOCATION) {
       poolDeviceFree(v_, bytes);
@@ -141,6 +153,31 @@ void ColorSpinorField::createViews() {
 }
 ColorSpinorField &ColorSpinorField::Even() { if (!even_) createViews(); return *even_; }
 ColorSpinorField &ColorSpinorField::Odd() { if (!odd_) createViews(); return *odd_; }
+
+ColorSpinorField &ColorSpinorField::Flavor(int f) {
+  if (nFlavor != 2 || f < 0 || f > 1) errorQuda("Flavor(%d) of a field of %d flavour(s)", f, nFlavor);
+  if (siteSubset != QUDA_PARITY_SITE_SUBSET || location != QUDA_CUDA_FIELD_LOCATION || nSpin != 4) errorQuda("Flavor() needs a device parity doublet");
+  if (!flavor_[f]) {
+    const int Vh = VolumeCB4();
+    ColorSpinorParam p = param();
+    p.setFlavors(1);
+    p.twistFlavor = f == 0 ? QUDA_TWIST_PLUS : QUDA_TWIST_MINUS;
+    p.pad = stride - Vh;   // the planes of the view are the doublet's
+    p.create = QUDA_REFERENCE_FIELD_CREATE;
+    const size_t entry = 16;   // one plane entry of a site: double2, float4 or eight int16 (device_io.h)
+    p.v = (char *)v_ + (size_t)f * Vh * entry;
+    p.norm = norm_ ? (char *)norm_ + (size_t)f * Vh * sizeof(float) : nullptr;
+    flavor_[f] = new ColorSpinorField(p);
+  }
+  return *flavor_[f];
+}
+
+void ColorSpinorField::changeTwist(QudaTwistFlavorType f) {
+  if ((f == QUDA_TWIST_NONDEG_DOUBLET) != (nFlavor == 2)) errorQuda("changeTwist(%d) on a field of %d flavour(s): the non-degenerate doublet is fixed when the field is created", f, nFlavor);
+  twistFlavor = f;
+  if (even_) even_->twistFlavor = f;
+  if (odd_) odd_->twistFlavor = f;
+}
 
 ColorSpinorField &ColorSpinorField::operator=(const ColorSpinorField &src) {
   if (&src != this) copyColorSpinor(*this, src);
@@ -360,7 +397,7 @@ static void copyParity(ColorSpinorField &dst, const ColorSpinorField &src) {
 void copyColorSpinor(ColorSpinorField &dst, const ColorSpinorField &src) {
   if (dst.nSpin != src.nSpin || dst.nColor != src.nColor) errorQuda("spin/colour mismatch %d,%d vs %d,%d", dst.nSpin, dst.nColor, src.nSpin, src.nColor);
   if (dst.SiteSubset() != src.SiteSubset()) errorQuda("site subset mismatch");
-  if (dst.VolumeCB() != src.VolumeCB()) errorQuda("volume mismatch %d vs %d", dst.VolumeCB(), src.VolumeCB());
+  if (dst.VolumeCB() != src.VolumeCB() || dst.Nflavor() != src.Nflavor()) errorQuda("volume mismatch %d (%d flavours) vs %d (%d)", dst.VolumeCB(), dst.Nflavor(), src.VolumeCB(), src.Nflavor());
   if (src.SiteSubset() == QUDA_FULL_SITE_SUBSET) {
     copyParity(dst.Even(), src.Even());
     copyParity(dst.Odd(), src.Odd());

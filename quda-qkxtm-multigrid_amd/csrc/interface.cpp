@@ -53,11 +53,18 @@ void setDiracParam(DiracParam &dp, QudaInvertParam *inv, const bool pc) {
     case QUDA_WILSON_DSLASH: dp.type = pc ? QUDA_WILSONPC_DIRAC : QUDA_WILSON_DIRAC; break;
     case QUDA_TWISTED_MASS_DSLASH:
       dp.type = pc ? QUDA_TWISTED_MASSPC_DIRAC : QUDA_TWISTED_MASS_DIRAC;
-      if (inv->twist_flavor != QUDA_TWIST_MINUS && inv->twist_flavor != QUDA_TWIST_PLUS)
-        errorQuda("twist_flavor %d: only the degenerate +-1 flavours are on this library's path", inv->twist_flavor);
+      if (inv->twist_flavor != QUDA_TWIST_MINUS && inv->twist_flavor != QUDA_TWIST_PLUS && inv->twist_flavor != QUDA_TWIST_NONDEG_DOUBLET)
+        errorQuda("twist_flavor %d: the degenerate +-1 flavours and the non-degenerate doublet are on this library's path", inv->twist_flavor);
+      if (inv->twist_flavor == QUDA_TWIST_NONDEG_DOUBLET) {
+        if (!(inv->epsilon == inv->epsilon)) errorQuda("non-degenerate doublet: parameter epsilon undefined");
+        if (inv->inv_type_precondition == QUDA_MG_INVERTER) errorQuda("non-degenerate doublet: a multigrid preconditioner is not available for it");
+        double a, b, d;
+        ndegTwistCoefficients(inv->kappa, inv->mu, inv->epsilon, true, false, a, b, d);   // stops here if the twist has no inverse
+      }
       break;
     case QUDA_TWISTED_CLOVER_DSLASH:
       dp.type = pc ? QUDA_TWISTED_CLOVERPC_DIRAC : QUDA_TWISTED_CLOVER_DIRAC;
+      if (inv->twist_flavor == QUDA_TWIST_NONDEG_DOUBLET) errorQuda("twisted clover has no non-degenerate doublet operator (twist_flavor %d)", inv->twist_flavor);
       if (inv->twist_flavor != QUDA_TWIST_MINUS && inv->twist_flavor != QUDA_TWIST_PLUS) errorQuda("twist_flavor %d not supported", inv->twist_flavor);
       break;
     default: errorQuda("Unsupported dslash_type %d (Wilson, twisted-mass and twisted-clover are implemented)", inv->dslash_type);
@@ -70,7 +77,7 @@ void setDiracParam(DiracParam &dp, QudaInvertParam *inv, const bool pc) {
   dp.mass = inv->mass;
   dp.m5 = inv->m5;
   dp.mu = inv->mu;
-  dp.epsilon = 0.0;
+  dp.epsilon = inv->twist_flavor == QUDA_TWIST_NONDEG_DOUBLET ? inv->epsilon : 0.0;
   for (int i = 0; i < 4; i++) dp.commDim[i] = 1;
 }
 void setDiracSloppyParam(DiracParam &dp, QudaInvertParam *inv, const bool pc) {
@@ -88,6 +95,14 @@ static void checkResident(const QudaInvertParam *inv) {
   if (!g_initialized) errorQuda("QUDA not initialized");
   if (!gaugePrecise) errorQuda("Gauge field not allocated");
   if (!cloverPrecise && inv->dslash_type == QUDA_TWISTED_CLOVER_DSLASH) errorQuda("Clover field not allocated");
+  if (inv->dslash_type == QUDA_TWISTED_CLOVER_DSLASH && inv->twist_flavor == QUDA_TWIST_NONDEG_DOUBLET)
+    errorQuda("twisted clover has no non-degenerate doublet operator (twist_flavor %d)", inv->twist_flavor);
+}
+
+// the twist flavour the fields of a C ABI call carry: only the twisted-mass operator has a doublet, so a QUDA_TWIST_NONDEG_DOUBLET left in the
+// parameters of a Wilson call (where twist_flavor means nothing) does not make two-flavour fields
+QudaTwistFlavorType fieldTwistFlavor(const QudaInvertParam &inv) {
+  return inv.twist_flavor == QUDA_TWIST_NONDEG_DOUBLET && inv.dslash_type != QUDA_TWISTED_MASS_DSLASH ? QUDA_TWIST_NO : inv.twist_flavor;
 }
 
 ColorSpinorParam deviceSpinorParam(QudaPrecision prec, QudaSiteSubset subset, QudaTwistFlavorType flavor) {
@@ -98,6 +113,7 @@ ColorSpinorParam deviceSpinorParam(QudaPrecision prec, QudaSiteSubset subset, Qu
   p.siteSubset = subset;
   p.precision = prec;
   p.twistFlavor = flavor;
+  if (flavor == QUDA_TWIST_NONDEG_DOUBLET) p.setFlavors(2);
   p.create = QUDA_NULL_FIELD_CREATE;
   return p;
 }
@@ -422,7 +438,7 @@ void dslashQuda(void *h_out, void *h_in, QudaInvertParam *inv, QudaParity parity
   if (inv->tune == QUDA_TUNE_YES || inv->tune == QUDA_TUNE_NO) setTuning(inv->tune);   // reference dslashQuda: setTuning(inv_param->tune)
   ColorSpinorParam cpuParam(h_in, *inv, g_geom.X, true);
   ColorSpinorField in_h(cpuParam);
-  ColorSpinorParam dp = deviceSpinorParam(inv->cuda_prec, QUDA_PARITY_SITE_SUBSET, inv->twist_flavor);
+  ColorSpinorParam dp = deviceSpinorParam(inv->cuda_prec, QUDA_PARITY_SITE_SUBSET, fieldTwistFlavor(*inv));
   ColorSpinorField in(dp), out(dp);
   in = in_h;
   meetRanksBeforeOperator();
@@ -461,7 +477,7 @@ static void applyMat(void *h_out, void *h_in, QudaInvertParam *inv, bool dagmat)
   const bool pc = inv->solution_type == QUDA_MATPC_SOLUTION || inv->solution_type == QUDA_MATPCDAG_MATPC_SOLUTION;
   ColorSpinorParam cpuParam(h_in, *inv, g_geom.X, pc);
   ColorSpinorField in_h(cpuParam);
-  ColorSpinorParam dp = deviceSpinorParam(inv->cuda_prec, pc ? QUDA_PARITY_SITE_SUBSET : QUDA_FULL_SITE_SUBSET, inv->twist_flavor);
+  ColorSpinorParam dp = deviceSpinorParam(inv->cuda_prec, pc ? QUDA_PARITY_SITE_SUBSET : QUDA_FULL_SITE_SUBSET, fieldTwistFlavor(*inv));
   ColorSpinorField in(dp), out(dp);
   in = in_h;
   meetRanksBeforeOperator();
@@ -486,7 +502,7 @@ void cloverQuda(void *h_out, void *h_in, QudaInvertParam *inv, QudaParity *parit
   if (!cloverPrecise) errorQuda("Clover field not allocated");
   ColorSpinorParam cpuParam(h_in, *inv, g_geom.X, true);
   ColorSpinorField in_h(cpuParam);
-  ColorSpinorParam dp = deviceSpinorParam(inv->cuda_prec, QUDA_PARITY_SITE_SUBSET, inv->twist_flavor);
+  ColorSpinorParam dp = deviceSpinorParam(inv->cuda_prec, QUDA_PARITY_SITE_SUBSET, fieldTwistFlavor(*inv));
   ColorSpinorField in(dp), out(dp);
   in = in_h;
   applySite(out, in, SITE_CLOVER, 0.0, 1.0, cloverPrecise, (int)*parity, inverse != 0);
@@ -522,6 +538,17 @@ void qudaAmdSpinorSave(const void *f, void *h_dst, const QudaInvertParam *inv) {
 }
 void qudaAmdSpinorCopy(void *dst, const void *src) { copyColorSpinor(*(ColorSpinorField *)dst, *(const ColorSpinorField *)src); }
 void qudaAmdSpinorSetTwist(void *f, QudaTwistFlavorType flavor) { ((ColorSpinorField *)f)->changeTwist(flavor); }
+// the flavour mixing of the non-degenerate doublet on resident parity (or full) doublets, out may be in:
+// direct 1 + i a g5 tau3 + b tau1 with a = 2 kappa mu, b = -2 kappa epsilon, or its inverse; dagger flips a
+void qudaAmdNdegTwist(void *out, const void *in, double kappa, double mu, double epsilon, int dagger, int inverse) {
+  ColorSpinorField &o = *(ColorSpinorField *)out;
+  const ColorSpinorField &i = *(const ColorSpinorField *)in;
+  double a, b, d;
+  ndegTwistCoefficients(kappa, mu, epsilon, inverse != 0, dagger != 0, a, b, d);
+  if (i.SiteSubset() != o.SiteSubset()) errorQuda("site subset mismatch");
+  if (i.SiteSubset() == QUDA_FULL_SITE_SUBSET) { applyNdegTwist(o.Even(), i.Even(), a, b, d); applyNdegTwist(o.Odd(), i.Odd(), a, b, d); }
+  else applyNdegTwist(o, i, a, b, d);
+}
 
 void *qudaAmdDiracCreate(QudaInvertParam *inv, int pc, int which) {
   checkResident(inv);

@@ -159,6 +159,7 @@ void gaussianSmear(ColorSpinorField &v, const GaugeField &U, double alpha, int n
 
 static void checkCalcParam(const QudaInvertParam *param, const char *fname) {
   // reference :6041-6054
+  if (param->twist_flavor == QUDA_TWIST_NONDEG_DOUBLET) errorQuda("%s: the QKXTM drivers are not available for the non-degenerate doublet", fname);
   if (param->solve_type != QUDA_DIRECT_PC_SOLVE) errorQuda("%s: This function works only with Direct solve and even odd preconditioning", fname);
   if (param->inv_type != QUDA_GCR_INVERTER) errorQuda("%s: This function works only with GCR method", fname);
   if (param->gamma_basis != QUDA_UKQCD_GAMMA_BASIS) errorQuda("%s: This function works only with ukqcd gamma basis", fname);
@@ -471,6 +472,7 @@ static void loopSolves(QudaInvertParam *param, const qudaQKXTM_loopInfo &loopInf
                        Deflation *defl = nullptr, const std::vector<int> &steps = std::vector<int>()) {
   if (!gaugePrecise) errorQuda("%s: Gauge field not allocated", fname);
   if (!cloverPrecise && param->dslash_type == QUDA_TWISTED_CLOVER_DSLASH) errorQuda("%s: Clover field not allocated", fname);
+  if (param->twist_flavor == QUDA_TWIST_NONDEG_DOUBLET) errorQuda("%s: the QKXTM drivers are not available for the non-degenerate doublet", fname);
   if (param->solve_type != QUDA_DIRECT_PC_SOLVE) errorQuda("%s: This function works only with Direct solve and even odd preconditioning", fname);
   if (param->gamma_basis != QUDA_UKQCD_GAMMA_BASIS) errorQuda("%s: This function works only with ukqcd gamma basis", fname);
   if (param->dirac_order != QUDA_DIRAC_ORDER) errorQuda("%s: This function works only with colors inside the spins", fname);

@@ -95,7 +95,7 @@ void invertQuda(void *hp_x, void *hp_b, QudaInvertParam *param) {
   ColorSpinorField h_b(cpuParam);
   cpuParam.v = hp_x;
   ColorSpinorField h_x(cpuParam);
-  ColorSpinorParam cp = deviceSpinorParam(param->cuda_prec, pc_solution ? QUDA_PARITY_SITE_SUBSET : QUDA_FULL_SITE_SUBSET, param->twist_flavor);
+  ColorSpinorParam cp = deviceSpinorParam(param->cuda_prec, pc_solution ? QUDA_PARITY_SITE_SUBSET : QUDA_FULL_SITE_SUBSET, fieldTwistFlavor(*param));
   cp.create = QUDA_ZERO_FIELD_CREATE;
   ColorSpinorField *b = new ColorSpinorField(cp), *x = new ColorSpinorField(cp);
   *b = h_b;
@@ -179,7 +179,7 @@ void invertMultiShiftQuda(void **hp_x, void *hp_b, QudaInvertParam *param) {
   const LatticeGeom &geom = residentGeom();
   ColorSpinorParam cpuParam(hp_b, *param, geom.X, pc_solution);
   ColorSpinorField h_b(cpuParam);
-  ColorSpinorParam cp = deviceSpinorParam(param->cuda_prec, pc_solution ? QUDA_PARITY_SITE_SUBSET : QUDA_FULL_SITE_SUBSET, param->twist_flavor);
+  ColorSpinorParam cp = deviceSpinorParam(param->cuda_prec, pc_solution ? QUDA_PARITY_SITE_SUBSET : QUDA_FULL_SITE_SUBSET, fieldTwistFlavor(*param));
   cp.create = QUDA_ZERO_FIELD_CREATE;
   ColorSpinorField *b = new ColorSpinorField(cp);
   std::vector<ColorSpinorField *> x(n);
@@ -236,7 +236,11 @@ void invertMultiShiftQuda(void **hp_x, void *hp_b, QudaInvertParam *param) {
   delete d; delete dSloppy; delete dPre;
 }
 
-void *newMultigridQuda(QudaMultigridParam *mg_param) { return new multigrid_solver(*mg_param); }
+void *newMultigridQuda(QudaMultigridParam *mg_param) {
+  if (mg_param && mg_param->invert_param && mg_param->invert_param->twist_flavor == QUDA_TWIST_NONDEG_DOUBLET)
+    errorQuda("newMultigridQuda: multigrid is not available for the non-degenerate doublet");
+  return new multigrid_solver(*mg_param);
+}
 void destroyMultigridQuda(void *mg) { delete static_cast<multigrid_solver *>(mg); }
 
 // reference MG::verify (lib/multigrid.cpp:372-486): worst relative deviations of the three identities over all levels
@@ -250,7 +254,7 @@ void qudaAmdMultigridCycle(void *mg_instance, void *h_x, void *h_b, QudaInvertPa
   ColorSpinorField hb(cpuParam);
   cpuParam.v = h_x;
   ColorSpinorField hx(cpuParam);
-  ColorSpinorParam cp = deviceSpinorParam(QUDA_SINGLE_PRECISION, QUDA_FULL_SITE_SUBSET, param->twist_flavor);
+  ColorSpinorParam cp = deviceSpinorParam(QUDA_SINGLE_PRECISION, QUDA_FULL_SITE_SUBSET, fieldTwistFlavor(*param));
   cp.create = QUDA_ZERO_FIELD_CREATE;
   ColorSpinorField b(cp), x(cp);
   b = hb;
