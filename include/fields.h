@@ -192,6 +192,12 @@ class CloverField {
 // gauge tools on the device (fields.hip): APE smearing of the spatial links (a new fp64 field), the plaquette averages, and the
 // forward links back in host QDP order
 GaugeField *apeSmear(const GaugeField &U, unsigned nSteps, double alpha);
+// stout smearing of the first ndir directions (3: spatial links from spatial staples, 4: all links, all six planes); a new fp64 field
+GaugeField *stoutSmear(const GaugeField &U, unsigned nSteps, double rho, int ndir);
+// global topological charge from the clover-leaf field strength; h_density (may be NULL): this rank's q(x), even sites then odd
+double topologicalCharge(const GaugeField &U, double *h_density);
+// exp(i q[k]) of n traceless Hermitian 3x3 matrices (18 reals each) through the device function of the stout kernel (test hook)
+void su3ExpIQ(int n, const double *h_q, double *h_out);
 void plaquette(const GaugeField &U, double plq[3]);
 void saveGaugeQDP(const GaugeField &U, void *const h_gauge[4], QudaPrecision cpu_prec);
 

@@ -174,6 +174,8 @@ void freeGaugeQuda(void);                                  /* ref quda.h:591 */
 void saveGaugeQuda(void *h_gauge, QudaGaugeParam *param);  /* ref quda.h:598; lib/interface_quda.cpp:694: resident links back in host QDP order */
 void plaqQuda(double plaq[3]);                             /* ref quda.h:964; lib/interface_quda.cpp:5510: total, spatial, temporal plaquette of the resident links */
 void performAPEnStep(unsigned int nSteps, double alpha);   /* ref quda.h:971; lib/interface_quda.cpp:5565: APE-smear the resident spatial links into the library's smeared field */
+void performSTOUTnStep(unsigned int nSteps, double rho);   /* ref quda.h:978; lib/interface_quda.cpp:5640: stout-smear the resident spatial links into the library's smeared field */
+double qChargeCuda(void);                                  /* ref quda.h:983; lib/interface_quda.cpp:5940: topological charge of the smeared field if one is resident, else of the resident links */
 void loadCloverQuda(void *h_clover, void *h_clovinv, QudaInvertParam *inv_param); /* ref quda.h:607; interface_quda.cpp:730 */
 void freeCloverQuda(void);                                 /* ref quda.h:613 */
 

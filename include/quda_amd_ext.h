@@ -189,6 +189,20 @@ typedef struct QudaAmdSourceParam_s {
  * the QKXTM lexicographic order gauge_APE uses (lexicographic = 1).  The two functions below also accept gauge_APE = NULL and
  * then smear with that resident field — what the drivers' read-smeared-configuration step supplies otherwise. */
 void qudaAmdSaveSmearedGauge(void **h_gauge, int lexicographic);
+/* Stout smearing (Morningstar and Peardon, hep-lat/0311018) of the resident links into the library's smeared field, which replaces
+ * an earlier one.  smear_time = 0 is performSTOUTnStep: the spatial links from the staples of the three spatial planes, time links
+ * copied.  smear_time = 1 smears all four directions with the staples of all six planes - what a measurement of the topological
+ * charge wants.  fp64 arithmetic whatever the precision of the resident links. */
+void qudaAmdStoutSmear(unsigned int nSteps, double rho, int smear_time);
+/* Topological charge Q = sum_x q(x), q(x) = [Re tr(F10 F32) + Re tr(F30 F21) - Re tr(F20 F31)] / (4 pi^2) with the clover-leaf
+ * F_mu_nu = (Q_mu_nu - Q_mu_nu^dag)/8.  which = -1: the smeared field if one is resident, else the resident links (qChargeCuda);
+ * 0: the resident links; 1: the smeared field (an error if there is none).  h_density (may be NULL) receives q(x) of the calling
+ * rank's local lattice, V doubles: even sites then odd (lexicographic = 0) or lexicographic, x fastest (1).  Returns the global Q,
+ * summed in a fixed order: two calls on the same field return the same bits. */
+double qudaAmdQCharge(double *h_density, int lexicographic, int which);
+/* Test hook: out[k] = exp(i q[k]) for n traceless Hermitian 3x3 matrices, 18 doubles each (row-major, re/im), evaluated on the
+ * device by the function the stout kernel calls (Cayley-Hamilton form). */
+void qudaAmdSu3ExpIQ(int n, const double *q, double *out);
 /* h_out = smear^nsmear(h_in) (QKXTM_Vector_Kepler::gaussianSmearing, lib/qudaQKXTM_Vector_Kepler.cpp:386-421); the lattice is
  * that of the resident gauge field */
 void qudaAmdGaussianSmear(void *h_out, const void *h_in, void **gauge_APE, int nsmear, double alpha);

@@ -108,7 +108,7 @@ class QudaMultigridParam(C.Structure):
 # every extern "C" symbol include/quda.h and include/quda_amd_ext.h declare
 QUDA_H_SYMBOLS = ["setVerbosityQuda", "initCommsGridQuda", "initQudaDevice", "initQudaMemory", "initQuda", "endQuda",
                   "newQudaGaugeParam", "newQudaInvertParam", "newQudaMultigridParam", "printQudaGaugeParam", "printQudaInvertParam",
-                  "printQudaMultigridParam", "loadGaugeQuda", "freeGaugeQuda", "loadCloverQuda", "freeCloverQuda", "invertQuda", "invertMultiSrcQuda", "invertMultiShiftQuda",
+                  "printQudaMultigridParam", "loadGaugeQuda", "freeGaugeQuda", "performSTOUTnStep", "qChargeCuda", "loadCloverQuda", "freeCloverQuda", "invertQuda", "invertMultiSrcQuda", "invertMultiShiftQuda",
                   "newMultigridQuda", "destroyMultigridQuda", "dslashQuda", "cloverQuda", "MatQuda", "MatDagMatQuda", "openMagma",
                   "closeMagma"]
 EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLoad", "qudaAmdSpinorSave", "qudaAmdSpinorCopy",
@@ -126,7 +126,7 @@ EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLo
                  "qudaAmdDeflationExactLoop", "qudaAmdHostSymmetricEig", "qudaAmdRotateBasis", "qudaAmdBlockDot", "qudaAmdBlockAxpy", "qudaAmdLastEigenvalues",
                  "qudaAmdBlasAxpyCGNorm", "qudaAmdBlasAxpyZpbx", "qudaAmdBlasTripleCGReduction", "qudaAmdBlasAxpyReDot", "qudaAmdBlasMultiShiftUpdate",
                  "qudaAmdBlasMultiShiftChunk", "qudaAmdDiracMdagMShift", "qudaAmdTimeMdagM", "qudaAmdTimeCGBlas", "qudaAmdTimeMultiShift",
-                 "qudaAmdNdegTwist"]
+                 "qudaAmdNdegTwist", "qudaAmdStoutSmear", "qudaAmdQCharge", "qudaAmdSu3ExpIQ"]
 
 _lib = None
 
@@ -281,6 +281,16 @@ def lib():
         L.qudaAmdWriteLimeGauge.argtypes = [C.POINTER(_p), C.c_char_p, C.POINTER(QudaGaugeParam), C.c_char_p]
         L.plaqQuda.argtypes = [C.POINTER(_d)]
         L.performAPEnStep.argtypes = [C.c_uint, _d]
+        L.performSTOUTnStep.argtypes = [C.c_uint, _d]
+        L.performSTOUTnStep.restype = None
+        L.qChargeCuda.argtypes = []
+        L.qChargeCuda.restype = _d
+        L.qudaAmdStoutSmear.argtypes = [C.c_uint, _d, _i]
+        L.qudaAmdStoutSmear.restype = None
+        L.qudaAmdQCharge.argtypes = [_p, _i, _i]
+        L.qudaAmdQCharge.restype = _d
+        L.qudaAmdSu3ExpIQ.argtypes = [_i, _p, _p]
+        L.qudaAmdSu3ExpIQ.restype = None
         L.saveGaugeQuda.argtypes = [_p, C.POINTER(QudaGaugeParam)]
         L.qudaAmdSaveSmearedGauge.argtypes = [C.POINTER(_p), _i]
         L.qudaAmdGaussianSmear.argtypes = [_p, _p, C.POINTER(_p), _i, _d]
@@ -556,6 +566,39 @@ def plaquette():
 
 def perform_ape(n_steps, alpha):
     lib().performAPEnStep(int(n_steps), float(alpha))
+
+
+def perform_stout(n_steps, rho):
+    """performSTOUTnStep: stout-smear the resident spatial links into the library's smeared field (save_smeared_gauge reads it)"""
+    lib().performSTOUTnStep(int(n_steps), float(rho))
+
+
+def stout_smear(n_steps, rho, smear_time=False):
+    """qudaAmdStoutSmear: as perform_stout; smear_time=True smears all four directions with the staples of all six planes"""
+    lib().qudaAmdStoutSmear(int(n_steps), float(rho), int(bool(smear_time)))
+
+
+def q_charge(density=False, lexicographic=False, which=-1):
+    """qChargeCuda / qudaAmdQCharge: the topological charge of the smeared field if one is resident, else of the resident links
+    (which=-1), of the resident links (0) or of the smeared field (1).  density=True: returns (Q, q) with q(x) of the local lattice,
+    even sites then odd or lexicographic"""
+    if not density:
+        if which == -1:
+            return float(lib().qChargeCuda())
+        return float(lib().qudaAmdQCharge(None, 0, int(which)))
+    q = np.zeros(2 * gauge_raw_info(0)["Vh"])   # the smeared field has the lattice of the resident links
+    Q = lib().qudaAmdQCharge(_vp(q), int(bool(lexicographic)), int(which))
+    return float(Q), q
+
+
+def su3_exp_iq(q):
+    """qudaAmdSu3ExpIQ: exp(iq) of traceless Hermitian matrices q[..., 3, 3] (complex) through the stout kernel's device function"""
+    q = np.asarray(q, dtype=np.complex128)
+    flat = np.ascontiguousarray(np.stack([q.real, q.imag], axis=-1).reshape(-1, 18))
+    out = np.zeros_like(flat)
+    lib().qudaAmdSu3ExpIQ(int(flat.shape[0]), _vp(flat), _vp(out))
+    out = out.reshape(q.shape + (2,))
+    return out[..., 0] + 1j * out[..., 1]
 
 
 def save_gauge(gp):

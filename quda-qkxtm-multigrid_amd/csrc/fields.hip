@@ -968,6 +968,29 @@ __global__ void cl_pack_kernel(double *packed, MatField b1_0, MatField b1_1, Mat
 
 void applyShift(double *out, const double *in, const LatticeGeom &g, int stride, int parity, int dir);  // dslash.hip
 
+// out(x) = in(x + dhat(dir)) of a matrix field, both parities (dir = 2 mu: forward, 2 mu + 1: backward)
+static void shiftField(MatField out, MatField in, const LatticeGeom &geom, int dir) {
+  for (int par = 0; par < 2; par++) applyShift(out.par(par), in.par(1 - par), geom, geom.Vh, par, dir);
+}
+// the four clover leaves of the mu-nu plane by transport: on return W[4] = P, W[1] = T_mu P, W[2] = T_nu P, W[3] = T_nu T_mu P
+// (W[0] is scratch).  Shared by the decomposed clover construction and the field strength of the topological charge.
+template <typename T, int R> static void cloverLeaves(MatField W[5], const LatticeGeom &geom, const GaugeView &g, int mu, int nu) {
+  const int Vh = geom.Vh, bs = 128, nb = (2 * Vh + bs - 1) / bs;
+  hipStream_t s = computeStream();
+  hipLaunchKernelGGL((cl_extract_kernel<T, R>), dim3(nb), dim3(bs), 0, s, W[0], g, nu, Vh);
+  hipLaunchKernelGGL((cl_extract_kernel<T, R>), dim3(nb), dim3(bs), 0, s, W[1], g, mu, Vh);
+  shiftField(W[2], W[0], geom, 2 * mu);   // U_nu(x + mu)
+  shiftField(W[3], W[1], geom, 2 * nu);   // U_mu(x + nu)
+  hipLaunchKernelGGL((cl_plaq_kernel<T, R>), dim3(nb), dim3(bs), 0, s, W[4], W[2], W[3], g, mu, nu, Vh);            // P
+  shiftField(W[0], W[4], geom, 2 * mu + 1);
+  hipLaunchKernelGGL((cl_transport_kernel<T, R>), dim3(nb), dim3(bs), 0, s, W[1], W[0], g, mu, Vh);                  // A = T_mu P
+  shiftField(W[0], W[4], geom, 2 * nu + 1);
+  hipLaunchKernelGGL((cl_transport_kernel<T, R>), dim3(nb), dim3(bs), 0, s, W[2], W[0], g, nu, Vh);                  // B = T_nu P
+  shiftField(W[0], W[1], geom, 2 * nu + 1);
+  hipLaunchKernelGGL((cl_transport_kernel<T, R>), dim3(nb), dim3(bs), 0, s, W[3], W[0], g, nu, Vh);                  // C = T_nu T_mu P
+  HIP_CHECK(hipGetLastError());
+}
+
 template <typename T, int R> static void cloverFromGaugeDecomposed(double *stage, const GaugeField &U, const GaugeView &g, double coeff) {
   const LatticeGeom &geom = U.geom;
   const int Vh = geom.Vh, bs = 128, nb = (2 * Vh + bs - 1) / bs;
@@ -979,23 +1002,10 @@ template <typename T, int R> static void cloverFromGaugeDecomposed(double *stage
   b1[0] = {pool + 5 * fieldDoubles, Vh}; b1[1] = {pool + 6 * fieldDoubles, Vh};
   b2[0] = {pool + 7 * fieldDoubles, Vh}; b2[1] = {pool + 8 * fieldDoubles, Vh};
   hipStream_t s = computeStream();
-  auto shift = [&](MatField out, MatField in, int dir) {   // out(x) = in(x + dhat(dir)), both parities
-    for (int par = 0; par < 2; par++) applyShift(out.par(par), in.par(1 - par), geom, Vh, par, dir);
-  };
   bool first = true;
   for (int mu = 1; mu < 4; mu++)
     for (int nu = 0; nu < mu; nu++) {
-      hipLaunchKernelGGL((cl_extract_kernel<T, R>), dim3(nb), dim3(bs), 0, s, W[0], g, nu, Vh);
-      hipLaunchKernelGGL((cl_extract_kernel<T, R>), dim3(nb), dim3(bs), 0, s, W[1], g, mu, Vh);
-      shift(W[2], W[0], 2 * mu);   // U_nu(x + mu)
-      shift(W[3], W[1], 2 * nu);   // U_mu(x + nu)
-      hipLaunchKernelGGL((cl_plaq_kernel<T, R>), dim3(nb), dim3(bs), 0, s, W[4], W[2], W[3], g, mu, nu, Vh);            // P
-      shift(W[0], W[4], 2 * mu + 1);
-      hipLaunchKernelGGL((cl_transport_kernel<T, R>), dim3(nb), dim3(bs), 0, s, W[1], W[0], g, mu, Vh);                  // A = T_mu P
-      shift(W[0], W[4], 2 * nu + 1);
-      hipLaunchKernelGGL((cl_transport_kernel<T, R>), dim3(nb), dim3(bs), 0, s, W[2], W[0], g, nu, Vh);                  // B = T_nu P
-      shift(W[0], W[1], 2 * nu + 1);
-      hipLaunchKernelGGL((cl_transport_kernel<T, R>), dim3(nb), dim3(bs), 0, s, W[3], W[0], g, nu, Vh);                  // C = T_nu T_mu P
+      cloverLeaves<T, R>(W, geom, g, mu, nu);
       hipLaunchKernelGGL(cl_accum_kernel, dim3(nb), dim3(bs), 0, s, b1[0], b1[1], b2[0], b2[1], W[4], W[1], W[2], W[3], mu * (mu - 1) / 2 + nu, coeff,
                          first ? 1 : 0, Vh);
       HIP_CHECK(hipGetLastError());
@@ -1297,43 +1307,49 @@ static void extractForwardLinks(MatField F, const GaugeField &U, int mu) {
   HIP_CHECK(hipGetLastError());
 }
 
-GaugeField *apeSmear(const GaugeField &U, unsigned nSteps, double alpha) {
+// S = sum over the smeared directions mu != nu (mu < ndir) of the upper and the lower staple of (x, nu); F: the forward links of
+// the previous step, W1, W2, T1, T2: scratch.  Shared by the APE and the stout step.
+static void stapleSum(MatField S, const MatField *F, int nu, int ndir, MatField W1, MatField W2, MatField T1, MatField T2, const LatticeGeom &geom) {
+  const int Vh = geom.Vh, bs = 128, nb = (2 * Vh + bs - 1) / bs;
+  hipStream_t s = computeStream();
+  HIP_CHECK(hipMemsetAsync(S.p, 0, (size_t)2 * 24 * Vh * sizeof(double), s));
+  for (int mu = 0; mu < ndir; mu++) {
+    if (mu == nu) continue;
+    shiftField(W1, F[nu], geom, 2 * mu);   // U_nu(x + mu)
+    shiftField(W2, F[mu], geom, 2 * nu);   // U_mu(x + nu)
+    hipLaunchKernelGGL(mf_mul_kernel, dim3(nb), dim3(bs), 0, s, T1, F[mu], W1, 0, 0, 0, Vh);   // U_mu(x) U_nu(x+mu)
+    hipLaunchKernelGGL(mf_mul_kernel, dim3(nb), dim3(bs), 0, s, S, T1, W2, 0, 1, 1, Vh);       // S += ... U_mu(x+nu)^dag
+    hipLaunchKernelGGL(mf_mul_kernel, dim3(nb), dim3(bs), 0, s, T1, F[mu], F[nu], 1, 0, 0, Vh); // U_mu(x)^dag U_nu(x)
+    hipLaunchKernelGGL(mf_mul_kernel, dim3(nb), dim3(bs), 0, s, T2, T1, W2, 0, 0, 0, Vh);      // ... U_mu(x+nu)
+    shiftField(T1, T2, geom, 2 * mu + 1);  // carried from x - mu to x
+    hipLaunchKernelGGL(mf_add_kernel, dim3(nb), dim3(bs), 0, s, S, T1, Vh);
+    HIP_CHECK(hipGetLastError());
+  }
+}
+
+// nSteps smearing steps of the directions 0 .. ndir-1 on a copy of U; update(Unew, S, Uold) launches the link update of one
+// direction from its staple sum.  The result is a new fp64 field without reconstruction.
+template <typename Update> static GaugeField *smearLinks(const GaugeField &U, unsigned nSteps, int ndir, Update update) {
   const LatticeGeom &geom = U.geom;
   const int Vh = geom.Vh, bs = 128, nb = (2 * Vh + bs - 1) / bs;
   const size_t fieldDoubles = (size_t)2 * 24 * Vh;
   double *pool = nullptr;
   HIP_CHECK(qaMalloc((void **)&pool, 13 * fieldDoubles * sizeof(double)));
-  MatField F[4], G[3], S, W1, W2, T1, T2;
+  MatField F[4], G[4], S, W1, W2, T1, T2;
   for (int i = 0; i < 4; i++) F[i] = {pool + i * fieldDoubles, Vh};
-  for (int i = 0; i < 3; i++) G[i] = {pool + (4 + i) * fieldDoubles, Vh};
-  S = {pool + 7 * fieldDoubles, Vh}; W1 = {pool + 8 * fieldDoubles, Vh}; W2 = {pool + 9 * fieldDoubles, Vh};
-  T1 = {pool + 10 * fieldDoubles, Vh}; T2 = {pool + 11 * fieldDoubles, Vh};
+  for (int i = 0; i < 4; i++) G[i] = {pool + (4 + i) * fieldDoubles, Vh};
+  S = {pool + 8 * fieldDoubles, Vh}; W1 = {pool + 9 * fieldDoubles, Vh}; W2 = {pool + 10 * fieldDoubles, Vh};
+  T1 = {pool + 11 * fieldDoubles, Vh}; T2 = {pool + 12 * fieldDoubles, Vh};
   hipStream_t s = computeStream();
-  auto shift = [&](MatField out, MatField in, int dir) {   // out(x) = in(x + dhat(dir)), both parities
-    for (int par = 0; par < 2; par++) applyShift(out.par(par), in.par(1 - par), geom, Vh, par, dir);
-  };
   for (int mu = 0; mu < 4; mu++) extractForwardLinks(F[mu], U, mu);
-  const double tol = 1e-15;   // DOUBLE_TOL, lib/gauge_ape.cu:9
   for (unsigned step = 0; step < nSteps; step++) {
-    for (int nu = 0; nu < 3; nu++) {
-      HIP_CHECK(hipMemsetAsync(S.p, 0, fieldDoubles * sizeof(double), s));
-      for (int mu = 0; mu < 3; mu++) {
-        if (mu == nu) continue;
-        shift(W1, F[nu], 2 * mu);   // U_nu(x + mu)
-        shift(W2, F[mu], 2 * nu);   // U_mu(x + nu)
-        hipLaunchKernelGGL(mf_mul_kernel, dim3(nb), dim3(bs), 0, s, T1, F[mu], W1, 0, 0, 0, Vh);   // U_mu(x) U_nu(x+mu)
-        hipLaunchKernelGGL(mf_mul_kernel, dim3(nb), dim3(bs), 0, s, S, T1, W2, 0, 1, 1, Vh);       // S += ... U_mu(x+nu)^dag
-        hipLaunchKernelGGL(mf_mul_kernel, dim3(nb), dim3(bs), 0, s, T1, F[mu], F[nu], 1, 0, 0, Vh); // U_mu(x)^dag U_nu(x)
-        hipLaunchKernelGGL(mf_mul_kernel, dim3(nb), dim3(bs), 0, s, T2, T1, W2, 0, 0, 0, Vh);      // ... U_mu(x+nu)
-        shift(T1, T2, 2 * mu + 1);  // carried from x - mu to x
-        hipLaunchKernelGGL(mf_add_kernel, dim3(nb), dim3(bs), 0, s, S, T1, Vh);
-        HIP_CHECK(hipGetLastError());
-      }
-      hipLaunchKernelGGL(ape_project_kernel, dim3(nb), dim3(bs), 0, s, G[nu], S, F[nu], alpha, tol, Vh);
+    for (int nu = 0; nu < ndir; nu++) {
+      stapleSum(S, F, nu, ndir, W1, W2, T1, T2, geom);
+      update(G[nu], S, F[nu]);
       HIP_CHECK(hipGetLastError());
     }
     // every direction of a step is smeared from the links of the previous step (the reference reads a copy, :5621-5627)
-    for (int nu = 0; nu < 3; nu++) std::swap(F[nu], G[nu]);
+    for (int nu = 0; nu < ndir; nu++) std::swap(F[nu], G[nu]);
   }
   // back through the loader: it builds the bidirectional layout and fetches the backward links that live on the neighbour ranks
   std::vector<std::vector<double>> host(4, std::vector<double>((size_t)geom.V * 18));
@@ -1352,6 +1368,135 @@ GaugeField *apeSmear(const GaugeField &U, unsigned nSteps, double alpha) {
   return out;
 }
 
+GaugeField *apeSmear(const GaugeField &U, unsigned nSteps, double alpha) {
+  const int Vh = U.geom.Vh, bs = 128, nb = (2 * Vh + bs - 1) / bs;
+  const double tol = 1e-15;   // DOUBLE_TOL, lib/gauge_ape.cu:9
+  return smearLinks(U, nSteps, 3, [&](MatField Unew, MatField S, MatField Uold) {
+    hipLaunchKernelGGL(ape_project_kernel, dim3(nb), dim3(bs), 0, computeStream(), Unew, S, Uold, alpha, tol, Vh);
+  });
+}
+
+// ================================================================================================================
+// Stout smearing (Morningstar and Peardon, hep-lat/0311018; reference lib/gauge_stout.cu, include/quda_matrix.h exponentiate_iQ,
+// lib/interface_quda.cpp:5640-5713).  Staples as for APE; per link
+//   Omega = rho S U^dag,   Q = (i/2) [(Omega^dag - Omega) - tr(Omega^dag - Omega)/3],   U' = exp(iQ) U.
+// U^dag stands where the reference inverts U: the same matrix for unitary links, without the division.
+//
+// exp(iQ) = f0 + f1 Q + f2 Q^2 of a traceless Hermitian Q by the Cayley-Hamilton form (eqs. 14-34 of the paper):
+//   c0 = tr Q^3 / 3 = det Q,  c1 = tr Q^2 / 2,  c0max = 2 (c1/3)^(3/2),  theta = acos(c0 / c0max),
+//   u = sqrt(c1/3) cos(theta/3),  w = sqrt(c1) sin(theta/3),  f_j = h_j / (9 u^2 - w^2).
+// c0 < 0 goes through f_j(-c0) = (-1)^j conj f_j(c0), so theta/3 <= pi/6 and 9 u^2 - w^2 = c1 (3 cos^2 - sin^2) >= 2 c1 > 0.
+// The only other divisions are by c0max and by w in xi0 = sin(w)/w: xi0 takes its even Taylor polynomial for |w| <= 0.05, and
+// below c1 = 1e-60 (c0max would underflow towards 0; c1 = 0 means Q = 0) the result is 1 + iQ, exact to c1/2: the unit matrix
+// for Q = 0.  Rounding can push c0 / c0max past 1 at the degenerate point; it is clamped.
+__device__ __forceinline__ void su3_exp_iq(M3 &E, const M3 &Q) {
+  double c1 = 0;
+#pragma unroll
+  for (int k = 0; k < 9; k++) c1 += Q.re[k] * Q.re[k] + Q.im[k] * Q.im[k];   // tr Q^2 = sum |Q_ij|^2 for Hermitian Q
+  c1 *= 0.5;
+  if (c1 < 1e-60) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) { E.re[k] = -Q.im[k]; E.im[k] = Q.re[k]; }
+    E.re[0] += 1.0; E.re[4] += 1.0; E.re[8] += 1.0;
+    return;
+  }
+  M3 Q2;
+  m3_mul(Q2, Q, Q);
+  double c0 = 0;   // tr(Q Q^2) = sum_ij Q_ij (Q^2)_ji, real
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) c0 += Q.re[3 * i + j] * Q2.re[3 * j + i] - Q.im[3 * i + j] * Q2.im[3 * j + i];
+  c0 *= 1.0 / 3.0;
+  const bool neg = c0 < 0;
+  c0 = fabs(c0);
+  const double c13 = c1 * (1.0 / 3.0), c0max = 2.0 * c13 * sqrt(c13);   // > 0: c1 >= 1e-60
+  const double theta3 = acos(fmin(c0 / c0max, 1.0)) * (1.0 / 3.0);
+  const double u = sqrt(c13) * cos(theta3), w = sqrt(c1) * sin(theta3);
+  const double u2 = u * u, w2 = w * w, cw = cos(w);
+  const double xi0 = fabs(w) <= 0.05 ? 1.0 - w2 * (1.0 / 6.0) * (1.0 - w2 * (1.0 / 20.0) * (1.0 - w2 * (1.0 / 42.0))) : sin(w) / w;
+  double s2u, c2u, su, cu;
+  sincos(2.0 * u, &s2u, &c2u);
+  sincos(u, &su, &cu);
+  // h_j = a_j e^{2iu} + e^{-iu} (b_j + i d_j)
+  const double b0 = 8.0 * u2 * cw, d0 = 2.0 * u * (3.0 * u2 + w2) * xi0;
+  const double b1 = -2.0 * u * cw, d1 = (3.0 * u2 - w2) * xi0;
+  const double b2 = -cw, d2 = -3.0 * u * xi0;
+  const double a0 = u2 - w2, a1 = 2.0 * u, inv = 1.0 / (9.0 * u2 - w2);
+  double fr[3], fi[3];
+  fr[0] = (a0 * c2u + cu * b0 + su * d0) * inv; fi[0] = (a0 * s2u + cu * d0 - su * b0) * inv;
+  fr[1] = (a1 * c2u + cu * b1 + su * d1) * inv; fi[1] = (a1 * s2u + cu * d1 - su * b1) * inv;
+  fr[2] = (c2u + cu * b2 + su * d2) * inv;      fi[2] = (s2u + cu * d2 - su * b2) * inv;
+  if (neg) { fi[0] = -fi[0]; fr[1] = -fr[1]; fi[2] = -fi[2]; }
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+    E.re[k] = fr[1] * Q.re[k] - fi[1] * Q.im[k] + fr[2] * Q2.re[k] - fi[2] * Q2.im[k];
+    E.im[k] = fr[1] * Q.im[k] + fi[1] * Q.re[k] + fr[2] * Q2.im[k] + fi[2] * Q2.re[k];
+  }
+  E.re[0] += fr[0]; E.re[4] += fr[0]; E.re[8] += fr[0];
+  E.im[0] += fi[0]; E.im[4] += fi[0]; E.im[8] += fi[0];
+}
+
+// one thread per site and parity: Unew = exp(iQ) U with Q from the staple sum S
+__global__ void __launch_bounds__(128) stout_update_kernel(MatField Unew, MatField S, MatField U, double rho, int Vh) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= 2 * Vh) return;
+  const int par = gid >= Vh, idx = gid - par * Vh;
+  M3 s, u, t, om, q;
+  mf_load(s, S, par, idx); mf_load(u, U, par, idx);
+  m3_dag(t, u);
+  m3_mul(om, s, t);   // Omega / rho
+  // Q_ij = (i/2) (conj(Om_ji) - Om_ij) - delta_ij (i/6) tr(Om^dag - Om);  tr(Om^dag - Om) = -2i sum_k Im Om_kk.  rho multiplies the
+  // differences, not Omega: rho a - rho b contracts to fma(rho, a, -(rho b)), which is not 0 for a = b and would leave Q
+  // Hermitian only to rounding (and the unit gauge not a fixed point)
+  const double h = 0.5 * rho, tr3 = rho * ((om.im[0] + om.im[4] + om.im[8]) * (1.0 / 3.0));
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      q.re[3 * i + j] = h * (om.im[3 * j + i] + om.im[3 * i + j]);
+      q.im[3 * i + j] = h * (om.re[3 * j + i] - om.re[3 * i + j]);
+    }
+  q.re[0] -= tr3; q.re[4] -= tr3; q.re[8] -= tr3;
+  su3_exp_iq(t, q);
+  m3_mul(s, t, u);
+  mf_store(s, Unew, par, idx);
+}
+
+// test hook (qudaAmdSu3ExpIQ): out[n] = exp(i q[n]) through the function the stout kernel calls; 18 reals per matrix, row-major re/im
+__global__ void __launch_bounds__(128) su3_exp_iq_kernel(double *out, const double *in, int n) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= n) return;
+  M3 q, e;
+#pragma unroll
+  for (int k = 0; k < 9; k++) { q.re[k] = in[(size_t)gid * 18 + 2 * k]; q.im[k] = in[(size_t)gid * 18 + 2 * k + 1]; }
+  su3_exp_iq(e, q);
+#pragma unroll
+  for (int k = 0; k < 9; k++) { out[(size_t)gid * 18 + 2 * k] = e.re[k]; out[(size_t)gid * 18 + 2 * k + 1] = e.im[k]; }
+}
+
+void su3ExpIQ(int n, const double *h_q, double *h_out) {
+  if (n <= 0) return;
+  const size_t bytes = (size_t)n * 18 * sizeof(double);
+  double *d = nullptr;
+  HIP_CHECK(qaMalloc((void **)&d, 2 * bytes));
+  hipStream_t s = computeStream();
+  HIP_CHECK(hipMemcpyAsync(d, h_q, bytes, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(su3_exp_iq_kernel, dim3((n + 127) / 128), dim3(128), 0, s, d + (size_t)n * 18, d, n);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(h_out, d + (size_t)n * 18, bytes, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  HIP_CHECK(hipFree(d));
+}
+
+// ndir = 3: the spatial links from spatial staples (performSTOUTnStep); ndir = 4: all links from the staples of all six planes
+GaugeField *stoutSmear(const GaugeField &U, unsigned nSteps, double rho, int ndir) {
+  if (ndir != 3 && ndir != 4) errorQuda("stoutSmear: %d smeared directions (3 or 4)", ndir);
+  const int Vh = U.geom.Vh, bs = 128, nb = (2 * Vh + bs - 1) / bs;
+  return smearLinks(U, nSteps, ndir, [&](MatField Unew, MatField S, MatField Uold) {
+    hipLaunchKernelGGL(stout_update_kernel, dim3(nb), dim3(bs), 0, computeStream(), Unew, S, Uold, rho, Vh);
+  });
+}
 void saveGaugeQDP(const GaugeField &U, void *const h_gauge[4], QudaPrecision cpu_prec) {
   if (cpu_prec != QUDA_DOUBLE_PRECISION) errorQuda("saving links: fp64 host fields only");
   const LatticeGeom &geom = U.geom;
@@ -1400,6 +1545,114 @@ void plaquette(const GaugeField &U, double plq[3]) {
   comm_allreduce(h, 2);
   const double norm = 9.0 * (double)geom.V * commGrid().size;
   plq[1] = h[0] / norm; plq[2] = h[1] / norm; plq[0] = 0.5 * (plq[1] + plq[2]);
+}
+
+// ================================================================================================================
+// Topological charge from the clover-leaf field strength (reference lib/field_strength_tensor.cu, lib/qcharge_quda.cu,
+// lib/interface_quda.cpp:5940-5991): F_mu_nu = (Q_mu_nu - Q_mu_nu^dag)/8, no trace removed, the leaves by the transport above;
+//   q(x) = [Re tr(F10 F32) + Re tr(F30 F21) - Re tr(F20 F31)] / (4 pi^2),   Q = sum_x q(x).
+__global__ void fmunu_kernel(MatField F, MatField P, MatField A, MatField B, MatField C, int Vh) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= 2 * Vh) return;
+  const int par = gid >= Vh, idx = gid - par * Vh;
+  M3 Q, m;
+  mf_load(Q, P, par, idx);
+  mf_load(m, A, par, idx);
+#pragma unroll
+  for (int k = 0; k < 9; k++) { Q.re[k] += m.re[k]; Q.im[k] += m.im[k]; }
+  mf_load(m, B, par, idx);
+#pragma unroll
+  for (int k = 0; k < 9; k++) { Q.re[k] += m.re[k]; Q.im[k] += m.im[k]; }
+  mf_load(m, C, par, idx);
+#pragma unroll
+  for (int k = 0; k < 9; k++) { Q.re[k] += m.re[k]; Q.im[k] += m.im[k]; }
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      m.re[i * 3 + j] = 0.125 * (Q.re[i * 3 + j] - Q.re[j * 3 + i]);
+      m.im[i * 3 + j] = 0.125 * (Q.im[i * 3 + j] + Q.im[j * 3 + i]);
+    }
+  mf_store(m, F, par, idx);
+}
+__device__ __forceinline__ double re_tr_mul(const M3 &a, const M3 &b) {
+  double r = 0;
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) r += a.re[3 * i + j] * b.re[3 * j + i] - a.im[3 * i + j] * b.im[3 * j + i];
+  return r;
+}
+struct FmunuFields { MatField f[6]; };
+// q(x) for every site (even sites then odd) and one partial sum per block, in a fixed order: lanes by shuffle, the four waves
+// through LDS.  No atomics: the partials are added in block order by the host, so the same field gives the same bits.
+__global__ void __launch_bounds__(256) qcharge_density_kernel(double *q, double *partial, FmunuFields F, int Vh) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  double v = 0;
+  if (gid < 2 * Vh) {
+    const int par = gid >= Vh, idx = gid - par * Vh;
+    M3 a, b;
+    mf_load(a, F.f[0], par, idx); mf_load(b, F.f[5], par, idx);
+    v = re_tr_mul(a, b);
+    mf_load(a, F.f[3], par, idx); mf_load(b, F.f[2], par, idx);
+    v += re_tr_mul(a, b);
+    mf_load(a, F.f[1], par, idx); mf_load(b, F.f[4], par, idx);
+    v -= re_tr_mul(a, b);
+    v *= 1.0 / (4.0 * M_PI * M_PI);
+    q[gid] = v;
+  }
+  __shared__ double lds[4];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+
+template <typename T, int R> static void fieldStrength(MatField F[6], MatField W[5], const GaugeField &U, const GaugeView &g) {
+  const int Vh = U.geom.Vh, bs = 128, nb = (2 * Vh + bs - 1) / bs;
+  for (int mu = 1; mu < 4; mu++)
+    for (int nu = 0; nu < mu; nu++) {
+      cloverLeaves<T, R>(W, U.geom, g, mu, nu);
+      hipLaunchKernelGGL(fmunu_kernel, dim3(nb), dim3(bs), 0, computeStream(), F[mu * (mu - 1) / 2 + nu], W[4], W[1], W[2], W[3], Vh);
+      HIP_CHECK(hipGetLastError());
+    }
+}
+
+// the global charge; h_density (may be NULL) receives this rank's q(x), even sites then odd
+double topologicalCharge(const GaugeField &U, double *h_density) {
+  const LatticeGeom &geom = U.geom;
+  const int Vh = geom.Vh, bs = 256, nb = (2 * Vh + bs - 1) / bs;   // the grid depends on the volume only
+  const size_t fieldDoubles = (size_t)2 * 24 * Vh;
+  double *pool = nullptr;
+  HIP_CHECK(qaMalloc((void **)&pool, (11 * fieldDoubles + (size_t)2 * Vh + nb) * sizeof(double)));
+  MatField W[5];
+  FmunuFields F;
+  for (int i = 0; i < 5; i++) W[i] = {pool + i * fieldDoubles, Vh};
+  for (int i = 0; i < 6; i++) F.f[i] = {pool + (5 + i) * fieldDoubles, Vh};
+  double *d_q = pool + 11 * fieldDoubles, *d_partial = d_q + (size_t)2 * Vh;
+  const GaugeView g = viewOf(U);
+  const bool r12 = U.reconstruct == QUDA_RECONSTRUCT_12, r8 = U.reconstruct == QUDA_RECONSTRUCT_8;
+#define QA_FS(T) { if (r12) fieldStrength<T, 12>(F.f, W, U, g); else if (r8) fieldStrength<T, 8>(F.f, W, U, g); else fieldStrength<T, 18>(F.f, W, U, g); }
+  switch (U.precision) {
+    case QUDA_DOUBLE_PRECISION: QA_FS(double) break;
+    case QUDA_SINGLE_PRECISION: QA_FS(float) break;
+    case QUDA_HALF_PRECISION: QA_FS(short) break;
+    default: errorQuda("bad gauge precision %d", U.precision);
+  }
+#undef QA_FS
+  hipStream_t s = computeStream();
+  hipLaunchKernelGGL(qcharge_density_kernel, dim3(nb), dim3(bs), 0, s, d_q, d_partial, F, Vh);
+  HIP_CHECK(hipGetLastError());
+  std::vector<double> partial(nb);
+  HIP_CHECK(hipMemcpyAsync(partial.data(), d_partial, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (h_density) HIP_CHECK(hipMemcpyAsync(h_density, d_q, (size_t)2 * Vh * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  HIP_CHECK(hipFree(pool));
+  double Q = 0;
+  for (int b = 0; b < nb; b++) Q += partial[b];
+  comm_allreduce(&Q, 1);
+  return Q;
 }
 
 }  // namespace quda

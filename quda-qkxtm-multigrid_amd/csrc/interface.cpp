@@ -358,6 +358,50 @@ void performAPEnStep(unsigned int nSteps, double alpha) {
   }
 }
 
+// reference lib/interface_quda.cpp:5640-5713 (lib/gauge_stout.cu): as performAPEnStep with the stout link update; smear_time = 1
+// also smears the time links and takes the staples of all six planes
+void qudaAmdStoutSmear(unsigned int nSteps, double rho, int smear_time) {
+  if (!g_initialized) errorQuda("QUDA not initialized");
+  if (!gaugePrecise) errorQuda("Gauge field must be loaded");
+  delete gaugeSmeared;
+  gaugeSmeared = nullptr;
+  gaugeSmeared = stoutSmear(*gaugePrecise, nSteps, rho, smear_time ? 4 : 3);
+  if (getVerbosity() >= QUDA_VERBOSE) {
+    double p0[3], p1[3];
+    plaquette(*gaugePrecise, p0); plaquette(*gaugeSmeared, p1);
+    printfQuda("Plaquette after 0 STOUT steps: %le\nPlaquette after %u STOUT steps: %le\n", p0[0], nSteps, p1[0]);
+  }
+}
+void performSTOUTnStep(unsigned int nSteps, double rho) { qudaAmdStoutSmear(nSteps, rho, 0); }
+
+// reference lib/interface_quda.cpp:5940-5991 (lib/field_strength_tensor.cu, lib/qcharge_quda.cu)
+double qudaAmdQCharge(double *h_density, int lexicographic, int which) {
+  if (!g_initialized) errorQuda("QUDA not initialized");
+  if (which < -1 || which > 1) errorQuda("qudaAmdQCharge: which = %d (-1: smeared field if resident, 0: resident links, 1: smeared field)", which);
+  if (which == 1 && !gaugeSmeared) errorQuda("qudaAmdQCharge: no smeared field is resident (performAPEnStep / performSTOUTnStep)");
+  const GaugeField *U = (which == 0 || !gaugeSmeared) ? gaugePrecise : gaugeSmeared;
+  if (!U) errorQuda("Gauge field must be loaded");
+  if (!h_density || !lexicographic) return topologicalCharge(*U, h_density);
+  const LatticeGeom &g = U->geom;
+  std::vector<double> eo((size_t)g.V);
+  const double Q = topologicalCharge(*U, eo.data());
+  for (long iv = 0; iv < g.V; iv++) {
+    long l = iv / g.X[0];
+    const int x = (int)(iv % g.X[0]), y = (int)(l % g.X[1]); l /= g.X[1];
+    const int z = (int)(l % g.X[2]), t = (int)(l / g.X[2]);
+    const int parity = (x + y + z + t) & 1;
+    h_density[iv] = eo[(size_t)parity * g.Vh + iv / 2];
+  }
+  return Q;
+}
+double qChargeCuda(void) { return qudaAmdQCharge(nullptr, 0, -1); }
+
+void qudaAmdSu3ExpIQ(int n, const double *q, double *out) {
+  if (!g_initialized) errorQuda("QUDA not initialized");
+  if (n < 0 || (n > 0 && (!q || !out))) errorQuda("qudaAmdSu3ExpIQ: n = %d, q = %p, out = %p", n, (const void *)q, (void *)out);
+  su3ExpIQ(n, q, out);
+}
+
 void qudaAmdSaveSmearedGauge(void **h_gauge, int lexicographic) {
   if (!gaugeSmeared) errorQuda("qudaAmdSaveSmearedGauge: no smeared field (call performAPEnStep first)");
   if (!lexicographic) { saveGaugeQDP(*gaugeSmeared, (void *const *)h_gauge, QUDA_DOUBLE_PRECISION); return; }
