@@ -26,6 +26,8 @@ bool globalReduction();
 void zero(ColorSpinorField &a);
 void copy(ColorSpinorField &dst, const ColorSpinorField &src);
 
+// cDotProduct(x, x) has a zero imaginary part and the bits of norm2(x).  The functions below that update a field and return a sum over it
+// (xmyNorm, axpyNorm, caxpyNorm, caxpyXmazNormX, cabxpyAxNorm, caxpyDotzy) sum, on a 16-bit field, the fp32 values before the store rounds them
 double norm2(const ColorSpinorField &a);
 double reDotProduct(const ColorSpinorField &x, const ColorSpinorField &y);
 Complex cDotProduct(const ColorSpinorField &x, const ColorSpinorField &y);           // sum conj(x) y

@@ -74,6 +74,29 @@ void qudaAmdBlasTripleCGReduction(const void *x, const void *y, const void *z, d
 double qudaAmdBlasAxpyReDot(double a, const void *x, void *y);
 void qudaAmdBlasMultiShiftUpdate(int k, void *x[], void *p[], const void *r, const double *alpha, const double *beta, const double *zeta);
 int qudaAmdBlasMultiShiftChunk(void);
+/* test hooks onto the rest of namespace blas (include/blas.h), all on qudaAmdSpinor handles of one precision and geometry.
+ * qudaAmdBlasApply calls the function named op (its name in blas.h: "caxpyXmazNormX", ...) on the operands it takes (the others may be
+ * null), writes the sums it returns to result — a dot product as (re, im), the NormA / NormB forms as (re, im, norm) — and returns
+ * their number.  coeff: a complex a is (coeff[0], coeff[1]) and a complex b (coeff[2], coeff[3]); two real coefficients a, b (axpby) are
+ * coeff[0], coeff[1]; cabxpyAx / cabxpyAxNorm take the real a from coeff[0] and the complex b from (coeff[2], coeff[3]).  Operands are
+ * named as in blas.h; the operations are norm2, reDotProduct, cDotProduct, cDotProductNormA, cDotProductNormB, ax, axpy, xpy, xpay, mxpy,
+ * axpby, xmyNorm, axpyNorm, caxpy, caxpby, xmyz, cxpaypbz, caxpyNorm, caxpyXmaz, caxpyXmazNormX, caxXmaz, caxInit, cabxpyAx,
+ * cabxpyAxNorm, caxpyDotzy, caxpbypzYmbw */
+int qudaAmdBlasApply(const char *op, const double coeff[4], void *x, void *y, void *z, void *w, double result[3]);
+/* the device-scalar sequence of the MR smoother: cDotProductNormADev(p, q) immediately followed by the update named op — "caxpyXmazDev",
+ * "caxXmazDev" (x, y, z) or "caxInitDev" (x, y, z, w) — which takes alpha = omega (p, q) / |p|^2 from device memory (0 where |p|^2 = 0) */
+void qudaAmdBlasDevUpdate(const char *op, double omega, const void *p, const void *q, void *x, void *y, void *z, void *w);
+/* the multi-field kernels of the blocked GCR orthogonalisation, k fields f[i]; complex arrays as (re, im) pairs:
+ *   MultiSupported       1 if k fields of field's precision can go through them
+ *   MultiDot             beta[i] = (f_i, y) for i < k, yr = (y, r), *ynorm = |y|^2
+ *   MultiCaxpyResidual   y <- scale (y + sum_i c_i f_i) ; r <- r - a y ; sums = (|r|^2, |y|^2)
+ *   MultiCaxpy           y <- y + sum_i c_i f_i */
+int qudaAmdBlasMultiSupported(const void *field, int k);
+void qudaAmdBlasMultiDot(int k, void *f[], const void *y, const void *r, double *beta, double yr[2], double *ynorm);
+void qudaAmdBlasMultiCaxpyResidual(int k, void *f[], const double *c, double scale, void *y, const double a[2], void *r, double sums[2]);
+void qudaAmdBlasMultiCaxpy(int k, void *f[], const double *c, void *y);
+/* result = (|x|^2, |r|^2, mean over sites of |r(site)|^2 / |x(site)|^2, a site with x = 0 counting 1) */
+void qudaAmdBlasHeavyQuarkResidualNorm(const void *x, const void *r, double result[3]);
 /* out = (M^dag M + shift) in through the DiracMdagM functor the solvers use; shift = 0 launches exactly what qudaAmdDiracMdagM does */
 void qudaAmdDiracMdagMShift(void *dirac, void *out, const void *in, double shift);
 /* device-event timed loops for tools/cg_timing.py, seconds per pass:

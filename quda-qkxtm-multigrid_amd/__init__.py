@@ -126,7 +126,9 @@ EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLo
                  "qudaAmdDeflationExactLoop", "qudaAmdHostSymmetricEig", "qudaAmdRotateBasis", "qudaAmdBlockDot", "qudaAmdBlockAxpy", "qudaAmdLastEigenvalues",
                  "qudaAmdBlasAxpyCGNorm", "qudaAmdBlasAxpyZpbx", "qudaAmdBlasTripleCGReduction", "qudaAmdBlasAxpyReDot", "qudaAmdBlasMultiShiftUpdate",
                  "qudaAmdBlasMultiShiftChunk", "qudaAmdDiracMdagMShift", "qudaAmdTimeMdagM", "qudaAmdTimeCGBlas", "qudaAmdTimeMultiShift",
-                 "qudaAmdNdegTwist", "qudaAmdStoutSmear", "qudaAmdQCharge", "qudaAmdSu3ExpIQ"]
+                 "qudaAmdNdegTwist", "qudaAmdStoutSmear", "qudaAmdQCharge", "qudaAmdSu3ExpIQ",
+                 "qudaAmdBlasApply", "qudaAmdBlasDevUpdate", "qudaAmdBlasMultiSupported", "qudaAmdBlasMultiDot", "qudaAmdBlasMultiCaxpyResidual",
+                 "qudaAmdBlasMultiCaxpy", "qudaAmdBlasHeavyQuarkResidualNorm"]
 
 _lib = None
 
@@ -223,6 +225,20 @@ def lib():
         L.qudaAmdBlasMultiShiftUpdate.restype = None
         L.qudaAmdBlasMultiShiftChunk.argtypes = []
         L.qudaAmdBlasMultiShiftChunk.restype = _i
+        L.qudaAmdBlasApply.argtypes = [C.c_char_p, C.POINTER(_d), _p, _p, _p, _p, C.POINTER(_d)]
+        L.qudaAmdBlasApply.restype = _i
+        L.qudaAmdBlasDevUpdate.argtypes = [C.c_char_p, _d, _p, _p, _p, _p, _p, _p]
+        L.qudaAmdBlasDevUpdate.restype = None
+        L.qudaAmdBlasMultiSupported.argtypes = [_p, _i]
+        L.qudaAmdBlasMultiSupported.restype = _i
+        L.qudaAmdBlasMultiDot.argtypes = [_i, C.POINTER(_p), _p, _p, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]
+        L.qudaAmdBlasMultiDot.restype = None
+        L.qudaAmdBlasMultiCaxpyResidual.argtypes = [_i, C.POINTER(_p), C.POINTER(_d), _d, _p, C.POINTER(_d), _p, C.POINTER(_d)]
+        L.qudaAmdBlasMultiCaxpyResidual.restype = None
+        L.qudaAmdBlasMultiCaxpy.argtypes = [_i, C.POINTER(_p), C.POINTER(_d), _p]
+        L.qudaAmdBlasMultiCaxpy.restype = None
+        L.qudaAmdBlasHeavyQuarkResidualNorm.argtypes = [_p, _p, C.POINTER(_d)]
+        L.qudaAmdBlasHeavyQuarkResidualNorm.restype = None
         L.qudaAmdDiracMdagMShift.argtypes = [_p, _p, _p, _d]
         L.qudaAmdDiracMdagMShift.restype = None
         L.qudaAmdTimeMdagM.argtypes = [_p, _p, _p, _i]
@@ -517,6 +533,67 @@ def multi_shift_update(x, p, r, alpha, beta, zeta):
     hx, hp = (_p * max(k, 1))(*[f.h for f in x]), (_p * max(k, 1))(*[f.h for f in p])
     a, b, z = [(_d * max(k, 1))(*[float(v) for v in c]) for c in (alpha, beta, zeta)]
     lib().qudaAmdBlasMultiShiftUpdate(k, hx, hp, r.h, a, b, z)
+
+
+def blas_apply(op, coeff=(), x=None, y=None, z=None, w=None):
+    """qudaAmdBlasApply: the function of namespace blas named op (include/blas.h) on Spinors named as there; coeff as quda_amd_ext.h lays
+    it out (complex a, complex b as four reals; real a, b first; cabxpyAx: a, unused, re b, im b).  Returns the tuple of its sums"""
+    c = (_d * 4)(*([float(v) for v in coeff] + [0.0] * (4 - len(coeff))))
+    r = (_d * 3)()
+    n = lib().qudaAmdBlasApply(op.encode(), c, *[f.h if f is not None else None for f in (x, y, z, w)], r)
+    return tuple(r[i] for i in range(n))
+
+
+def blas_dev_update(op, omega, p, q, x, y, z, w=None):
+    """qudaAmdBlasDevUpdate: cDotProductNormADev(p, q), then caxpyXmazDev / caxXmazDev / caxInitDev (op) with alpha = omega (p, q) / |p|^2
+    taken from device memory"""
+    lib().qudaAmdBlasDevUpdate(op.encode(), float(omega), p.h, q.h, x.h, y.h, z.h, w.h if w is not None else None)
+
+
+def _complex_list(c):
+    k = len(c)
+    a = (_d * (2 * max(k, 1)))()
+    for i, v in enumerate(c):
+        a[2 * i], a[2 * i + 1] = complex(v).real, complex(v).imag
+    return a
+
+
+def multi_supported(field, k):
+    """qudaAmdBlasMultiSupported: can k fields of this precision go through the multi-field kernels"""
+    return bool(lib().qudaAmdBlasMultiSupported(field.h, int(k)))
+
+
+def multi_dot(f, y, r):
+    """qudaAmdBlasMultiDot: ([(f_i, y)], (y, r), |y|^2) in one sweep"""
+    k = len(f)
+    beta, yr, yn = (_d * (2 * max(k, 1)))(), (_d * 2)(), (_d * 1)()
+    lib().qudaAmdBlasMultiDot(k, (_p * max(k, 1))(*[g.h for g in f]), y.h, r.h, beta, yr, yn)
+    return [complex(beta[2 * i], beta[2 * i + 1]) for i in range(k)], complex(yr[0], yr[1]), yn[0]
+
+
+def multi_caxpy_residual(c, f, scale, y, a, r):
+    """qudaAmdBlasMultiCaxpyResidual: y <- scale (y + sum_i c_i f_i) ; r <- r - a y ; returns (|r|^2, |y|^2)"""
+    k = len(f)
+    if len(c) != k:
+        raise ValueError("one coefficient per field")
+    s = (_d * 2)()
+    lib().qudaAmdBlasMultiCaxpyResidual(k, (_p * max(k, 1))(*[g.h for g in f]), _complex_list(c), float(scale), y.h, _complex_list([a]), r.h, s)
+    return s[0], s[1]
+
+
+def multi_caxpy(c, f, y):
+    """qudaAmdBlasMultiCaxpy: y <- y + sum_i c_i f_i"""
+    k = len(f)
+    if len(c) != k:
+        raise ValueError("one coefficient per field")
+    lib().qudaAmdBlasMultiCaxpy(k, (_p * max(k, 1))(*[g.h for g in f]), _complex_list(c), y.h)
+
+
+def heavy_quark_residual_norm(x, r):
+    """qudaAmdBlasHeavyQuarkResidualNorm: (|x|^2, |r|^2, mean over sites of |r(site)|^2 / |x(site)|^2)"""
+    s = (_d * 3)()
+    lib().qudaAmdBlasHeavyQuarkResidualNorm(x.h, r.h, s)
+    return s[0], s[1], s[2]
 
 
 def multi_src_stats():

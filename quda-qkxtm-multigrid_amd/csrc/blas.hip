@@ -251,10 +251,11 @@ template <typename real, int M> struct alignas(16) Chunk { real v[M]; };
   static constexpr bool rx = RX, ry = RY, rz = RZ, rw = RW, wx = WX, wy = WY, wz = WZ, ww = WW; \
   static constexpr int nred = NRED;
 
+// norm2 and the real part of the complex dots accumulate one explicit fma per real, in element order: cDotProduct(x, x) then has the bits of norm2(x)
 struct Norm2F { QA_FLAGS(1, 0, 0, 0, 0, 0, 0, 0, 1)
   template <typename real, int M> __device__ void operator()(real *x, real *, real *, real *, double *r) const {
 #pragma unroll
-    for (int i = 0; i < M; i++) r[0] += (double)x[i] * (double)x[i];
+    for (int i = 0; i < M; i++) r[0] = fma((double)x[i], (double)x[i], r[0]);
   } };
 struct ReDotF { QA_FLAGS(1, 1, 0, 0, 0, 0, 0, 0, 1)
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *, real *, double *r) const {
@@ -267,8 +268,11 @@ template <int NORM> struct CDotF { QA_FLAGS(1, 1, 0, 0, 0, 0, 0, 0, (NORM ? 3 : 
 #pragma unroll
     for (int i = 0; i < M; i += 2) {
       const double xr = x[i], xi = x[i + 1], yr = y[i], yi = y[i + 1];
-      r[0] += xr * yr + xi * yi;
-      r[1] += xr * yi - xi * yr;
+      r[0] = fma(xi, yi, fma(xr, yr, r[0]));
+      // xr yi - xi yr with both products treated alike, so that it is exactly 0 where y is x: contracted to fma(xr, yi, -(xi yr)) it left the
+      // rounding error of the one rounded product of every fp64 element.  t = fl(xi yr); fma(xi, yr, -t) is that product's error, exactly
+      const double t = xi * yr;
+      r[1] += fma(xr, yi, -t) - fma(xi, yr, -t);
       if (NORM == 1) r[2] += xr * xr + xi * xi;
       if (NORM == 2) r[2] += yr * yr + yi * yi;
     }
@@ -313,6 +317,7 @@ struct CxpaypbzF { double ar, ai, br, bi; QA_FLAGS(1, 1, 1, 0, 0, 0, 1, 0, 0)
   } };
 // y += a x ; x -= a z  (+ |x|^2)
 template <int NRM> struct CaxpyXmazF { double ar, ai; QA_FLAGS(1, 1, 1, 0, 1, 1, 0, 0, NRM)
+  static constexpr bool identityAtZero = NRM == 0;   // a = 0 changes neither field and there is no sum to deliver
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *z, real *, double *r) const {
 #pragma unroll
     for (int i = 0; i < M; i += 2) {
@@ -551,9 +556,16 @@ template <typename Base> struct DevAlpha : Base {
     const double sc = z > 0.0 ? omega / z : 0.0;   // zero source or breakdown: nothing to add (the host loop breaks there)
     this->ar = sc * dres[0]; this->ai = sc * dres[1];
   }
+  // alpha = 0 and an update that then is the identity: the kernel returns at once.  Rewriting a 16-bit field is not the identity — the store
+  // derives the site's scale anew from the loaded values, fl(32767 fl(norm / 32767)), which is one ulp off norm at about one site in a hundred
+  __device__ __forceinline__ bool idle() const { return baseIdentityAtZero<Base>(0) && this->ar == 0.0 && this->ai == 0.0; }
+  template <typename B> static __device__ __forceinline__ constexpr auto baseIdentityAtZero(int) -> decltype(B::identityAtZero) { return B::identityAtZero; }
+  template <typename B> static __device__ __forceinline__ constexpr bool baseIdentityAtZero(long) { return false; }
 };
 template <typename F> __device__ __forceinline__ auto blas_prepare(F &f, int) -> decltype(f.prepare(), void()) { f.prepare(); }
 template <typename F> __device__ __forceinline__ void blas_prepare(F &, long) {}
+template <typename F> __device__ __forceinline__ auto blas_idle(const F &f, int) -> decltype(f.idle()) { return f.idle(); }
+template <typename F> __device__ __forceinline__ bool blas_idle(const F &, long) { return false; }
 
 // ---- kernel ----
 template <typename T, int M, bool SITE, typename F>
@@ -565,6 +577,7 @@ __global__ void __launch_bounds__(256) blas_kernel(BlasArg<F> arg) {
   const long total = arg.n * arg.nseg;
   F f = arg.f;
   blas_prepare(f, 0);
+  if (F::nred == 0 && blas_idle(f, 0)) return;   // uniform over the grid: every thread read the same device scalars
   if constexpr (!SITE) {
     // Four chunks per thread and trip, all their loads requested before the first is used: a streaming kernel needs ~64 KB in flight per CU
     // to cover the HBM latency at 8 TB/s (Little), and two 16-byte loads per lane in 8 waves per CU are 16 KB — the one-chunk loop ran

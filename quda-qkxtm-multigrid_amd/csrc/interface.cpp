@@ -681,6 +681,84 @@ void qudaAmdBlasMultiShiftUpdate(int k, void *x[], void *p[], const void *r, con
   blas::multiShiftUpdate(k, fieldList(x, k), fieldList(p, k), *(const ColorSpinorField *)r, alpha, beta, zeta);
 }
 int qudaAmdBlasMultiShiftChunk(void) { return blas::multiShiftChunk(); }
+// test hooks onto the rest of namespace blas: one dispatcher by name for the single-field functions
+int qudaAmdBlasApply(const char *op, const double coeff[4], void *x_, void *y_, void *z_, void *w_, double r[3]) {
+  auto is = [&](const char *name) { return !strcmp(op, name); };
+  auto field = [&](void *p, const char *which) -> ColorSpinorField & {
+    if (!p) errorQuda("qudaAmdBlasApply(%s): operand %s is missing", op, which);
+    return *(ColorSpinorField *)p;
+  };
+  auto X = [&]() -> ColorSpinorField & { return field(x_, "x"); };
+  auto Y = [&]() -> ColorSpinorField & { return field(y_, "y"); };
+  auto Z = [&]() -> ColorSpinorField & { return field(z_, "z"); };
+  auto W = [&]() -> ColorSpinorField & { return field(w_, "w"); };
+  const double ra = coeff[0], rb = coeff[1];
+  const Complex a(coeff[0], coeff[1]), b(coeff[2], coeff[3]);
+  auto put2 = [&](const Complex &c) { r[0] = c.real(); r[1] = c.imag(); return 2; };
+  auto put3 = [&](const double3_t &t) { r[0] = t.x; r[1] = t.y; r[2] = t.z; return 3; };
+  if (is("norm2")) { r[0] = blas::norm2(X()); return 1; }
+  if (is("reDotProduct")) { r[0] = blas::reDotProduct(X(), Y()); return 1; }
+  if (is("cDotProduct")) return put2(blas::cDotProduct(X(), Y()));
+  if (is("cDotProductNormA")) return put3(blas::cDotProductNormA(X(), Y()));
+  if (is("cDotProductNormB")) return put3(blas::cDotProductNormB(X(), Y()));
+  if (is("ax")) { blas::ax(ra, X()); return 0; }
+  if (is("axpy")) { blas::axpy(ra, X(), Y()); return 0; }
+  if (is("xpy")) { blas::xpy(X(), Y()); return 0; }
+  if (is("xpay")) { blas::xpay(X(), ra, Y()); return 0; }
+  if (is("mxpy")) { blas::mxpy(X(), Y()); return 0; }
+  if (is("axpby")) { blas::axpby(ra, X(), rb, Y()); return 0; }
+  if (is("xmyNorm")) { r[0] = blas::xmyNorm(X(), Y()); return 1; }
+  if (is("axpyNorm")) { r[0] = blas::axpyNorm(ra, X(), Y()); return 1; }
+  if (is("caxpy")) { blas::caxpy(a, X(), Y()); return 0; }
+  if (is("caxpby")) { blas::caxpby(a, X(), b, Y()); return 0; }
+  if (is("xmyz")) { blas::xmyz(X(), Y(), Z()); return 0; }
+  if (is("cxpaypbz")) { blas::cxpaypbz(X(), a, Y(), b, Z()); return 0; }
+  if (is("caxpyNorm")) { r[0] = blas::caxpyNorm(a, X(), Y()); return 1; }
+  if (is("caxpyXmaz")) { blas::caxpyXmaz(a, X(), Y(), Z()); return 0; }
+  if (is("caxpyXmazNormX")) { r[0] = blas::caxpyXmazNormX(a, X(), Y(), Z()); return 1; }
+  if (is("caxXmaz")) { blas::caxXmaz(a, X(), Y(), Z()); return 0; }
+  if (is("caxInit")) { blas::caxInit(a, X(), Y(), Z(), W()); return 0; }
+  if (is("cabxpyAx")) { blas::cabxpyAx(ra, b, X(), Y()); return 0; }
+  if (is("cabxpyAxNorm")) { r[0] = blas::cabxpyAxNorm(ra, b, X(), Y()); return 1; }
+  if (is("caxpyDotzy")) return put2(blas::caxpyDotzy(a, X(), Y(), Z()));
+  if (is("caxpbypzYmbw")) { blas::caxpbypzYmbw(a, X(), b, Y(), Z(), W()); return 0; }
+  errorQuda("qudaAmdBlasApply: unknown operation %s", op);
+  return -1;
+}
+// both calls in one function: nothing can overwrite the sums in device memory between them
+void qudaAmdBlasDevUpdate(const char *op, double omega, const void *p, const void *q, void *x, void *y, void *z, void *w) {
+  if (!x || !y || !z || !p || !q) errorQuda("qudaAmdBlasDevUpdate(%s): an operand is missing", op);
+  int which = !strcmp(op, "caxpyXmazDev") ? 0 : (!strcmp(op, "caxXmazDev") ? 1 : (!strcmp(op, "caxInitDev") ? 2 : -1));
+  if (which < 0) errorQuda("qudaAmdBlasDevUpdate: unknown operation %s", op);
+  if (which == 2 && !w) errorQuda("qudaAmdBlasDevUpdate(%s): operand w is missing", op);
+  blas::cDotProductNormADev(*(const ColorSpinorField *)p, *(const ColorSpinorField *)q);
+  if (which == 0) blas::caxpyXmazDev(omega, *(ColorSpinorField *)x, *(ColorSpinorField *)y, *(const ColorSpinorField *)z);
+  else if (which == 1) blas::caxXmazDev(omega, *(ColorSpinorField *)x, *(ColorSpinorField *)y, *(const ColorSpinorField *)z);
+  else blas::caxInitDev(omega, *(const ColorSpinorField *)x, *(ColorSpinorField *)y, *(const ColorSpinorField *)z, *(ColorSpinorField *)w);
+}
+int qudaAmdBlasMultiSupported(const void *f, int k) { return blas::multiSupported(*(const ColorSpinorField *)f, k) ? 1 : 0; }
+static std::vector<Complex> complexList(const double *c, int k) {
+  std::vector<Complex> v(k > 0 ? k : 1);
+  for (int i = 0; i < k; i++) v[i] = Complex(c[2 * i], c[2 * i + 1]);
+  return v;
+}
+void qudaAmdBlasMultiDot(int k, void *f[], const void *y, const void *r, double *beta, double yr[2], double *ynorm) {
+  std::vector<Complex> b(k > 0 ? k : 1);
+  Complex c;
+  blas::multiDot(b.data(), c, *ynorm, fieldList(f, k), k, *(const ColorSpinorField *)y, *(const ColorSpinorField *)r);
+  for (int i = 0; i < k; i++) { beta[2 * i] = b[i].real(); beta[2 * i + 1] = b[i].imag(); }
+  yr[0] = c.real(); yr[1] = c.imag();
+}
+void qudaAmdBlasMultiCaxpyResidual(int k, void *f[], const double *c, double scale, void *y, const double a[2], void *r, double sums[2]) {
+  blas::multiCaxpyResidual(sums[0], sums[1], complexList(c, k).data(), fieldList(f, k), k, scale, *(ColorSpinorField *)y, Complex(a[0], a[1]), *(ColorSpinorField *)r);
+}
+void qudaAmdBlasMultiCaxpy(int k, void *f[], const double *c, void *y) {
+  blas::multiCaxpy(complexList(c, k).data(), fieldList(f, k), k, *(ColorSpinorField *)y);
+}
+void qudaAmdBlasHeavyQuarkResidualNorm(const void *x, const void *r, double result[3]) {
+  const double3_t t = blas::HeavyQuarkResidualNorm(*(const ColorSpinorField *)x, *(const ColorSpinorField *)r);
+  result[0] = t.x; result[1] = t.y; result[2] = t.z;
+}
 void qudaAmdDiracMdagMShift(void *d, void *out, const void *in, double shift) {
   DiracMdagM m((const Dirac *)d);
   m.shift = shift;
