@@ -26,6 +26,7 @@ bool globalReduction();
 void zero(ColorSpinorField &a);
 void copy(ColorSpinorField &dst, const ColorSpinorField &src);
 
+// Every sum below, HeavyQuarkResidualNorm included, is added in a fixed order: the same inputs give the same bits on every call.
 // cDotProduct(x, x) has a zero imaginary part and the bits of norm2(x).  The functions below that update a field and return a sum over it
 // (xmyNorm, axpyNorm, caxpyNorm, caxpyXmazNormX, cabxpyAxNorm, caxpyDotzy) sum, on a 16-bit field, the fp32 values before the store rounds them
 double norm2(const ColorSpinorField &a);

@@ -11,6 +11,7 @@
 // fp64/fp32 fields of any spin/colour are treated as flat arrays (complex pairs stay adjacent in the
 // FLOAT2/FLOAT4 planar orders); 16-bit fields go site by site because of their per-site scale.
 #include <cstring>
+#include <type_traits>
 #include <sys/time.h>
 #include <unistd.h>
 #include "blas.h"
@@ -18,6 +19,7 @@
 #include "device_io.h"
 #include "halo.h"
 #include "p2p.h"
+#include "reduce.h"
 
 namespace quda {
 namespace blas {
@@ -32,6 +34,7 @@ static double *d_part = nullptr;  // per-block partial sums
 static unsigned *d_count = nullptr;  // completion counter (zero between launches)
 constexpr int kMaxBlocks = 4096;
 constexpr int kMaxRed = 64;
+constexpr unsigned long long kPeerWaitTicks = 2000000ull;   // 20 ms of in-kernel waiting for the other ranks (they arrive within microseconds when in step), then the host takes over
 constexpr int kSlotDoubles = 48;  // doubles per (buffer, rank) slot of the all-reduce window (the blocked GCR orthogonalisation reduces 2 k + 3 <= 43 sums at once)
 
 // Block-level all-reduce over ranks through the peer windows (called by ONE block per rank, all threads of it).  Thread r
@@ -224,12 +227,8 @@ struct Seg {           // one contiguous parity block of a field
   float *norm[2];
 };
 
-template <typename F> struct BlasArg {
-  Seg x, y, z, w;
-  int nseg;
-  long n;        // chunks per segment
-  int stride;    // site path: plane stride
-  F f;
+// where the sums of a reducing kernel go (finish_reduction below; filled by planReduction)
+struct RedCtl {
   double *red;       // device result
   double *hred;      // pinned host result (nullptr: an all-reduce follows, the host reads the device word afterwards)
   double *part;      // [block][nred] partial sums
@@ -244,26 +243,43 @@ template <typename F> struct BlasArg {
   unsigned long long waitTicks;
 };
 
+template <typename F> struct BlasArg {
+  Seg x, y, z, w;
+  int nseg;
+  long n;        // chunks per segment
+  int stride;    // site path: plane stride
+  F f;
+  RedCtl c;
+};
+
 template <typename real, int M> struct alignas(16) Chunk { real v[M]; };
 
 // ---- functors: operate on one chunk (M reals, complex pairs adjacent) ----
+// what a functor may override: prepare() runs once per thread before the loop, idle() says that the update would change nothing (the kernel
+// then returns at once), identityAtZero that a zero coefficient makes it the identity, siteOnly that it needs whole sites (24 reals) in every
+// precision
+struct Functor {
+  static constexpr bool identityAtZero = false, siteOnly = false;
+  __device__ __forceinline__ void prepare() {}
+  __device__ __forceinline__ bool idle() const { return false; }
+};
 #define QA_FLAGS(RX, RY, RZ, RW, WX, WY, WZ, WW, NRED)                                        \
   static constexpr bool rx = RX, ry = RY, rz = RZ, rw = RW, wx = WX, wy = WY, wz = WZ, ww = WW; \
   static constexpr int nred = NRED;
 
 // norm2 and the real part of the complex dots accumulate one explicit fma per real, in element order: cDotProduct(x, x) then has the bits of norm2(x)
-struct Norm2F { QA_FLAGS(1, 0, 0, 0, 0, 0, 0, 0, 1)
+struct Norm2F : Functor { QA_FLAGS(1, 0, 0, 0, 0, 0, 0, 0, 1)
   template <typename real, int M> __device__ void operator()(real *x, real *, real *, real *, double *r) const {
 #pragma unroll
     for (int i = 0; i < M; i++) r[0] = fma((double)x[i], (double)x[i], r[0]);
   } };
-struct ReDotF { QA_FLAGS(1, 1, 0, 0, 0, 0, 0, 0, 1)
+struct ReDotF : Functor { QA_FLAGS(1, 1, 0, 0, 0, 0, 0, 0, 1)
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *, real *, double *r) const {
 #pragma unroll
     for (int i = 0; i < M; i++) r[0] += (double)x[i] * (double)y[i];
   } };
 // r0 + i r1 = conj(x) y ; r2 = |x|^2 (NORM=1) or |y|^2 (NORM=2)
-template <int NORM> struct CDotF { QA_FLAGS(1, 1, 0, 0, 0, 0, 0, 0, (NORM ? 3 : 2))
+template <int NORM> struct CDotF : Functor { QA_FLAGS(1, 1, 0, 0, 0, 0, 0, 0, (NORM ? 3 : 2))
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *, real *, double *r) const {
 #pragma unroll
     for (int i = 0; i < M; i += 2) {
@@ -277,19 +293,19 @@ template <int NORM> struct CDotF { QA_FLAGS(1, 1, 0, 0, 0, 0, 0, 0, (NORM ? 3 : 
       if (NORM == 2) r[2] += yr * yr + yi * yi;
     }
   } };
-struct AxF { double a; QA_FLAGS(1, 0, 0, 0, 1, 0, 0, 0, 0)
+struct AxF : Functor { double a; QA_FLAGS(1, 0, 0, 0, 1, 0, 0, 0, 0)
   template <typename real, int M> __device__ void operator()(real *x, real *, real *, real *, double *) const {
 #pragma unroll
     for (int i = 0; i < M; i++) x[i] *= (real)a;
   } };
 // y = a x + b y (+ |y|^2 if NRM)
-template <int NRM> struct AxpbyF { double a, b; QA_FLAGS(1, 1, 0, 0, 0, 1, 0, 0, NRM)
+template <int NRM> struct AxpbyF : Functor { double a, b; QA_FLAGS(1, 1, 0, 0, 0, 1, 0, 0, NRM)
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *, real *, double *r) const {
 #pragma unroll
     for (int i = 0; i < M; i++) { y[i] = (real)a * x[i] + (real)b * y[i]; if (NRM) r[0] += (double)y[i] * (double)y[i]; }
   } };
 // y = a x + b y complex (+ |y|^2)
-template <int NRM> struct CaxpbyF { double ar, ai, br, bi; QA_FLAGS(1, 1, 0, 0, 0, 1, 0, 0, NRM)
+template <int NRM> struct CaxpbyF : Functor { double ar, ai, br, bi; QA_FLAGS(1, 1, 0, 0, 0, 1, 0, 0, NRM)
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *, real *, double *r) const {
 #pragma unroll
     for (int i = 0; i < M; i += 2) {
@@ -300,13 +316,13 @@ template <int NRM> struct CaxpbyF { double ar, ai, br, bi; QA_FLAGS(1, 1, 0, 0, 
     }
   } };
 // z = x - y   (z is not read: it may hold anything)
-struct XmyzF { QA_FLAGS(1, 1, 0, 0, 0, 0, 1, 0, 0)
+struct XmyzF : Functor { QA_FLAGS(1, 1, 0, 0, 0, 0, 1, 0, 0)
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *z, real *, double *) const {
 #pragma unroll
     for (int i = 0; i < M; i++) z[i] = x[i] - y[i];
   } };
 // z = x + a y + b z
-struct CxpaypbzF { double ar, ai, br, bi; QA_FLAGS(1, 1, 1, 0, 0, 0, 1, 0, 0)
+struct CxpaypbzF : Functor { double ar, ai, br, bi; QA_FLAGS(1, 1, 1, 0, 0, 0, 1, 0, 0)
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *z, real *, double *) const {
 #pragma unroll
     for (int i = 0; i < M; i += 2) {
@@ -316,7 +332,7 @@ struct CxpaypbzF { double ar, ai, br, bi; QA_FLAGS(1, 1, 1, 0, 0, 0, 1, 0, 0)
     }
   } };
 // y += a x ; x -= a z  (+ |x|^2)
-template <int NRM> struct CaxpyXmazF { double ar, ai; QA_FLAGS(1, 1, 1, 0, 1, 1, 0, 0, NRM)
+template <int NRM> struct CaxpyXmazF : Functor { double ar, ai; QA_FLAGS(1, 1, 1, 0, 1, 1, 0, 0, NRM)
   static constexpr bool identityAtZero = NRM == 0;   // a = 0 changes neither field and there is no sum to deliver
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *z, real *, double *r) const {
 #pragma unroll
@@ -330,7 +346,7 @@ template <int NRM> struct CaxpyXmazF { double ar, ai; QA_FLAGS(1, 1, 1, 0, 1, 1,
     }
   } };
 // y = a x ; x -= a z      (first iteration of MR from a zero start: y is not read)
-struct CaxXmazF { double ar, ai; QA_FLAGS(1, 0, 1, 0, 1, 1, 0, 0, 0)
+struct CaxXmazF : Functor { double ar, ai; QA_FLAGS(1, 0, 1, 0, 1, 1, 0, 0, 0)
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *z, real *, double *) const {
 #pragma unroll
     for (int i = 0; i < M; i += 2) {
@@ -342,7 +358,7 @@ struct CaxXmazF { double ar, ai; QA_FLAGS(1, 0, 1, 0, 1, 1, 0, 0, 0)
     }
   } };
 // y = a x ; w = x - a z    (the same with the residual still in the source field x, which stays untouched)
-struct CaxInitF { double ar, ai; QA_FLAGS(1, 0, 1, 0, 0, 1, 0, 1, 0)
+struct CaxInitF : Functor { double ar, ai; QA_FLAGS(1, 0, 1, 0, 0, 1, 0, 1, 0)
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *z, real *w, double *) const {
 #pragma unroll
     for (int i = 0; i < M; i += 2) {
@@ -354,7 +370,7 @@ struct CaxInitF { double ar, ai; QA_FLAGS(1, 0, 1, 0, 0, 1, 0, 1, 0)
     }
   } };
 // x = a x ; y += b x (+ |y|^2)
-template <int NRM> struct CabxpyAxF { double a, br, bi; QA_FLAGS(1, 1, 0, 0, 1, 1, 0, 0, NRM)
+template <int NRM> struct CabxpyAxF : Functor { double a, br, bi; QA_FLAGS(1, 1, 0, 0, 1, 1, 0, 0, NRM)
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *, real *, double *r) const {
 #pragma unroll
     for (int i = 0; i < M; i += 2) {
@@ -366,7 +382,7 @@ template <int NRM> struct CabxpyAxF { double a, br, bi; QA_FLAGS(1, 1, 0, 0, 1, 
     }
   } };
 // y += a x ; (z, y)
-struct CaxpyDotzyF { double ar, ai; QA_FLAGS(1, 1, 1, 0, 0, 1, 0, 0, 2)
+struct CaxpyDotzyF : Functor { double ar, ai; QA_FLAGS(1, 1, 1, 0, 0, 1, 0, 0, 2)
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *z, real *, double *r) const {
 #pragma unroll
     for (int i = 0; i < M; i += 2) {
@@ -378,7 +394,7 @@ struct CaxpyDotzyF { double ar, ai; QA_FLAGS(1, 1, 1, 0, 0, 1, 0, 0, 2)
     }
   } };
 // z += a x + b y ; y -= b w
-struct CaxpbypzYmbwF { double ar, ai, br, bi; QA_FLAGS(1, 1, 1, 1, 0, 1, 1, 0, 0)
+struct CaxpbypzYmbwF : Functor { double ar, ai, br, bi; QA_FLAGS(1, 1, 1, 1, 0, 1, 1, 0, 0)
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *z, real *w, double *) const {
 #pragma unroll
     for (int i = 0; i < M; i += 2) {
@@ -409,7 +425,7 @@ template <typename T, int M> __device__ __forceinline__ void storedImage(typenam
   }
 }
 // y += a x ; (|y|^2, (y_new, y_new - y_old))
-struct AxpyCGNormF { double a; QA_FLAGS(1, 1, 0, 0, 0, 1, 0, 0, 2)
+struct AxpyCGNormF : Functor { double a; QA_FLAGS(1, 1, 0, 0, 0, 1, 0, 0, 2)
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *, real *, double *r) const {
 #pragma unroll
     for (int i = 0; i < M; i++) {
@@ -433,13 +449,13 @@ struct AxpyCGNormF { double a; QA_FLAGS(1, 1, 0, 0, 0, 1, 0, 0, 2)
     }
   } };
 // y += a x ; x = z + b x
-struct AxpyZpbxF { double a, b; QA_FLAGS(1, 1, 1, 0, 1, 1, 0, 0, 0)
+struct AxpyZpbxF : Functor { double a, b; QA_FLAGS(1, 1, 1, 0, 1, 1, 0, 0, 0)
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *z, real *, double *) const {
 #pragma unroll
     for (int i = 0; i < M; i++) { y[i] += (real)a * x[i]; x[i] = z[i] + (real)b * x[i]; }
   } };
 // (|x|^2, |y|^2, (y, z))
-struct TripleCGF { QA_FLAGS(1, 1, 1, 0, 0, 0, 0, 0, 3)
+struct TripleCGF : Functor { QA_FLAGS(1, 1, 1, 0, 0, 0, 0, 0, 3)
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *z, real *, double *r) const {
 #pragma unroll
     for (int i = 0; i < M; i++) {
@@ -448,7 +464,7 @@ struct TripleCGF { QA_FLAGS(1, 1, 1, 0, 0, 0, 0, 0, 3)
     }
   } };
 // y += a x ; (x, y)
-struct AxpyReDotF { double a; QA_FLAGS(1, 1, 0, 0, 0, 1, 0, 0, 1)
+struct AxpyReDotF : Functor { double a; QA_FLAGS(1, 1, 0, 0, 0, 1, 0, 0, 1)
   template <typename real, int M> __device__ void operator()(real *x, real *y, real *, real *, double *r) const {
 #pragma unroll
     for (int i = 0; i < M; i++) { y[i] += (real)a * x[i]; r[0] += (double)x[i] * (double)y[i]; }
@@ -473,15 +489,6 @@ template <typename T, typename real, int M, typename F> __device__ __forceinline
 // ---- the tail of every reducing kernel: wave shuffles -> LDS -> per-block partial -> the LAST block (completion counter) adds the
 // partials in block order (bit-reproducible), optionally does the all-reduce over ranks through the peer windows, and writes the
 // sums to device and pinned host memory.  NRED sums per thread come in, every thread of the block must call it. ----
-struct RedCtl {
-  double *red, *hred, *part;
-  unsigned *count;
-  double *const *peerSlots;
-  unsigned *const *peerCount;
-  int nranks, rank, buf;
-  unsigned expect;
-  unsigned long long waitTicks;
-};
 template <int NRED> __device__ __forceinline__ void finish_reduction(const double *red, const RedCtl &arg) {
   __shared__ double lds[4][NRED];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -499,15 +506,7 @@ template <int NRED> __device__ __forceinline__ void finish_reduction(const doubl
     for (int wv = 0; wv < (int)(blockDim.x >> 6); wv++) v += lds[wv][threadIdx.x];
     __hip_atomic_store(&arg.part[(size_t)blockIdx.x * NRED + threadIdx.x], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  __shared__ int isLast;
-  // the partials are sc1 (write-through) stores; the storing wave waits for their acknowledgement BEFORE the barrier, so the
-  // counter bump below cannot overtake them on their way to memory (the last block may sit on another XCD with its own L2);
-  // it then reads them with sc1 loads behind its own barrier — the drained-sc1 hand-off of MI355X_MICROARCH.md
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) isLast = __hip_atomic_fetch_add(arg.count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-  __syncthreads();
-  if (isLast) {
+  lastBlockFinishes(arg.count, [&] {
     // the last block adds the partials in a fixed order: thread t takes blocks t, t + blockDim, ...; then the block tree
 #pragma unroll 1
     for (int k = 0; k < NRED; k++) {
@@ -541,8 +540,7 @@ template <int NRED> __device__ __forceinline__ void finish_reduction(const doubl
       arg.red[threadIdx.x] = v;
       if (arg.hred) __hip_atomic_store(&arg.hred[threadIdx.x], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    if (threadIdx.x == 0) __hip_atomic_store(arg.count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  });
 }
 
 // ---- device-side scalars: the coefficient of an update comes from the sums the PREVIOUS kernel of the stream left in device memory, so a fixed-length
@@ -558,14 +556,8 @@ template <typename Base> struct DevAlpha : Base {
   }
   // alpha = 0 and an update that then is the identity: the kernel returns at once.  Rewriting a 16-bit field is not the identity — the store
   // derives the site's scale anew from the loaded values, fl(32767 fl(norm / 32767)), which is one ulp off norm at about one site in a hundred
-  __device__ __forceinline__ bool idle() const { return baseIdentityAtZero<Base>(0) && this->ar == 0.0 && this->ai == 0.0; }
-  template <typename B> static __device__ __forceinline__ constexpr auto baseIdentityAtZero(int) -> decltype(B::identityAtZero) { return B::identityAtZero; }
-  template <typename B> static __device__ __forceinline__ constexpr bool baseIdentityAtZero(long) { return false; }
+  __device__ __forceinline__ bool idle() const { return Base::identityAtZero && this->ar == 0.0 && this->ai == 0.0; }
 };
-template <typename F> __device__ __forceinline__ auto blas_prepare(F &f, int) -> decltype(f.prepare(), void()) { f.prepare(); }
-template <typename F> __device__ __forceinline__ void blas_prepare(F &, long) {}
-template <typename F> __device__ __forceinline__ auto blas_idle(const F &f, int) -> decltype(f.idle()) { return f.idle(); }
-template <typename F> __device__ __forceinline__ bool blas_idle(const F &, long) { return false; }
 
 // ---- kernel ----
 template <typename T, int M, bool SITE, typename F>
@@ -576,8 +568,8 @@ __global__ void __launch_bounds__(256) blas_kernel(BlasArg<F> arg) {
   for (int k = 0; k < (F::nred > 0 ? F::nred : 1); k++) red[k] = 0.0;
   const long total = arg.n * arg.nseg;
   F f = arg.f;
-  blas_prepare(f, 0);
-  if (F::nred == 0 && blas_idle(f, 0)) return;   // uniform over the grid: every thread read the same device scalars
+  f.prepare();
+  if (F::nred == 0 && f.idle()) return;   // uniform over the grid: every thread read the same device scalars
   if constexpr (!SITE) {
     // Four chunks per thread and trip, all their loads requested before the first is used: a streaming kernel needs ~64 KB in flight per CU
     // to cover the HBM latency at 8 TB/s (Little), and two 16-byte loads per lane in 8 waves per CU are 16 KB — the one-chunk loop ran
@@ -631,9 +623,7 @@ __global__ void __launch_bounds__(256) blas_kernel(BlasArg<F> arg) {
   }
   }
   if (F::nred > 0) {
-    RedCtl c;
-    c.red = arg.red; c.hred = arg.hred; c.part = arg.part; c.count = arg.count; c.peerSlots = arg.peerSlots; c.peerCount = arg.peerCount;
-    c.nranks = arg.nranks; c.rank = arg.rank; c.buf = arg.buf; c.expect = arg.expect; c.waitTicks = arg.waitTicks;
+    const RedCtl c = arg.c;   // a copy: through a reference into the kernel argument the compiler reads the block ahead of the loop, up to 28 more VGPRs
     finish_reduction<(F::nred > 0 ? F::nred : 1)>(red, c);
   }
 }
@@ -821,9 +811,98 @@ static void checkSame(const ColorSpinorField &a, const ColorSpinorField &b) {
     errorQuda("blas geometry mismatch");
 }
 
+// ---- what the host decides for a launch: the kernel's shape, the instantiation for a run-time count, the grid, the route of the sums ----
+// The kernel shape of a field: fp64 / fp32 fields are flat arrays of 16-byte chunks (2 / 4 reals), 16-bit fields — and, with SITES, every
+// field — go site by site, 24 reals a chunk.  fn(Shape<T, M, SITE>(), extent) gets the shape as a type and the loop bounds that go with it.
+template <typename T_, int M_, bool SITE_> struct Shape { using T = T_; static constexpr int M = M_; static constexpr bool SITE = SITE_; };
+struct Extent {
+  int nseg;      // parity segments
+  long n;        // chunks per segment
+  int stride;    // site path: plane stride
+};
+template <bool SITES = false, typename Fn> static void forShape(const ColorSpinorField &x, Fn &&fn) {
+  Extent e;
+  e.nseg = x.SiteSubset() == QUDA_FULL_SITE_SUBSET ? 2 : 1;
+  e.stride = x.Stride();
+  const long nreal = (long)x.Stride() * x.Nspin() * x.Ncolor() * 2;
+  const auto sites = [&](auto shape) {
+    if (x.Nspin() != 4 || x.Ncolor() != 3) errorQuda("16-bit blas only for fine-grid spinors");
+    e.n = x.VolumeCB();
+    fn(shape, e);
+  };
+  switch (x.Precision()) {
+    case QUDA_DOUBLE_PRECISION:
+      if constexpr (SITES) sites(Shape<double, 24, true>());
+      else { e.n = nreal / 2; fn(Shape<double, 2, false>(), e); }
+      break;
+    case QUDA_SINGLE_PRECISION:
+      if constexpr (SITES) sites(Shape<float, 24, true>());
+      else {
+        if (nreal % 4) errorQuda("field length %ld not a multiple of 4", nreal);
+        e.n = nreal / 4; fn(Shape<float, 4, false>(), e);
+      }
+      break;
+    case QUDA_HALF_PRECISION: sites(Shape<short, 24, true>()); break;
+    default: errorQuda("bad precision %d", x.Precision());
+  }
+}
+// fn(std::integral_constant<int, I>()) for the first I of the ascending list with v <= I (the last I if there is none)
+template <int I, int... Rest, typename Fn> static void forAtLeast(int v, Fn &&fn) {
+  if constexpr (sizeof...(Rest) == 0) fn(std::integral_constant<int, I>());
+  else if (v <= I) fn(std::integral_constant<int, I>());
+  else forAtLeast<Rest...>(v, fn);
+}
+// work-groups of 256 threads for a kernel over `chunks` chunks, at most dflt of them — or at most QUDA_AMD_BLAS_BLOCKS, read once per process,
+// where that is a number in [1, kMaxBlocks].  The defaults, measured on MI355X:
+//   512 (2 per CU) for the one- to four-field kernels: 32x16x16x16 fp64 norm2 65 us at 4096 blocks (the completion counter / fp64 atomics of
+//   3072 blocks serialise on one address) -> 34 us at 512; streaming axpy 5.5 -> 6.0 TB/s;
+//   2048 / 1024 for the k-field updates / dots.  At 48^3 x 96 (fp32, k = 1..9 fields, tools/profile_mg_solve.sh with QUDA_AMD_BLAS_BLOCKS) the
+//   k-field update runs at 0.43 / 0.61 / 0.69 of the HBM roofline with 512 / 1024 / 2048 work-groups (one chunk of every field per thread and
+//   trip: more resident waves, not deeper loops, keep the k + 2 streams busy), the k-field dots at 0.56 / 0.59 / 0.54 (their 43-value block
+//   reduction grows with the grid); the one- to four-field kernels prefer 512 (0.72 against 0.67).
+static int gridFor(long chunks, int dflt) {
+  static const int cap = [] { const char *e = getenv("QUDA_AMD_BLAS_BLOCKS"); const int c = e ? atoi(e) : 0; return c >= 1 && c <= kMaxBlocks ? c : 0; }();
+  const int c = cap ? cap : dflt;
+  const long b = (chunks + 255) / 256;
+  return (int)(b > c ? c : (b < 1 ? 1 : b));
+}
+// The route of a kernel's nred sums: rank-local (the kernel writes them to the pinned host buffer), all-reduced by the kernel's last block
+// through the peer windows, or all-reduced by RCCL after the kernel.  Every reducing launch goes planReduction -> kernel -> finishPlan.
+struct RedPlan { bool allreduce, peer; };
+static RedPlan planReduction(RedCtl &c, int nred) {
+  if (!d_red) init();
+  RedPlan p;
+  p.allreduce = g_global_reduction && commReductionsNeeded(); p.peer = false;
+  c.red = d_red; c.part = d_part; c.count = d_count;
+  c.hred = p.allreduce ? nullptr : h_red_dev;
+  c.peerSlots = nullptr; c.peerCount = nullptr; c.nranks = 1; c.rank = 0; c.buf = 0; c.expect = 0; c.waitTicks = 0;
+  // (nred = 0, a kernel without sums: nothing to route, and the collective set-up of the window must not start on its account)
+  if (p.allreduce && nred > 0 && nred <= kSlotDoubles && reduceWindowActive()) {
+    // the last block of the kernel does the all-reduce itself through the peer windows and writes the global sums to the host
+    const CommGrid &cg = commGrid();
+    c.peerSlots = g_rw.d_slots; c.peerCount = g_rw.d_counts;
+    c.nranks = cg.size; c.rank = cg.rank;
+    c.buf = (int)(++g_rw.seq & 1);
+    c.expect = (g_rw.uses[c.buf] += (unsigned)cg.size);
+    c.waitTicks = kPeerWaitTicks;
+    c.hred = h_red_dev;
+    p.allreduce = false; p.peer = true;
+    p2pStats()[4]++;
+  } else if (p.allreduce) p2pStats()[5]++;
+  return p;
+}
+static void finishPlan(const RedPlan &p, const RedCtl &c, int nred, double *out, hipStream_t s) {
+  if (p.allreduce) {
+    commAllreduceDevice(d_red, nred, s);  // RCCL all-reduce of the rank sums, in stream order
+    HIP_CHECK(hipMemcpyAsync(h_red, d_red, nred * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (p.peer && h_red[kMaxRed - 1] == 0.0) finishAllreduceOnHost(c.buf, c.expect, nred, h_red);
+  for (int k = 0; k < nred; k++) out[k] = h_red[k];
+}
+
 template <typename F>
 static void launch(const F &f, const ColorSpinorField &x, const ColorSpinorField *y, const ColorSpinorField *z, const ColorSpinorField *w, double *out) {
-  if (!d_red) init();
   if (y) checkSame(x, *y);
   if (z) checkSame(x, *z);
   if (w) checkSame(x, *w);
@@ -832,65 +911,18 @@ static void launch(const F &f, const ColorSpinorField &x, const ColorSpinorField
   arg.y = y ? segOf(*y) : arg.x;
   arg.z = z ? segOf(*z) : arg.x;
   arg.w = w ? segOf(*w) : arg.x;
-  arg.nseg = x.SiteSubset() == QUDA_FULL_SITE_SUBSET ? 2 : 1;
-  arg.stride = x.Stride();
   arg.f = f;
-  arg.red = d_red;
-  arg.part = d_part;
-  arg.count = d_count;
-  bool allreduce = g_global_reduction && commReductionsNeeded(), peer = false;
-  arg.hred = allreduce ? nullptr : h_red_dev;
-  arg.peerSlots = nullptr; arg.peerCount = nullptr; arg.nranks = 1; arg.rank = 0; arg.buf = 0; arg.expect = 0; arg.waitTicks = 0;
-  if (allreduce && F::nred > 0 && F::nred <= kSlotDoubles && reduceWindowActive()) {
-    // the last block of the kernel does the all-reduce itself through the peer windows and writes the global sums to the host
-    const CommGrid &cg = commGrid();
-    arg.peerSlots = g_rw.d_slots; arg.peerCount = g_rw.d_counts;
-    arg.nranks = cg.size; arg.rank = cg.rank;
-    arg.buf = (int)(++g_rw.seq & 1);
-    arg.expect = (g_rw.uses[arg.buf] += (unsigned)cg.size);
-    arg.waitTicks = 2000000ull;   // 20 ms of in-kernel waiting (ranks in step arrive within microseconds), then the host takes over
-    arg.hred = h_red_dev;
-    allreduce = false;
-    peer = true;
-    p2pStats()[4]++;
-  } else if (allreduce) p2pStats()[5]++;
+  const RedPlan p = planReduction(arg.c, F::nred);
   hipStream_t s = computeStream();
-  const long nreal = (long)x.Stride() * x.Nspin() * x.Ncolor() * 2;
-  const int bs = 256;
-  // grid cap: 512 blocks (2 per CU) measured best on MI355X — 32x16x16x16 fp64 norm2 65 us at 4096 blocks (the completion
-  // counter / fp64 atomics of 3072 blocks serialise on one address) -> 34 us at 512; streaming axpy 5.5 -> 6.0 TB/s
-  static int cap = 0;
-  if (!cap) { const char *e = getenv("QUDA_AMD_BLAS_BLOCKS"); cap = e ? atoi(e) : 512; if (cap < 1 || cap > kMaxBlocks) cap = 512; }
-  auto grid = [&](long n) { long b = (n * arg.nseg + bs - 1) / bs; return (int)(b > cap ? cap : (b < 1 ? 1 : b)); };
-  switch (x.Precision()) {
-    case QUDA_DOUBLE_PRECISION:
-      arg.n = nreal / 2;
-      hipLaunchKernelGGL((blas_kernel<double, 2, false, F>), dim3(grid(arg.n)), dim3(bs), 0, s, arg);
-      break;
-    case QUDA_SINGLE_PRECISION:
-      arg.n = nreal / 4;
-      if (nreal % 4) errorQuda("field length %ld not a multiple of 4", nreal);
-      hipLaunchKernelGGL((blas_kernel<float, 4, false, F>), dim3(grid(arg.n)), dim3(bs), 0, s, arg);
-      break;
-    case QUDA_HALF_PRECISION:
-      if (x.Nspin() != 4 || x.Ncolor() != 3) errorQuda("16-bit blas only for fine-grid spinors");
-      arg.n = x.VolumeCB();
-      hipLaunchKernelGGL((blas_kernel<short, 24, true, F>), dim3(grid(arg.n)), dim3(bs), 0, s, arg);
-      break;
-    default: errorQuda("bad precision %d", x.Precision());
-  }
+  forShape<F::siteOnly>(x, [&](auto shape, const Extent &e) {
+    using S = decltype(shape);
+    arg.nseg = e.nseg; arg.n = e.n; arg.stride = e.stride;
+    hipLaunchKernelGGL((blas_kernel<typename S::T, S::M, S::SITE, F>), dim3(gridFor(e.n * e.nseg, 512)), dim3(256), 0, s, arg);
+  });
   HIP_CHECK(hipGetLastError());
   if (F::nred > 0 && !out) {   // deferred: the sums stay in d_red for the next kernel of the stream (DevAlpha); rank-local sums only
-    if (allreduce || peer) errorQuda("a deferred reduction cannot be a global one");
-  } else if (F::nred > 0) {
-    if (allreduce) {
-      commAllreduceDevice(d_red, F::nred, s);  // RCCL all-reduce of the rank sums, in stream order
-      HIP_CHECK(hipMemcpyAsync(h_red, d_red, F::nred * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (peer && h_red[kMaxRed - 1] == 0.0) finishAllreduceOnHost(arg.buf, arg.expect, F::nred, h_red);
-    for (int k = 0; k < F::nred; k++) out[k] = h_red[k];
-  }
+    if (p.allreduce || p.peer) errorQuda("a deferred reduction cannot be a global one");
+  } else if (F::nred > 0) finishPlan(p, arg.c, F::nred, out, s);
   const int nrd = F::rx + F::ry + F::rz + F::rw, nwr = F::wx + F::wy + F::wz + F::ww;
   if (g_acctOn) { char tag[48]; snprintf(tag, sizeof(tag), "%s prec %d", x.Nspin() == 4 ? "level 0" : "coarse", (int)x.Precision()); acct("blas_kernel", (double)(nrd + nwr) * x.RealLength() * x.Precision(), tag); }
   bytes += (unsigned long long)(nrd + nwr) * x.RealLength() * x.Precision();
@@ -902,47 +934,6 @@ bool multiSupported(const ColorSpinorField &x, int k) {
   static int off = -1;
   if (off < 0) { const char *e = getenv("QUDA_AMD_GCR_BLOCK_ORTHO"); off = (e && !atoi(e)) ? 1 : 0; }
   return !off && k >= 0 && k <= kMaxDirs && (x.Precision() == QUDA_DOUBLE_PRECISION || x.Precision() == QUDA_SINGLE_PRECISION) && x.Location() == QUDA_CUDA_FIELD_LOCATION;
-}
-struct RedPlan { bool allreduce, peer; };
-static RedPlan planReduction(RedCtl &c, int nred) {
-  if (!d_red) init();
-  RedPlan p;
-  p.allreduce = g_global_reduction && commReductionsNeeded(); p.peer = false;
-  c.red = d_red; c.part = d_part; c.count = d_count;
-  c.hred = p.allreduce ? nullptr : h_red_dev;
-  c.peerSlots = nullptr; c.peerCount = nullptr; c.nranks = 1; c.rank = 0; c.buf = 0; c.expect = 0; c.waitTicks = 0;
-  if (p.allreduce && nred <= kSlotDoubles && reduceWindowActive()) {
-    const CommGrid &cg = commGrid();
-    c.peerSlots = g_rw.d_slots; c.peerCount = g_rw.d_counts;
-    c.nranks = cg.size; c.rank = cg.rank;
-    c.buf = (int)(++g_rw.seq & 1);
-    c.expect = (g_rw.uses[c.buf] += (unsigned)cg.size);
-    c.waitTicks = 2000000ull;
-    c.hred = h_red_dev;
-    p.allreduce = false; p.peer = true;
-    p2pStats()[4]++;
-  } else if (p.allreduce) p2pStats()[5]++;
-  return p;
-}
-static void finishPlan(const RedPlan &p, const RedCtl &c, int nred, double *out, hipStream_t s) {
-  if (p.allreduce) {
-    commAllreduceDevice(d_red, nred, s);
-    HIP_CHECK(hipMemcpyAsync(h_red, d_red, nred * sizeof(double), hipMemcpyDeviceToHost, s));
-  }
-  HIP_CHECK(hipStreamSynchronize(s));
-  if (p.peer && h_red[kMaxRed - 1] == 0.0) finishAllreduceOnHost(c.buf, c.expect, nred, h_red);
-  for (int k = 0; k < nred; k++) out[k] = h_red[k];
-}
-// work-groups of the multi-field kernels.  Measured at 48^3 x 96 (fp32, k = 1..9 fields, tools/profile_mg_solve.sh with QUDA_AMD_BLAS_BLOCKS):
-// the k-field update runs at 0.43 / 0.61 / 0.69 of the HBM roofline with 512 / 1024 / 2048 work-groups (one chunk of every field per
-// thread and trip: more resident waves, not deeper loops, keep the k + 2 streams busy), the k-field dots at 0.56 / 0.59 / 0.54 (their
-// 43-value block reduction grows with the grid); the one- to four-field kernels above prefer 512 (0.72 against 0.67).
-static int multiGrid(long chunks, int dflt) {
-  static int cap = -1;
-  if (cap < 0) { const char *e = getenv("QUDA_AMD_BLAS_BLOCKS"); cap = e ? atoi(e) : 0; if (cap < 1 || cap > kMaxBlocks) cap = 0; }
-  const int c = cap ? cap : dflt;
-  const long b = (chunks + 255) / 256;
-  return (int)(b > c ? c : (b < 1 ? 1 : b));
 }
 static void fillMulti(MultiArg &a, const std::vector<ColorSpinorField *> &f, int k, const ColorSpinorField &y, const ColorSpinorField *r) {
   if (!multiSupported(y, k)) errorQuda("multi-field blas: %d fields of precision %d not supported", k, y.Precision());
@@ -956,26 +947,35 @@ static void fillMulti(MultiArg &a, const std::vector<ColorSpinorField *> &f, int
   // surplus slots of the kernel's bucket (multiple of 4 >= k): a valid field again — y itself where there is none — with a zero
   // coefficient / an ignored sum
   for (int i = k; i < kMaxDirs; i++) { a.f[i][0] = k ? a.f[0][0] : a.y[0]; a.f[i][1] = k ? a.f[0][1] : a.y[1]; }
-  a.k = k; a.nseg = y.SiteSubset() == QUDA_FULL_SITE_SUBSET ? 2 : 1;
-  const long nreal = (long)y.Stride() * y.Nspin() * y.Ncolor() * 2;
-  a.n = y.Precision() == QUDA_DOUBLE_PRECISION ? nreal / 2 : nreal / 4;
-  if (y.Precision() == QUDA_SINGLE_PRECISION && nreal % 4) errorQuda("field length %ld not a multiple of 4", nreal);
+  a.k = k;
   a.scale = 1.0; a.ar = a.ai = 0.0;
+}
+// the kernel's bucket: the first of 4, 8, 12, 16, 20 that holds k fields
+template <typename Fn> static void forBucket(int k, Fn &&fn) {
+  static_assert(kMaxDirs == 20, "the buckets below end at 20");
+  forAtLeast<4, 8, 12, 16, 20>(k, fn);
+}
+static int bucketOf(int k) { int b = 0; forBucket(k, [&](auto KB) { b = KB; }); return b; }
+// launches the instantiation pick(shape, bucket) names for y's precision and a.k fields, on at most maxBlocks work-groups
+template <typename Pick> static void launchMulti(MultiArg &a, const ColorSpinorField &y, int maxBlocks, Pick &&pick) {
+  forShape(y, [&](auto shape, const Extent &e) {
+    if constexpr (decltype(shape)::SITE) errorQuda("multi-field blas: no 16-bit kernels");
+    else forBucket(a.k, [&](auto KB) {
+      a.nseg = e.nseg; a.n = e.n;
+      hipLaunchKernelGGL(pick(shape, KB), dim3(gridFor(e.n * e.nseg, maxBlocks)), dim3(256), 0, computeStream(), a);
+    });
+  });
+  HIP_CHECK(hipGetLastError());
 }
 void multiDot(Complex *beta, Complex &yr, double &ynorm, const std::vector<ColorSpinorField *> &f, int k, const ColorSpinorField &y, const ColorSpinorField &r) {
   constexpr int NRED = 2 * kMaxDirs + 3;
   MultiArg a;
   fillMulti(a, f, k, y, &r);
-  const int KBsel = k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 12 ? 12 : (k <= 16 ? 16 : 20))), nred = 2 * KBsel + 3;   // sums of the bucket: [2 d], [2 d + 1] for its KBsel fields, then (y, r) and |y|^2
+  const int KBsel = bucketOf(k), nred = 2 * KBsel + 3;   // sums of the bucket: [2 d], [2 d + 1] for its KBsel fields, then (y, r) and |y|^2
   const RedPlan p = planReduction(a.c, nred);
-  hipStream_t s = computeStream();
-#define QA_MD(KB) { if (y.Precision() == QUDA_DOUBLE_PRECISION) hipLaunchKernelGGL((multi_dot_kernel<double, 2, KB>), dim3(multiGrid(a.n * a.nseg, 1024)), dim3(256), 0, s, a); \
-                   else hipLaunchKernelGGL((multi_dot_kernel<float, 4, KB>), dim3(multiGrid(a.n * a.nseg, 1024)), dim3(256), 0, s, a); }
-  if (k <= 4) QA_MD(4) else if (k <= 8) QA_MD(8) else if (k <= 12) QA_MD(12) else if (k <= 16) QA_MD(16) else QA_MD(20)
-#undef QA_MD
-  HIP_CHECK(hipGetLastError());
+  launchMulti(a, y, 1024, [](auto shape, auto KB) { using S = decltype(shape); return multi_dot_kernel<typename S::T, S::M, KB>; });
   double out[NRED];
-  finishPlan(p, a.c, nred, out, s);
+  finishPlan(p, a.c, nred, out, computeStream());
   for (int i = 0; i < k; i++) beta[i] = Complex(out[2 * i], out[2 * i + 1]);
   yr = Complex(out[2 * KBsel], out[2 * KBsel + 1]);
   ynorm = out[2 * KBsel + 2];
@@ -989,14 +989,9 @@ void multiCaxpyResidual(double &r2, double &y2, const Complex *c, const std::vec
   for (int i = 0; i < k; i++) { a.cr[i] = c[i].real(); a.ci[i] = c[i].imag(); }
   a.scale = scale; a.ar = a_.real(); a.ai = a_.imag();
   const RedPlan p = planReduction(a.c, 2);
-  hipStream_t s = computeStream();
-#define QA_MC(KB) { if (y.Precision() == QUDA_DOUBLE_PRECISION) hipLaunchKernelGGL((multi_caxpy_kernel<double, 2, true, KB>), dim3(multiGrid(a.n * a.nseg, 2048)), dim3(256), 0, s, a); \
-                   else hipLaunchKernelGGL((multi_caxpy_kernel<float, 4, true, KB>), dim3(multiGrid(a.n * a.nseg, 2048)), dim3(256), 0, s, a); }
-  if (k <= 4) QA_MC(4) else if (k <= 8) QA_MC(8) else if (k <= 12) QA_MC(12) else if (k <= 16) QA_MC(16) else QA_MC(20)
-#undef QA_MC
-  HIP_CHECK(hipGetLastError());
+  launchMulti(a, y, 2048, [](auto shape, auto KB) { using S = decltype(shape); return multi_caxpy_kernel<typename S::T, S::M, true, KB>; });
   double out[2];
-  finishPlan(p, a.c, 2, out, s);
+  finishPlan(p, a.c, 2, out, computeStream());
   r2 = out[0]; y2 = out[1];
   acct("multi_caxpy_kernel", (double)(k + 4) * y.RealLength() * y.Precision(), y.Nspin() == 4 ? "level 0" : "coarse");
   bytes += (unsigned long long)(k + 4) * y.RealLength() * y.Precision();
@@ -1007,12 +1002,7 @@ void multiCaxpy(const Complex *c, const std::vector<ColorSpinorField *> &f, int 
   fillMulti(a, f, k, y, nullptr);
   for (int i = 0; i < k; i++) { a.cr[i] = c[i].real(); a.ci[i] = c[i].imag(); }
   memset(&a.c, 0, sizeof(a.c));
-  hipStream_t s = computeStream();
-#define QA_MC(KB) { if (y.Precision() == QUDA_DOUBLE_PRECISION) hipLaunchKernelGGL((multi_caxpy_kernel<double, 2, false, KB>), dim3(multiGrid(a.n * a.nseg, 2048)), dim3(256), 0, s, a); \
-                   else hipLaunchKernelGGL((multi_caxpy_kernel<float, 4, false, KB>), dim3(multiGrid(a.n * a.nseg, 2048)), dim3(256), 0, s, a); }
-  if (k <= 4) QA_MC(4) else if (k <= 8) QA_MC(8) else if (k <= 12) QA_MC(12) else if (k <= 16) QA_MC(16) else QA_MC(20)
-#undef QA_MC
-  HIP_CHECK(hipGetLastError());
+  launchMulti(a, y, 2048, [](auto shape, auto KB) { using S = decltype(shape); return multi_caxpy_kernel<typename S::T, S::M, false, KB>; });
   acct("multi_caxpy_kernel", (double)(k + 2) * y.RealLength() * y.Precision(), y.Nspin() == 4 ? "level 0" : "coarse");
   bytes += (unsigned long long)(k + 2) * y.RealLength() * y.Precision();
   flops += (unsigned long long)(8 * k) * (y.RealLength() / 2);
@@ -1037,26 +1027,14 @@ void multiShiftUpdate(int k, const std::vector<ColorSpinorField *> &x, const std
       a.x[d] = segOf(*x[i]); a.p[d] = segOf(*p[i]);
       a.alpha[d] = alpha[i]; a.beta[d] = beta[i]; a.zeta[d] = zeta[i];
     }
-    a.nseg = r.SiteSubset() == QUDA_FULL_SITE_SUBSET ? 2 : 1;
-    a.stride = r.Stride();
-    const long nreal = (long)r.Stride() * r.Nspin() * r.Ncolor() * 2;
-#define QA_MS(T, M, SITE, K) hipLaunchKernelGGL((multi_shift_update_kernel<T, M, SITE, K>), dim3(multiGrid(a.n * a.nseg, 2048)), dim3(256), 0, s, a)
-#define QA_MSK(T, M, SITE) \
-  switch (kk) { case 1: QA_MS(T, M, SITE, 1); break; case 2: QA_MS(T, M, SITE, 2); break; case 3: QA_MS(T, M, SITE, 3); break; case 4: QA_MS(T, M, SITE, 4); break; \
-                case 5: QA_MS(T, M, SITE, 5); break; case 6: QA_MS(T, M, SITE, 6); break; case 7: QA_MS(T, M, SITE, 7); break; default: QA_MS(T, M, SITE, 8); break; }
-    static_assert(kShiftKB == 8, "the dispatch above lists K = 1..8");
-    switch (r.Precision()) {
-      case QUDA_DOUBLE_PRECISION: a.n = nreal / 2; QA_MSK(double, 2, false) break;
-      case QUDA_SINGLE_PRECISION:
-        if (nreal % 4) errorQuda("field length %ld not a multiple of 4", nreal);
-        a.n = nreal / 4; QA_MSK(float, 4, false) break;
-      case QUDA_HALF_PRECISION:
-        if (r.Nspin() != 4 || r.Ncolor() != 3) errorQuda("16-bit blas only for fine-grid spinors");
-        a.n = r.VolumeCB(); QA_MSK(short, 24, true) break;
-      default: errorQuda("bad precision %d", r.Precision());
-    }
-#undef QA_MSK
-#undef QA_MS
+    static_assert(kShiftKB == 8, "the dispatch below lists K = 1..8");
+    forShape(r, [&](auto shape, const Extent &e) {
+      using S = decltype(shape);
+      a.nseg = e.nseg; a.n = e.n; a.stride = e.stride;
+      forAtLeast<1, 2, 3, 4, 5, 6, 7, 8>(kk, [&](auto K) {
+        hipLaunchKernelGGL((multi_shift_update_kernel<typename S::T, S::M, S::SITE, K>), dim3(gridFor(e.n * e.nseg, 2048)), dim3(256), 0, s, a);
+      });
+    });
     HIP_CHECK(hipGetLastError());
     acct("multi_shift_update_kernel", (double)(4 * kk + 1) * r.RealLength() * r.Precision(), r.Nspin() == 4 ? "level 0" : "coarse");
     bytes += (unsigned long long)(4 * kk + 1) * r.RealLength() * r.Precision();
@@ -1154,47 +1132,24 @@ double axpyReDot(const double &a, const ColorSpinorField &x, ColorSpinorField &y
   AxpyReDotF f; f.a = a; double r[1]; launch(f, x, &y, nullptr, nullptr, r); return r[0];
 }
 
-// heavy-quark residual: sum_sites |r(x)|^2 / |x(x)|^2 — needs the site structure (reference lib/blas_cpu.cpp:311-352)
-template <typename T> __global__ void hq_kernel(const void *x, const float *xn, const void *r, const float *rn, int stride, int Vh, double *red) {
-  using real = typename Store<T>::real;
-  double acc[3] = {0, 0, 0};
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < Vh; i += gridDim.x * blockDim.x) {
-    real a[24], b[24];
-    Planar<T, 24>::load(a, x, stride, i, xn, i);
-    Planar<T, 24>::load(b, r, stride, i, rn, i);
+// heavy-quark residual: sum_sites |r(x)|^2 / |x(x)|^2 — needs the site structure (reference lib/blas_cpu.cpp:311-352), so it walks
+// fp64 and fp32 fields site by site too; y is the residual.  (|x|^2, |r|^2, sum_sites r2 / x2 with 1 where x2 = 0)
+struct HeavyQuarkF : Functor { QA_FLAGS(1, 1, 0, 0, 0, 0, 0, 0, 3)
+  static constexpr bool siteOnly = true;
+  template <typename real, int M> __device__ void operator()(real *x, real *y, real *, real *, double *r) const {
+    static_assert(M == 24, "one chunk is one site");
     double x2 = 0, r2 = 0;
 #pragma unroll
-    for (int k = 0; k < 24; k++) { x2 += (double)a[k] * a[k]; r2 += (double)b[k] * b[k]; }
-    acc[0] += x2; acc[1] += r2; acc[2] += x2 > 0.0 ? r2 / x2 : 1.0;
-  }
-  for (int k = 0; k < 3; k++) {
-    double v = acc[k];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63) == 0) atomicAdd(&red[k], v);
-  }
-}
+    for (int k = 0; k < M; k++) { x2 += (double)x[k] * x[k]; r2 += (double)y[k] * y[k]; }
+    r[0] += x2; r[1] += r2; r[2] += x2 > 0.0 ? r2 / x2 : 1.0;
+  } };
 
 double3_t HeavyQuarkResidualNorm(const ColorSpinorField &x, const ColorSpinorField &r) {
-  if (!d_red) init();
-  checkSame(x, r);
   if (x.Nspin() != 4 || x.Ncolor() != 3) errorQuda("heavy-quark residual only for fine-grid spinors");
-  hipStream_t s = computeStream();
-  HIP_CHECK(hipMemsetAsync(d_red, 0, 3 * sizeof(double), s));
-  const Seg sx = segOf(x), sr = segOf(r);
-  const int nseg = x.SiteSubset() == QUDA_FULL_SITE_SUBSET ? 2 : 1, bs = 256;
-  for (int sg = 0; sg < nseg; sg++) {
-    int nb = (x.VolumeCB() + bs - 1) / bs; if (nb > 2048) nb = 2048;
-    switch (x.Precision()) {
-      case QUDA_DOUBLE_PRECISION: hipLaunchKernelGGL((hq_kernel<double>), dim3(nb), dim3(bs), 0, s, sx.v[sg], sx.norm[sg], sr.v[sg], sr.norm[sg], x.Stride(), x.VolumeCB(), d_red); break;
-      case QUDA_SINGLE_PRECISION: hipLaunchKernelGGL((hq_kernel<float>), dim3(nb), dim3(bs), 0, s, sx.v[sg], sx.norm[sg], sr.v[sg], sr.norm[sg], x.Stride(), x.VolumeCB(), d_red); break;
-      default: hipLaunchKernelGGL((hq_kernel<short>), dim3(nb), dim3(bs), 0, s, sx.v[sg], sx.norm[sg], sr.v[sg], sr.norm[sg], x.Stride(), x.VolumeCB(), d_red); break;
-    }
-  }
-  HIP_CHECK(hipMemcpyAsync(h_red, d_red, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  double out[3] = {h_red[0], h_red[1], h_red[2]};
+  double out[3];
+  launch(HeavyQuarkF(), x, &r, nullptr, nullptr, out);
   double vol = (double)x.Volume();
-  if (g_global_reduction) { comm_allreduce(out, 3); double v[1] = {vol}; comm_allreduce(v, 1); vol = v[0]; }
+  if (g_global_reduction) { double v[1] = {vol}; comm_allreduce(v, 1); vol = v[0]; }
   return {out[0], out[1], out[2] / vol};
 }
 

@@ -5,7 +5,7 @@
 // multiCaxpy stop at 20 fields and return their sums through the host per call.  Here:
 //   eig_block_dot_kernel   c[j] = (v_j, w), j < m: a block stages a tile of w in LDS (the one read of w), wave q takes the vectors
 //                          j = q, q + 4, ... and streams the tile of v_j past it; shuffle sum over the lanes, the tiles of a block in
-//                          order, the blocks in order by the last block (completion counter, as finish_reduction of blas.hip);
+//                          order, the blocks in order by the last block (completion counter: lastBlockFinishes of reduce.h, as finish_reduction of blas.hip);
 //   eig_block_axpy_kernel  w -= sum_j c[j] v_j: the coefficients in LDS, two complex numbers of w per thread;
 //   eig_rotate_kernel      V[:, 0..k) <- V[:, 0..m) Q in place on the fp64 matrix cores (v_mfma_f64_16x16x4_f64): a block owns 32
 //                          real rows of ALL m vectors, stages them in LDS (m x 32 x 8 B <= 64 KiB), synchronises and only then writes
@@ -16,6 +16,7 @@
 
 #include "eig.h"
 #include "qa_core.h"
+#include "reduce.h"
 
 namespace quda {
 
@@ -30,7 +31,6 @@ __global__ void __launch_bounds__(256) eig_block_dot_kernel(double *const *V, in
                                                             unsigned *count, double *out) {
   __shared__ double2 sw[DOT_TILE];
   __shared__ double2 sacc[kEigMaxVectors];
-  __shared__ int isLast;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int j = threadIdx.x; j < m; j += 256) sacc[j] = make_double2(0.0, 0.0);
   for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
@@ -63,19 +63,13 @@ __global__ void __launch_bounds__(256) eig_block_dot_kernel(double *const *V, in
     __hip_atomic_store(&part[((size_t)blockIdx.x * m + j) * 2], sacc[j].x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(&part[((size_t)blockIdx.x * m + j) * 2 + 1], sacc[j].y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  // the hand-off of finish_reduction (blas.hip): write-through stores drained before the counter announces them
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) isLast = __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-  __syncthreads();
-  if (isLast) {
+  lastBlockFinishes(count, [&] {
     for (int j = threadIdx.x; j < 2 * m; j += 256) {
       double v = 0;
       for (int b = 0; b < (int)gridDim.x; b++) v += __hip_atomic_load(&part[(size_t)b * 2 * m + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       out[j] = v;
     }
-    if (threadIdx.x == 0) __hip_atomic_store(count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  });
 }
 
 // ---- w -= sum_j c[j] v_j ----

@@ -29,7 +29,7 @@ Function -> test:
   xmyz with z = y, caxpy(a, x, x), cDotProduct(x, x)    test_aliased_operands
   cDotProductNormADev + caxpyXmazDev / caxXmazDev / caxInitDev     test_device_scalars, test_device_scalars_breakdown
   multiSupported, multiDot, multiCaxpyResidual, multiCaxpy         test_multi_supported, test_multi_dot, test_multi_caxpy_residual, test_multi_caxpy
-  HeavyQuarkResidualNorm                                test_heavy_quark_residual_norm
+  HeavyQuarkResidualNorm                                test_heavy_quark_residual_norm, test_capped_grids
   axpyCGNorm, axpyZpbx, tripleCGReduction, axpyReDot, multiShiftUpdate     tests/test_cg_kernels_gpu.py
   zero, copy, caxpy / cDotProduct over vectors of fields: loops over the above, not tested here"""
 import importlib
@@ -290,11 +290,14 @@ def check_multi_supported(qa, F):
 
 
 def check_heavy_quark(qa, F):
-    """(|x|^2, |r|^2, mean over sites of r2 / x2 with a zero x site counting 1); the kernel adds with floating atomics: no bit-reproducibility"""
+    """(|x|^2, |r|^2, mean over sites of r2 / x2 with a zero x site counting 1), bit-identical when the call is repeated on the same inputs"""
     try:
         x, r = F.new(), F.new()
         xv, rv = F.read(x), F.read(r)
         got = qa.heavy_quark_residual_norm(x, r)
+        again = qa.heavy_quark_residual_norm(x, r)
+        if tuple(again) != tuple(got):
+            raise R.Mismatch("HeavyQuarkResidualNorm: sums %r, then %r from the same inputs" % (tuple(got), tuple(again)))
         sx, sr, ratio = R.heavy_quark_summands(xv, rv)
         assert np.sum(ratio == 1.0) >= 1
         recs = [R.check_sum("HeavyQuarkResidualNorm |x|^2", got[0], sx), R.check_sum("HeavyQuarkResidualNorm |r|^2", got[1], sr),
@@ -377,8 +380,8 @@ def test_large_field(qa, op):
 
 
 def test_capped_grids():
-    """tools/blas_capped_check.py in a fresh process per grid cap (the cap is read once per process): every single-field, device-scalar and
-    multi-field check on 6x6x4x2 full in all three precisions with one and with two work-groups.  The second run only starts if the first passed"""
+    """tools/blas_capped_check.py in a fresh process per grid cap (the cap is read once per process): every single-field, device-scalar,
+    multi-field and heavy-quark check on 6x6x4x2 full in all three precisions with one and with two work-groups.  The second run only starts if the first passed"""
     tool = os.path.join(ROOT, "tools", "blas_capped_check.py")
     for cap in (1, 2):
         env = dict(os.environ, QUDA_AMD_BLAS_BLOCKS=str(cap))
@@ -389,7 +392,7 @@ def test_capped_grids():
         assert r.returncode == 0, (cap, r.stdout[-3000:], r.stderr[-3000:])
         assert ("cap %d" % cap) in r.stdout
         ops = {ln.split()[1] for ln in lines}
-        missing = [op for op in SINGLE_OPS + [o + "Dev" for o in DEV_OPS] + ["multiDot", "multiCaxpyResidual", "multiCaxpy", "multiSupported"] if op not in ops]
+        missing = [op for op in SINGLE_OPS + [o + "Dev" for o in DEV_OPS] + ["multiDot", "multiCaxpyResidual", "multiCaxpy", "multiSupported", "HeavyQuarkResidualNorm"] if op not in ops]
         assert not missing, missing
         for p in PRECS:
             assert sum(1 for ln in lines if ln.split()[2] == str(p)) >= len(SINGLE_OPS), p

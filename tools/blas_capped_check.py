@@ -8,7 +8,7 @@ last group with a partly live u = 1 lane and dead u = 2, 3), two over the 1728 f
 16-bit field; two work-groups run the same loops with more than one block in the completion-counter reduction and a live group across the
 switch between the parity segments.
 
-Runs every single-field, aliased, device-scalar and multi-field check in fp64, fp32 and 16 bits, prints one
+Runs every single-field, aliased, device-scalar, multi-field and heavy-quark check in fp64, fp32 and 16 bits, prints one
     OK <op> <prec> <error> <bound>
 line per check (the comparison of the call that came closest to its bound) and exits nonzero at the first failure.
 
@@ -49,6 +49,7 @@ def main():
                 ok(op + "Dev", T.check_dev(qa, fields(36), op, breakdown=True))
             T.check_multi_supported(qa, fields(37))
             ok("multiSupported", ("", 0.0, 0.0))
+            ok("HeavyQuarkResidualNorm", T.check_heavy_quark(qa, fields(130)))
             if prec == 2:
                 continue
             for k in T.MULTI_K:
