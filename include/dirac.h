@@ -1,7 +1,7 @@
 // dirac.h — operator classes behind the reference's C++ surface (include/dirac_quda.h:15-164, :449-617,
 // :868-1032): same class names, method names, argument meaning and flop accounting, so in-library callers
 // (solvers, multigrid, QKXTM-style drivers) read as they do against the reference.  The implementations
-// launch the CDNA4 kernels of dslash.hip / coarse.hip.
+// launch the CDNA4 kernels of dslash.hip / fine_block.hip / hop.hip / coarse.hip.
 #pragma once
 
 #include "dslash.h"

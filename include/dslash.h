@@ -75,7 +75,7 @@ void freeFineBlockDots();
 // in_other); it is filled here (pack + grouped exchange) before the launch
 // out[site][chirality][6][6] complex fp32 = A + i a s (s = +-1 for the upper / lower chirality) of one parity, or its inverse
 int haloWireFormat();
-// direct Galerkin construction, step 1 (dslash.hip galerkin_uv_kernel): UV(x) = coef U_dir(x) V(x + dhat(dir)) for all columns of the transfer
+// direct Galerkin construction, step 1 (hop.hip galerkin_uv_kernel): UV(x) = coef U_dir(x) V(x + dhat(dir)) for all columns of the transfer
 // matrix at once, V / UV in its aggregate-major order (4^4 aggregates); and the same for the site-diagonal term A + i a g5 of twisted clover
 void galerkinUV(float *UV, const float *V, const GaugeField &U, int dir, double coef, const int *block_to_fine, const int *fine_to_block, int aggOffset, int nAgg, int blockVol, int nvec, bool classMajor = false);   // classMajor: sites of a row ordered by (block coordinate along mu, the other three)   // aggregates [aggOffset, aggOffset + nAgg) -> UV[0 .. nAgg)
 void galerkinLocalUV(float *L, const float *V, const CloverField &C, double a, const int *block_to_fine, int aggOffset, int nAgg, int blockVol, int nvec);
@@ -98,7 +98,7 @@ void applySite(ColorSpinorField &out, const ColorSpinorField &in, SiteOp op, dou
 void ndegTwistCoefficients(double kappa, double mu, double epsilon, bool inverse, bool dagger, double &a, double &b, double &d);
 void applyNdegTwist(ColorSpinorField &out, const ColorSpinorField &in, double a, double b, double d, const ColorSpinorField *x = nullptr, double k = 0.0);
 
-// launch geometry of the stencil kernel (block size, XCD mapping, block order); see launchDslash
+// launch geometry of the stencil kernel (block size, XCD mapping, block order); see dslash_launch.h
 struct DslashTune {
   int block = 0;       // threads per block; 0: the largest of 256/192/128/64 that divides an (x, y) plane
   int remap = 1;       // XCD-aware block mapping on / off
@@ -109,9 +109,8 @@ struct DslashTune {
   int nxz = 0, tz = 0, tt = 0;   // plane-tiled order: XCDs along z, tile extents in z and t (0: automatic)
   int lds_pad = 0;     // dynamic LDS per block, only to cap the blocks per CU (measurement aid)
   int ygroups = -1;    // plane-tiled order: groups of plane chunks walked one after the other (0 / 1 none, -1 automatic: fp64 fields whose three-slice set per XCD exceeds the L2, n explicit)
-  // peer-store halo launch: face packing folded into the site threads (-1: environment QUDA_AMD_P2P_FOLD, default OFF; the path is compiled out unless dslash.hip is built with -DQA_P2P_FOLD=1: it measured slower than pack blocks), start delay of
-  // the site blocks and raised issue priority of the pack waves (measurement aids)
-  int p2p_fold = -1, site_delay = 0, pack_prio = 0;
+  // peer-store halo launch: start delay of the site blocks and raised issue priority of the pack waves (measurement aids)
+  int site_delay = 0, pack_prio = 0;
   // wire format of the peer-store ghost zones: 0 flag-in-data {word, flag, word, flag} vectors, 1 self-validating 16-byte atoms {3 words, flag} = one
   // 128-byte line per fp64 face site, -1 automatic (atoms between devices, flag-in-data where ranks share one); QUDA_AMD_HALO_FORMAT=ll|atom; must be
   // the same on every rank

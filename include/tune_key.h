@@ -2,7 +2,7 @@
  * tune_key.h — identification of the most recently launched kernel, quoted by the error messages of util_quda.h.
  * Counterpart of the reference's include/tune_key.h (struct layout is ABI: getLastTuneKey() returns it by value, and objects
  * built against the reference header call it from errorQuda).  This library has no autotuner; the key names the last stencil
- * launch geometry (csrc/dslash.hip) instead of a tune-cache entry.
+ * launch geometry (csrc/dslash_launch.cpp) instead of a tune-cache entry.
  */
 #ifndef _TUNE_KEY_H
 #define _TUNE_KEY_H

@@ -2,7 +2,7 @@
 // loadTuneCache at start-up, written by saveTuneCache when entries were added; TuneKey = (volume, kernel name, aux), TuneParam = block /
 // grid / shared bytes / aux int4 / time / comment).
 //
-// What is cached here.  The launch geometry of the stencil is a closed-form function of the lattice (dslash.hip launchDslash), but four
+// What is cached here.  The launch geometry of the stencil is a closed-form function of the lattice (dslash_launch.cpp dslashBlockOrder), but four
 // knobs have a best value that flips with volume, precision and partitioning — measured in rounds 2 and 3: the cache policy of the
 // 16-bit link loads (+13 % at 32^4, -6 % at 48^3 x 96), non-temporal output stores (+5 % from 2^18 sites up, -5 % on the 8-GPU
 // sub-lattice), the y groups of the plane-tiled order (fp64 at 48^3 x 96) and the block size.  Heuristics stand in for them; with tuning

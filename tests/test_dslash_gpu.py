@@ -233,7 +233,9 @@ def test_prepare_and_reconstruct_element_wise(qa, oracle, matpc):
 def test_block_orders_on_odd_shapes(qa, oracle, X):
     """Every block order of the stencil is a re-numbering of the work-groups and must not change a single site: plane-tiled XCD
     order, y groups (explicit counts and the automatic choice), the boundary-first order of partitioned launches and the legacy slab
-    order, on lattices whose planes / slabs divide differently (non-cubic, 3 x 2^k extents), against the oracle."""
+    order (also with an explicit slab thickness: accepted on 32 x 8 x 16 x 16, falls back on 16 x 16 x 8 x 24) and the plain round-robin order,
+    on lattices whose planes / slabs divide differently (non-cubic, 3 x 2^k extents), against the oracle.  The non-temporal store and link
+    instantiations (for 16-bit fields "link_aux" = 2 selects the latter) must not change a site either."""
     gauge, spinor, _ = oracle.make_fields(list(X), clover=False)
     nh = spinor.size // 2
     kappa, mu = 0.1, 0.01
@@ -247,8 +249,9 @@ def test_block_orders_on_odd_shapes(qa, oracle, X):
         for prec in (8, 2):
             _load_fields(qa, gauge, None, X, kappa, mu, prec, 18)
             ip = qa.invert_param(qa.QUDA_TWISTED_MASS_DSLASH, kappa, mu, +1, "ee", 0, cuda_prec=prec)
-            for setting in ({}, {"ygroups": 2}, {"ygroups": 3}, {"ygroups": 0}, {"tiled": 0}, {"tiled": 1, "tt": 2}, {"nxz": 4}, {"nxz": 2}, {"block": 64}, {"block": 128, "ygroups": 2}):
-                for k, v in dict(block=0, tiled=-1, nxz=0, tz=0, tt=0, ygroups=-1).items():
+            for setting in ({}, {"ygroups": 2}, {"ygroups": 3}, {"ygroups": 0}, {"tiled": 0}, {"tiled": 1, "tt": 2}, {"nxz": 4}, {"nxz": 2}, {"block": 64}, {"block": 128, "ygroups": 2},
+                            {"remap": 0}, {"tiled": 0, "order": 2}, {"store_aux": 2}, {"link_aux": 2}):
+                for k, v in dict(block=0, tiled=-1, nxz=0, tz=0, tt=0, ygroups=-1, remap=1, order=1, store_aux=-1, link_aux=-1).items():
                     L.qudaAmdSetDslashTune(k.encode(), v)
                 for k, v in setting.items():
                     L.qudaAmdSetDslashTune(k.encode(), v)
@@ -261,7 +264,7 @@ def test_block_orders_on_odd_shapes(qa, oracle, X):
                 _load_fields(qa, gauge, None, X, kappa, mu, prec, 18)
     finally:
         L.qudaAmdSetPartitionMask(0)
-        for k, v in dict(block=0, tiled=-1, nxz=0, tz=0, tt=0, ygroups=-1).items():
+        for k, v in dict(block=0, tiled=-1, nxz=0, tz=0, tt=0, ygroups=-1, remap=1, order=1, store_aux=-1, link_aux=-1).items():
             L.qudaAmdSetDslashTune(k.encode(), v)
 
 
@@ -485,7 +488,7 @@ def test_missing_neighbour_face_is_an_error_not_a_hang():
 
 @pytest.mark.parametrize("forced_failure", [False, True])
 def test_peer_store_halo_is_verified_on_first_use(forced_failure):
-    """The first partitioned application of every precision runs through both transports and compares (csrc/dslash.hip); a
+    """The first partitioned application of every precision runs through both transports and compares (csrc/dslash.hip launchDslash, csrc/dslash_launch.cpp verifyPeerStoreHalo); a
     failed comparison (forced here through the test hook) drops every rank back to the staged transport, results stay right."""
     import subprocess
     import sys

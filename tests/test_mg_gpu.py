@@ -657,7 +657,7 @@ def test_lockstep_bicgstab_variants_agree():
 
 
 def test_opt_in_xy_tile_of_the_multi_rhs_stencil():
-    """QUDA_AMD_BLOCK_FINE_XYTILE=1 (dslash.hip fine_block_kernel<8, 0, 1>: the x / y neighbour panels of an 8 x 4 tile staged in LDS; measured slower, off by
+    """QUDA_AMD_BLOCK_FINE_XYTILE=1 (fine_block.hip fine_block_kernel<8, 0, 1>: the x / y neighbour panels of an 8 x 4 tile staged in LDS; measured slower, off by
     default) stays correct: every right-hand side against the host tm_mat on lattices the tiles cover, unpartitioned and under partition masks whose x / y
     faces come out of the ghost zone.  The switch is read once per process, hence a child process (tools/fine_block_xy_check.py)."""
     import os

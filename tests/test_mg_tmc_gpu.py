@@ -234,7 +234,7 @@ def test_matdagmat_through_the_c_abi(qa, oracle, dslash):
 @pytest.mark.parametrize("mask", [0, 15, 6], ids=["unpartitioned", "self-neighbour-xyzt", "self-neighbour-yz"])
 @pytest.mark.parametrize("dslash", ["tm", "tmc"])
 def test_multi_rhs_fine_stencil_against_the_oracle(qa, oracle, dslash, mask):
-    """The 8/16/24/32-right-hand-side stencil of the lockstep null-vector solves (csrc/dslash.hip fine_block_kernel; twisted clover:
+    """The 8/16/24/32-right-hand-side stencil of the lockstep null-vector solves (csrc/fine_block.hip fine_block_kernel; twisted clover:
     the dense A + i a g5 site matrices of cloverTwistDense in its epilogue) applied to a batch, every right-hand side against the
     host tm_mat / tmc_mat (fp32 device arithmetic: 2e-5 of the largest element); and the hierarchy's own record that the level-0 null
     vectors came from the lockstep solve on that stencil (null_method 1), the coarse ones from the MFMA operator (2).

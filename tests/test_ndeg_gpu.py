@@ -182,12 +182,12 @@ def test_block_orders_do_not_change_the_doublet(qa, oracle):
     X = (16, 16, 8, 24)
     gauge, src, want = _seeded_fields(oracle, X)
     L = qa.lib()
-    reset = dict(block=0, tiled=-1, nxz=0, tz=0, tt=0, ygroups=-1, ndeg_fused=-1)
+    reset = dict(block=0, tiled=-1, nxz=0, tz=0, tt=0, ygroups=-1, ndeg_fused=-1, store_aux=-1, link_aux=-1)
     try:
         for prec in (8, 2):
             _load_gauge(qa, gauge, X, prec, 18)
             for fused in (1, 0):
-                for setting in ({}, {"tiled": 0}, {"ygroups": 2}, {"block": 128}):
+                for setting in ({}, {"tiled": 0}, {"ygroups": 2}, {"block": 128}, {"store_aux": 2}, {"link_aux": 2}):
                     for k, v in reset.items():
                         L.qudaAmdSetDslashTune(k.encode(), v)
                     L.qudaAmdSetDslashTune(b"ndeg_fused", fused)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: tools/build_variant.sh <name> <-D flags ...>  ->  quda-qkxtm-multigrid_amd/lib/libquda_<name>.so: the library with the stencil file
-# recompiled under the given macros (A/B timing of cache policies: QUDA_AMD_LIBRARY=<that file> python bench.py ...)
+# (dslash.hip only: fine_block.hip and hop.hip come from build/ as they are) recompiled under the given macros (A/B timing of cache policies: QUDA_AMD_LIBRARY=<that file> python bench.py ...)
 set -e
 name=$1; shift
 cd "$(dirname "$0")/../quda-qkxtm-multigrid_amd"

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Seconds per application of the 8-right-hand-side fine operator (csrc/dslash.hip fine_block_kernel<8>: two parity launches = M on
+"""Seconds per application of the 8-right-hand-side fine operator (csrc/fine_block.hip fine_block_kernel<8>: two parity launches = M on
 8 vectors), its HBM fraction on the algorithmic bytes (576/8 + 96 + 96 + 96 = 360 B per site and right-hand side), twisted mass and
 twisted clover.  QUDA_AMD_BLOCK_FINE_TILE=0 selects the linear site mapping for comparison."""
 import importlib

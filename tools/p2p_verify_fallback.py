@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""First-use verification of the peer-store halo (csrc/dslash.hip): with QUDA_AMD_P2P_VERIFY_FAIL=1 the check is made to fail, the
+"""First-use verification of the peer-store halo (csrc/dslash_launch.cpp verifyPeerStoreHalo): with QUDA_AMD_P2P_VERIFY_FAIL=1 the check is made to fail, the
 library must drop back to the staged transport and keep producing the right answer; without it the transport stays 1."""
 import importlib
 import os

@@ -22,7 +22,7 @@ src_h = np.random.default_rng(1).random(Vh * 24)
 out = []
 pmask = int(sys.argv[3]) if len(sys.argv) > 3 else 0b1110
 # optional 4th argument: stencil tuning variants "key=value[+key=value...],..." measured alternately in this one process (A/B on the
-# same box and clock state), e.g. "p2p_fold=1,p2p_fold=0"; 5th: rounds
+# same box and clock state), e.g. "edge_first=1,edge_first=0"; 5th: rounds
 variants = [v for v in (sys.argv[4].split(",") if len(sys.argv) > 4 else [""])]
 rounds = int(sys.argv[5]) if len(sys.argv) > 5 else 1
 for mask in (0, pmask):
