@@ -201,4 +201,31 @@ void su3ExpIQ(int n, const double *h_q, double *h_out);
 void plaquette(const GaugeField &U, double plq[3]);
 void saveGaugeQDP(const GaugeField &U, void *const h_gauge[4], QudaPrecision cpu_prec);
 
+// ---- gauge molecular dynamics (gauge_md.hip) ----
+// The conjugate momentum of the links: ten fp64 per link in the reference's MILC order of a reconstruct-10 field,
+// [site (even sites, then odd)][mu][10], on the device exactly as on the host
+class MomField {
+ public:
+  LatticeGeom geom;
+  size_t bytes;
+  double *data;
+  explicit MomField(const LatticeGeom &g);   // zeroed
+  ~MomField();
+  void zero();
+  void load(const void *h_mom);
+  void save(void *h_mom) const;
+};
+constexpr int kGaugeForceMaxLength = 8;    // links per path (plaquette 3, rectangle and chair 5, the Luescher-Weisz set fits)
+constexpr int kGaugeForceMaxPaths = 64;    // paths per direction (Wilson 6, tree-level Symanzik 24, Luescher-Weisz 48)
+// mom <- TA(mom - eb3 U V), V the coefficient-weighted sum of the path products (reference lib/gauge_force.cu:62-142); the direct
+// gather on an unpartitioned lattice, the transport formulation on a partitioned one or under QUDA_AMD_GAUGE_FORCE_TRANSPORT=1
+void gaugeForce(MomField &mom, const GaugeField &U, double eb3, int ***path, const int *length, const double *coeff, int num_paths, int max_length);
+bool gaugeForceUsesTransport();
+// exp(dt A) U (exact) or its eighth-order Taylor form, conj_mom: with the complex conjugate of A; the new links in host QDP order
+void updateGaugeLinks(void *const h_out[4], const GaugeField &U, const MomField &mom, double dt, bool conj_mom, bool exact);
+// the links projected onto SU(3), in host QDP order; returns the global number of links with max |U^dag U - 1| > tol
+long projectSU3Links(void *const h_out[4], const GaugeField &U, double tol);
+// sum over links of tr(A^dag A)/2 - 4, global, in a fixed order
+double momAction(const MomField &mom);
+
 }  // namespace quda

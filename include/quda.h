@@ -176,6 +176,15 @@ void plaqQuda(double plaq[3]);                             /* ref quda.h:964; li
 void performAPEnStep(unsigned int nSteps, double alpha);   /* ref quda.h:971; lib/interface_quda.cpp:5565: APE-smear the resident spatial links into the library's smeared field */
 void performSTOUTnStep(unsigned int nSteps, double rho);   /* ref quda.h:978; lib/interface_quda.cpp:5640: stout-smear the resident spatial links into the library's smeared field */
 double qChargeCuda(void);                                  /* ref quda.h:983; lib/interface_quda.cpp:5940: topological charge of the smeared field if one is resident, else of the resident links */
+/* gauge molecular dynamics (lib/gauge_force.cu, gauge_update_quda.cu, momentum.cu).  Host links: QUDA_QDP_GAUGE_ORDER; host momenta: ten reals
+   per link, [site (even, odd)][mu][Re A01, Im A01, Re A02, Im A02, Re A12, Im A12, Im A00, Im A11, Im A22, 0]; fp64.  Paths: 0..3 forwards in
+   x, y, z, t, 7 - d backwards in d, at most 8 links each.  New resident links rebuild the precise, sloppy and preconditioner copies and drop
+   the smeared field; a resident clover term and multigrid hierarchy are the caller's to rebuild. */
+int computeGaugeForceQuda(void *mom, void *sitelink, int ***input_path_buf, int *path_length, double *loop_coeff, int num_paths, int max_length,
+                          double dt, QudaGaugeParam *qudaGaugeParam);  /* ref quda.h:778; lib/interface_quda.cpp:3799: mom <- TA(mom - dt U V), V the weighted sum of the path products */
+void updateGaugeFieldQuda(void *gauge, void *momentum, double dt, int conj_mom, int exact, QudaGaugeParam *param);  /* ref quda.h:793; lib/interface_quda.cpp:5081: U <- exp(dt A) U, exact or to eighth order */
+void projectSU3Quda(void *gauge_h, double tol, QudaGaugeParam *param);  /* ref quda.h:815; lib/interface_quda.cpp:5187: every link onto SU(3); a link off by more than tol is an error */
+double momActionQuda(void *momentum, QudaGaugeParam *param);  /* ref quda.h:825; lib/interface_quda.cpp:5310: sum over links of tr(A^dag A)/2 - 4 */
 void loadCloverQuda(void *h_clover, void *h_clovinv, QudaInvertParam *inv_param); /* ref quda.h:607; interface_quda.cpp:730 */
 void freeCloverQuda(void);                                 /* ref quda.h:613 */
 

@@ -22,6 +22,7 @@ QUDA_HALF_PRECISION, QUDA_SINGLE_PRECISION, QUDA_DOUBLE_PRECISION = 2, 4, 8
 QUDA_RECONSTRUCT_NO, QUDA_RECONSTRUCT_12, QUDA_RECONSTRUCT_8 = 18, 12, 8
 QUDA_WILSON_LINKS = 0
 QUDA_QDP_GAUGE_ORDER = 5
+QUDA_MILC_GAUGE_ORDER = 8
 QUDA_ANTI_PERIODIC_T, QUDA_PERIODIC_T = -1, 1
 QUDA_GAUGE_FIXED_NO = 0
 QUDA_WILSON_DSLASH, QUDA_TWISTED_MASS_DSLASH, QUDA_TWISTED_CLOVER_DSLASH = 0, 7, 8
@@ -108,7 +109,8 @@ class QudaMultigridParam(C.Structure):
 # every extern "C" symbol include/quda.h and include/quda_amd_ext.h declare
 QUDA_H_SYMBOLS = ["setVerbosityQuda", "initCommsGridQuda", "initQudaDevice", "initQudaMemory", "initQuda", "endQuda",
                   "newQudaGaugeParam", "newQudaInvertParam", "newQudaMultigridParam", "printQudaGaugeParam", "printQudaInvertParam",
-                  "printQudaMultigridParam", "loadGaugeQuda", "freeGaugeQuda", "performSTOUTnStep", "qChargeCuda", "loadCloverQuda", "freeCloverQuda", "invertQuda", "invertMultiSrcQuda", "invertMultiShiftQuda",
+                  "printQudaMultigridParam", "loadGaugeQuda", "freeGaugeQuda", "performSTOUTnStep", "qChargeCuda", "computeGaugeForceQuda", "updateGaugeFieldQuda", "projectSU3Quda", "momActionQuda",
+                  "loadCloverQuda", "freeCloverQuda", "invertQuda", "invertMultiSrcQuda", "invertMultiShiftQuda",
                   "newMultigridQuda", "destroyMultigridQuda", "dslashQuda", "cloverQuda", "MatQuda", "MatDagMatQuda", "openMagma",
                   "closeMagma"]
 EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLoad", "qudaAmdSpinorSave", "qudaAmdSpinorCopy",
@@ -309,6 +311,14 @@ def lib():
         L.qudaAmdSu3ExpIQ.restype = None
         L.saveGaugeQuda.argtypes = [_p, C.POINTER(QudaGaugeParam)]
         L.qudaAmdSaveSmearedGauge.argtypes = [C.POINTER(_p), _i]
+        L.computeGaugeForceQuda.argtypes = [_p, _p, C.POINTER(C.POINTER(C.POINTER(_i))), C.POINTER(_i), C.POINTER(_d), _i, _i, _d, C.POINTER(QudaGaugeParam)]
+        L.computeGaugeForceQuda.restype = _i
+        L.updateGaugeFieldQuda.argtypes = [_p, _p, _d, _i, _i, C.POINTER(QudaGaugeParam)]
+        L.updateGaugeFieldQuda.restype = None
+        L.projectSU3Quda.argtypes = [_p, _d, C.POINTER(QudaGaugeParam)]
+        L.projectSU3Quda.restype = None
+        L.momActionQuda.argtypes = [_p, C.POINTER(QudaGaugeParam)]
+        L.momActionQuda.restype = _d
         L.qudaAmdGaussianSmear.argtypes = [_p, _p, C.POINTER(_p), _i, _d]
         L.qudaAmdCalcMGPropagators.argtypes = [_p, _p, C.POINTER(_p), C.POINTER(QudaInvertParam), C.POINTER(QudaAmdSourceParam)]
         L.qudaAmdTwopMomenta.argtypes = [_i, C.POINTER(_i), _i]
@@ -685,6 +695,75 @@ def save_gauge(gp):
     ptr = (_p * 4)(*[_vp(out[d]) for d in range(4)])
     lib().saveGaugeQuda(C.cast(ptr, _p), C.byref(gp))
     return out
+
+
+def _md_param(gp, **flags):
+    """a copy of gp with the residency flags of the molecular-dynamics calls set (all 0 unless named)"""
+    q = QudaGaugeParam.from_buffer_copy(gp)
+    for name in ("overwrite_mom", "use_resident_gauge", "use_resident_mom", "make_resident_gauge", "make_resident_mom",
+                 "return_result_gauge", "return_result_mom"):
+        setattr(q, name, int(bool(flags.pop(name, 0))))
+    if flags:
+        raise TypeError("unknown flags %s" % sorted(flags))
+    return q
+
+
+def _qdp_ptrs(gauge):
+    return C.cast((_p * 4)(*[_vp(gauge[d]) for d in range(4)]), _p)
+
+
+def gauge_force(gp, paths, coeff, eb3, gauge=None, mom=None, overwrite=False, make_resident_gauge=False, make_resident_mom=False,
+                return_mom=True, max_length=None):
+    """computeGaugeForceQuda: mom <- TA(mom - eb3 U V).  paths[mu][i] is the i-th path (a list of steps 0..7) of direction mu, coeff[i]
+    its coefficient.  gauge: (4, V*18) host QDP links, None: the resident links.  mom: (V, 4, 10) host momentum, None: the resident
+    momentum (or, with overwrite, none at all).  Returns the new momentum unless return_mom is False"""
+    n = len(coeff)
+    lengths = [len(paths[0][i]) for i in range(n)]
+    maxlen = max(lengths + [1])
+    rows = [[(_i * maxlen)(*[int(s) for s in paths[mu][i]]) for i in range(n)] for mu in range(4)]
+    per_dir = [(C.POINTER(_i) * max(n, 1))(*[C.cast(r, C.POINTER(_i)) for r in rows[mu]]) for mu in range(4)]
+    buf = (C.POINTER(C.POINTER(_i)) * 4)(*[C.cast(a, C.POINTER(C.POINTER(_i))) for a in per_dir])
+    V = int(np.prod([gp.X[d] for d in range(4)]))
+    use_res_mom = mom is None and not overwrite
+    out = np.zeros((V, 4, 10)) if mom is None else np.ascontiguousarray(mom, dtype=np.float64).reshape(V, 4, 10).copy()
+    q = _md_param(gp, overwrite_mom=overwrite, use_resident_gauge=gauge is None, use_resident_mom=use_res_mom,
+                  make_resident_gauge=make_resident_gauge, make_resident_mom=make_resident_mom, return_result_mom=return_mom)
+    if gauge is not None:
+        gauge = [np.ascontiguousarray(gauge[d], dtype=np.float64) for d in range(4)]
+    lib().computeGaugeForceQuda(_vp(out), _qdp_ptrs(gauge) if gauge is not None else None, buf, (_i * max(n, 1))(*lengths),
+                                (_d * max(n, 1))(*[float(c) for c in coeff]), n, int(max_length if max_length is not None else maxlen),
+                                float(eb3), C.byref(q))
+    return out if return_mom else None
+
+
+def update_gauge(gp, dt, gauge=None, mom=None, conj_mom=False, exact=True, make_resident_gauge=False, make_resident_mom=False,
+                 return_gauge=True):
+    """updateGaugeFieldQuda: U <- exp(dt A) U (exact) or its eighth-order Taylor form.  gauge / mom None: the resident fields.
+    Returns the new links, (4, V*18) host QDP order, unless return_gauge is False"""
+    V = int(np.prod([gp.X[d] for d in range(4)]))
+    out = np.zeros((4, V * 18)) if gauge is None else np.array([np.asarray(gauge[d], dtype=np.float64) for d in range(4)]).reshape(4, V * 18)
+    m = None if mom is None else np.ascontiguousarray(mom, dtype=np.float64)
+    q = _md_param(gp, use_resident_gauge=gauge is None, use_resident_mom=mom is None, make_resident_gauge=make_resident_gauge,
+                  make_resident_mom=make_resident_mom, return_result_gauge=return_gauge)
+    lib().updateGaugeFieldQuda(_qdp_ptrs(out), _vp(m), float(dt), int(bool(conj_mom)), int(bool(exact)), C.byref(q))
+    return out if return_gauge else None
+
+
+def mom_action(gp, mom=None, make_resident_mom=False):
+    """momActionQuda: sum over links of tr(A^dag A)/2 - 4 of the host momentum (V, 4, 10), None: of the resident momentum"""
+    m = None if mom is None else np.ascontiguousarray(mom, dtype=np.float64)
+    q = _md_param(gp, use_resident_mom=mom is None, make_resident_mom=make_resident_mom)
+    return float(lib().momActionQuda(_vp(m), C.byref(q)))
+
+
+def project_su3(gp, tol, gauge=None, make_resident_gauge=False, return_gauge=True):
+    """projectSU3Quda: every link projected onto SU(3); a link further than tol from unitary afterwards is an error.  gauge None:
+    the resident links.  Returns the projected links, (4, V*18), unless return_gauge is False"""
+    V = int(np.prod([gp.X[d] for d in range(4)]))
+    out = np.zeros((4, V * 18)) if gauge is None else np.array([np.asarray(gauge[d], dtype=np.float64) for d in range(4)]).reshape(4, V * 18)
+    q = _md_param(gp, use_resident_gauge=gauge is None, make_resident_gauge=make_resident_gauge, return_result_gauge=return_gauge)
+    lib().projectSU3Quda(_qdp_ptrs(out), float(tol), C.byref(q))
+    return out if return_gauge else None
 
 
 def save_smeared_gauge(local_volume, lexicographic=False):

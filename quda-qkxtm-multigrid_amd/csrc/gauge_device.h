@@ -1,0 +1,195 @@
+// gauge_device.h — the 3x3 colour-matrix device code that fields.hip (clover construction, smearing, plaquette, topological charge) and
+// gauge_md.hip (gauge force, link update, SU(3) projection) share: the matrix type and its products, the resident-link loader,
+// matrix fields with their load/store, the polar SU(3) projection and exp(iQ); and the host helpers of the transport formulation.
+#pragma once
+
+#include "fields.h"
+#include "device_io.h"
+
+namespace quda {
+
+// ---- 3x3 complex matrices in fp64 and the gather of a resident link ----
+struct M3 { double re[9], im[9]; };
+__device__ __forceinline__ void m3_mul(M3 &c, const M3 &a, const M3 &b) {
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      double r = 0, m = 0;
+#pragma unroll
+      for (int k = 0; k < 3; k++) { r += a.re[i * 3 + k] * b.re[k * 3 + j] - a.im[i * 3 + k] * b.im[k * 3 + j]; m += a.re[i * 3 + k] * b.im[k * 3 + j] + a.im[i * 3 + k] * b.re[k * 3 + j]; }
+      c.re[i * 3 + j] = r; c.im[i * 3 + j] = m;
+    }
+}
+__device__ __forceinline__ void m3_dag(M3 &c, const M3 &a) {
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) { c.re[i * 3 + j] = a.re[j * 3 + i]; c.im[i * 3 + j] = -a.im[j * 3 + i]; }
+}
+struct GaugeView { const char *data; size_t link_bytes; int stride; int X[4]; int tsign, tsign_bwd; };
+// U_mu at the (possibly out-of-range, wrapped) coordinates x: the forward link stored at its own site
+template <typename T, int R> __device__ __forceinline__ void load_link(M3 &U, const GaugeView &g, int mu, const int *xin) {
+  using real = typename Store<T>::real;
+  int x[4];
+#pragma unroll
+  for (int d = 0; d < 4; d++) { x[d] = xin[d]; if (x[d] < 0) x[d] += g.X[d]; if (x[d] >= g.X[d]) x[d] -= g.X[d]; }
+  const int par = (x[0] + x[1] + x[2] + x[3]) & 1;
+  const int idx = (((x[3] * g.X[2] + x[2]) * g.X[1] + x[1]) * g.X[0] + x[0]) >> 1;
+  real u[18];
+  // the host links carry the anti-periodic sign on the last time slice; recon-12 stores rows 0,1 as given and has to put the
+  // sign back on the reconstructed third row (in the plaquette the two boundary links of a leaf then cancel their signs)
+  const real sign = (R != 18 && mu == 3 && x[3] == g.X[3] - 1) ? (real)g.tsign : (real)1;   // (recon-8: u0 of the reconstruction)
+  Link<T, R>::load(u, g.data + ((size_t)par * 8 + 2 * mu) * g.link_bytes, g.stride, idx, sign);
+#pragma unroll
+  for (int k = 0; k < 9; k++) { U.re[k] = u[2 * k]; U.im[k] = u[2 * k + 1]; }
+}
+
+// ---- a 3x3 matrix per site: planar fp64, 24 reals per site (18 used), both parities ----
+struct MatField { double *p; int Vh; __host__ __device__ double *par(int q) const { return p + (size_t)q * 24 * Vh; } };
+__device__ __forceinline__ void mf_load(M3 &m, const MatField &f, int par, int idx) {
+  double v[24];
+  Planar<double, 24>::load(v, f.par(par), f.Vh, idx, nullptr, idx);
+#pragma unroll
+  for (int k = 0; k < 9; k++) { m.re[k] = v[2 * k]; m.im[k] = v[2 * k + 1]; }
+}
+__device__ __forceinline__ void mf_store(const M3 &m, const MatField &f, int par, int idx) {
+  double v[24];
+#pragma unroll
+  for (int k = 0; k < 9; k++) { v[2 * k] = m.re[k]; v[2 * k + 1] = m.im[k]; }
+#pragma unroll
+  for (int k = 18; k < 24; k++) v[k] = 0;
+  Planar<double, 24>::store(v, f.par(par), f.Vh, idx, nullptr, idx);
+}
+// stored matrix `slot` (2 mu: U_mu(x); 2 mu + 1: U_mu(x - mu)^dag) of site (par, idx) at time coordinate t
+template <typename T, int R> __device__ __forceinline__ void load_w(M3 &U, const GaugeView &g, int par, int idx, int slot, int t) {
+  using real = typename Store<T>::real;
+  real sign = 1;
+  if (R != 18 && (slot >> 1) == 3) sign = (slot & 1) ? (t == 0 ? (real)g.tsign_bwd : (real)1) : (t == g.X[3] - 1 ? (real)g.tsign : (real)1);
+  real u[18];
+  Link<T, R>::load(u, g.data + ((size_t)par * 8 + slot) * g.link_bytes, g.stride, idx, sign);
+#pragma unroll
+  for (int k = 0; k < 9; k++) { U.re[k] = u[2 * k]; U.im[k] = u[2 * k + 1]; }
+}
+__device__ __forceinline__ int time_coord(const GaugeView &g, int idx) { return idx / ((g.X[0] >> 1) * g.X[1] * g.X[2]); }
+
+// ---- determinant, inverse, polar projection onto SU(3) ----
+__device__ __forceinline__ void m3_det(double &dr, double &di, const M3 &a) {
+  dr = 0; di = 0;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+    const double mr = (a.re[3 + c1] * a.re[6 + c2] - a.im[3 + c1] * a.im[6 + c2]) - (a.re[3 + c2] * a.re[6 + c1] - a.im[3 + c2] * a.im[6 + c1]);
+    const double mi = (a.re[3 + c1] * a.im[6 + c2] + a.im[3 + c1] * a.re[6 + c2]) - (a.re[3 + c2] * a.im[6 + c1] + a.im[3 + c2] * a.re[6 + c1]);
+    dr += a.re[c] * mr - a.im[c] * mi;
+    di += a.re[c] * mi + a.im[c] * mr;
+  }
+}
+__device__ __forceinline__ void m3_inverse(M3 &o, const M3 &a) {   // adjugate / determinant
+  double dr, di;
+  m3_det(dr, di, a);
+  const double n = dr * dr + di * di, ir = dr / n, ii = -di / n;
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      const int r1 = (j + 1) % 3, r2 = (j + 2) % 3, c1 = (i + 1) % 3, c2 = (i + 2) % 3;
+      const double cr = (a.re[3 * r1 + c1] * a.re[3 * r2 + c2] - a.im[3 * r1 + c1] * a.im[3 * r2 + c2]) - (a.re[3 * r1 + c2] * a.re[3 * r2 + c1] - a.im[3 * r1 + c2] * a.im[3 * r2 + c1]);
+      const double ci = (a.re[3 * r1 + c1] * a.im[3 * r2 + c2] + a.im[3 * r1 + c1] * a.re[3 * r2 + c2]) - (a.re[3 * r1 + c2] * a.im[3 * r2 + c1] + a.im[3 * r1 + c2] * a.re[3 * r2 + c1]);
+      o.re[3 * i + j] = cr * ir - ci * ii;
+      o.im[3 * i + j] = cr * ii + ci * ir;
+    }
+}
+// su3_project.cuh polarSu3: Newton iteration X <- (X + X^-dag)/2 until X is unitary to tol (elementwise, X vs (X^-1)^dag),
+// then the phase of the determinant is divided out.  Capped at 100 sweeps (the reference loops until the test passes).
+__device__ __forceinline__ void polar_su3(M3 &m, double tol) {
+  M3 out = m, inv;
+  m3_inverse(inv, out);
+  for (int sweep = 0; sweep < 100; sweep++) {
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        out.re[3 * i + j] = 0.5 * (out.re[3 * i + j] + inv.re[3 * j + i]);
+        out.im[3 * i + j] = 0.5 * (out.im[3 * i + j] - inv.im[3 * j + i]);
+      }
+    m3_inverse(inv, out);
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) bad = bad || fabs(out.re[3 * i + j] - inv.re[3 * j + i]) > tol || fabs(out.im[3 * i + j] + inv.im[3 * j + i]) > tol;
+    if (!bad) break;
+  }
+  double dr, di;
+  m3_det(dr, di, out);
+  const double mod = pow(dr * dr + di * di, 1.0 / 6.0), angle = atan2(di, dr) / -3.0;
+  const double cr = cos(angle) / mod, ci = sin(angle) / mod;
+#pragma unroll
+  for (int k = 0; k < 9; k++) { m.re[k] = out.re[k] * cr - out.im[k] * ci; m.im[k] = out.re[k] * ci + out.im[k] * cr; }
+}
+
+// ---- exp(iQ) of a traceless Hermitian Q ----
+// exp(iQ) = f0 + f1 Q + f2 Q^2 of a traceless Hermitian Q by the Cayley-Hamilton form (eqs. 14-34 of the paper):
+//   c0 = tr Q^3 / 3 = det Q,  c1 = tr Q^2 / 2,  c0max = 2 (c1/3)^(3/2),  theta = acos(c0 / c0max),
+//   u = sqrt(c1/3) cos(theta/3),  w = sqrt(c1) sin(theta/3),  f_j = h_j / (9 u^2 - w^2).
+// c0 < 0 goes through f_j(-c0) = (-1)^j conj f_j(c0), so theta/3 <= pi/6 and 9 u^2 - w^2 = c1 (3 cos^2 - sin^2) >= 2 c1 > 0.
+// The only other divisions are by c0max and by w in xi0 = sin(w)/w: xi0 takes its even Taylor polynomial for |w| <= 0.05, and
+// below c1 = 1e-60 (c0max would underflow towards 0; c1 = 0 means Q = 0) the result is 1 + iQ, exact to c1/2: the unit matrix
+// for Q = 0.  Rounding can push c0 / c0max past 1 at the degenerate point; it is clamped.
+__device__ __forceinline__ void su3_exp_iq(M3 &E, const M3 &Q) {
+  double c1 = 0;
+#pragma unroll
+  for (int k = 0; k < 9; k++) c1 += Q.re[k] * Q.re[k] + Q.im[k] * Q.im[k];   // tr Q^2 = sum |Q_ij|^2 for Hermitian Q
+  c1 *= 0.5;
+  if (c1 < 1e-60) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) { E.re[k] = -Q.im[k]; E.im[k] = Q.re[k]; }
+    E.re[0] += 1.0; E.re[4] += 1.0; E.re[8] += 1.0;
+    return;
+  }
+  M3 Q2;
+  m3_mul(Q2, Q, Q);
+  double c0 = 0;   // tr(Q Q^2) = sum_ij Q_ij (Q^2)_ji, real
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) c0 += Q.re[3 * i + j] * Q2.re[3 * j + i] - Q.im[3 * i + j] * Q2.im[3 * j + i];
+  c0 *= 1.0 / 3.0;
+  const bool neg = c0 < 0;
+  c0 = fabs(c0);
+  const double c13 = c1 * (1.0 / 3.0), c0max = 2.0 * c13 * sqrt(c13);   // > 0: c1 >= 1e-60
+  const double theta3 = acos(fmin(c0 / c0max, 1.0)) * (1.0 / 3.0);
+  const double u = sqrt(c13) * cos(theta3), w = sqrt(c1) * sin(theta3);
+  const double u2 = u * u, w2 = w * w, cw = cos(w);
+  const double xi0 = fabs(w) <= 0.05 ? 1.0 - w2 * (1.0 / 6.0) * (1.0 - w2 * (1.0 / 20.0) * (1.0 - w2 * (1.0 / 42.0))) : sin(w) / w;
+  double s2u, c2u, su, cu;
+  sincos(2.0 * u, &s2u, &c2u);
+  sincos(u, &su, &cu);
+  // h_j = a_j e^{2iu} + e^{-iu} (b_j + i d_j)
+  const double b0 = 8.0 * u2 * cw, d0 = 2.0 * u * (3.0 * u2 + w2) * xi0;
+  const double b1 = -2.0 * u * cw, d1 = (3.0 * u2 - w2) * xi0;
+  const double b2 = -cw, d2 = -3.0 * u * xi0;
+  const double a0 = u2 - w2, a1 = 2.0 * u, inv = 1.0 / (9.0 * u2 - w2);
+  double fr[3], fi[3];
+  fr[0] = (a0 * c2u + cu * b0 + su * d0) * inv; fi[0] = (a0 * s2u + cu * d0 - su * b0) * inv;
+  fr[1] = (a1 * c2u + cu * b1 + su * d1) * inv; fi[1] = (a1 * s2u + cu * d1 - su * b1) * inv;
+  fr[2] = (c2u + cu * b2 + su * d2) * inv;      fi[2] = (s2u + cu * d2 - su * b2) * inv;
+  if (neg) { fi[0] = -fi[0]; fr[1] = -fr[1]; fi[2] = -fi[2]; }
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+    E.re[k] = fr[1] * Q.re[k] - fi[1] * Q.im[k] + fr[2] * Q2.re[k] - fi[2] * Q2.im[k];
+    E.im[k] = fr[1] * Q.im[k] + fi[1] * Q.re[k] + fr[2] * Q2.im[k] + fi[2] * Q2.re[k];
+  }
+  E.re[0] += fr[0]; E.re[4] += fr[0]; E.re[8] += fr[0];
+  E.im[0] += fi[0]; E.im[4] += fi[0]; E.im[8] += fi[0];
+}
+
+// host side (fields.hip): the view of a resident field, its forward links of one direction as a matrix field, out(x) = in(x + dhat(dir))
+// (dir = 2 mu: forward, 2 mu + 1: backward; ghost-aware), and out (+)= op(A) op(B) site by site
+GaugeView viewOf(const GaugeField &U);
+void extractForwardLinks(MatField F, const GaugeField &U, int mu);
+void shiftField(MatField out, MatField in, const LatticeGeom &geom, int dir);
+void mfMul(MatField out, MatField A, MatField B, int dagA, int dagB, int accumulate);
+
+}  // namespace quda

@@ -1,0 +1,433 @@
+// gauge_md.hip — the gauge sector of molecular dynamics: the path-product force, the link update, the momentum action and the
+// SU(3) projection (reference lib/gauge_force.cu, lib/gauge_update_quda.cu, lib/momentum.cu, lib/interface_quda.cpp:5187-5247).
+//
+// Momentum: one traceless anti-Hermitian 3x3 matrix A per link, ten reals in host and device memory alike,
+//   [site (even sites, then odd)][mu][Re A01, Im A01, Re A02, Im A02, Re A12, Im A12, Im A00, Im A11, Im A22, 0]
+// (the reference's MILC order of a reconstruct-10 field, include/gauge_field_order.h:424-456); A10 = -conj A01 and so on, and the
+// diagonal has no real part.  The device field keeps the host order, so upload and download are plain copies.
+//
+// Paths (lib/gauge_force.cu:51-52): directions 0..3 step forwards in x, y, z, t, 7 - d steps backwards in d.  For every site x and
+// direction mu the walk starts at x + mu and multiplies the links it meets from left to right, a forward step d from y with U_d(y)
+// and on to y + d, a backward step on to y - d with U_d(y - d)^dag (:86-129).  V_mu(x) = sum_i coeff_i product_i skips the paths of
+// coefficient 0, and A_mu(x) <- TA(A_mu(x) - eb3 U_mu(x) V_mu(x)) with TA(M) = (M - M^dag)/2 - tr(M - M^dag)/6 (:131-140).
+//
+// Two formulations of V, as for the clover term (clover_from_gauge_kernel / cloverFromGaugeDecomposed):
+//   direct     one thread per (site, parity, direction) gathers the links of every path itself; unpartitioned lattices only;
+//   transport  the partial products R_k(y) = L_k(y) R_{k+1}(y') are matrix fields carried one hop at a time by the ghost-aware
+//              shift, so no rank ever needs more than its nearest neighbours' links; any partition mask or rank grid.
+// Both end in force_epilogue, which multiplies with U_mu(x), takes TA, accumulates into the momentum and packs it.
+#include "gauge_device.h"
+#include "qkxtm_internal.h"
+
+#include <cstring>
+#include <vector>
+
+namespace quda {
+
+void comm_allreduce(double *data, int n);   // comm.cpp
+
+// the path table of one force call.  Every index into it is the same in all lanes of a wave (direction from blockIdx.y, the loop
+// counters), and it lives in constant memory, so the steps, lengths and coefficients arrive through scalar loads
+struct ForceTable {
+  int num_paths;
+  int length[kGaugeForceMaxPaths];
+  double coeff[kGaugeForceMaxPaths];
+  signed char step[4][kGaugeForceMaxPaths][kGaugeForceMaxLength];
+};
+__constant__ ForceTable c_force;
+
+MomField::MomField(const LatticeGeom &g) : geom(g), bytes((size_t)g.V * 40 * sizeof(double)), data(nullptr) {
+  HIP_CHECK(qaMalloc((void **)&data, bytes));
+  zero();
+}
+MomField::~MomField() { if (data) (void)hipFree(data); }
+void MomField::zero() { HIP_CHECK(hipMemsetAsync(data, 0, bytes, computeStream())); }
+void MomField::load(const void *h_mom) {
+  HIP_CHECK(hipMemcpyAsync(data, h_mom, bytes, hipMemcpyHostToDevice, computeStream()));
+  HIP_CHECK(hipStreamSynchronize(computeStream()));
+}
+void MomField::save(void *h_mom) const {
+  HIP_CHECK(hipMemcpyAsync(h_mom, data, bytes, hipMemcpyDeviceToHost, computeStream()));
+  HIP_CHECK(hipStreamSynchronize(computeStream()));
+}
+
+// y[dir] += s (s = +1 or -1), wrapped into the lattice after every single step: a path may cross the same boundary more than once
+// (extent 2), which one wrap of the summed displacement would miss.  dir is wave-uniform; y stays in registers (static indices)
+__device__ __forceinline__ void hop(int *y, int dir, int s, const GaugeView &g) {
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+    if (k == dir) {
+      const int v = y[k] + s;
+      y[k] = v < 0 ? v + g.X[k] : (v >= g.X[k] ? v - g.X[k] : v);
+    }
+}
+// A <- A B in place, row by row: a row of the product needs that row of A only, so six reals of scratch registers are enough
+__device__ __forceinline__ void m3_mul_right(M3 &a, const M3 &b) {
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    double r[3], m[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      r[j] = 0; m[j] = 0;
+#pragma unroll
+      for (int k = 0; k < 3; k++) { r[j] += a.re[i * 3 + k] * b.re[k * 3 + j] - a.im[i * 3 + k] * b.im[k * 3 + j]; m[j] += a.re[i * 3 + k] * b.im[k * 3 + j] + a.im[i * 3 + k] * b.re[k * 3 + j]; }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; j++) { a.re[i * 3 + j] = r[j]; a.im[i * 3 + j] = m[j]; }
+  }
+}
+// A <- A B^dag in place
+__device__ __forceinline__ void m3_mul_right_dag(M3 &a, const M3 &b) {
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    double r[3], m[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      r[j] = 0; m[j] = 0;
+#pragma unroll
+      for (int k = 0; k < 3; k++) { r[j] += a.re[i * 3 + k] * b.re[j * 3 + k] + a.im[i * 3 + k] * b.im[j * 3 + k]; m[j] += a.im[i * 3 + k] * b.re[j * 3 + k] - a.re[i * 3 + k] * b.im[j * 3 + k]; }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; j++) { a.re[i * 3 + j] = r[j]; a.im[i * 3 + j] = m[j]; }
+  }
+}
+
+// m (the ten reals of A_mu(x)) <- TA(A - eb3 U V), lib/gauge_force.cu:131-140.  The stored A is anti-Hermitian already, so only its
+// trace and the product W = U V go through the projection:
+//   off-diagonal  A_ij - eb3 (W_ij - conj W_ji)/2,   diagonal  d_i - (d_0 + d_1 + d_2)/3 with d_i = Im A_ii - eb3 Im W_ii
+__device__ __forceinline__ void force_epilogue(double *m, const M3 &U, const M3 &V, double eb3) {
+  M3 W;
+  m3_mul(W, U, V);
+  double a[10];
+#pragma unroll
+  for (int k = 0; k < 10; k++) a[k] = m[k];
+  const double h = 0.5 * eb3;
+  a[0] -= h * (W.re[1] - W.re[3]); a[1] -= h * (W.im[1] + W.im[3]);
+  a[2] -= h * (W.re[2] - W.re[6]); a[3] -= h * (W.im[2] + W.im[6]);
+  a[4] -= h * (W.re[5] - W.re[7]); a[5] -= h * (W.im[5] + W.im[7]);
+  const double d0 = a[6] - eb3 * W.im[0], d1 = a[7] - eb3 * W.im[4], d2 = a[8] - eb3 * W.im[8];
+  const double tr = (d0 + d1 + d2) * (1.0 / 3.0);
+  a[6] = d0 - tr; a[7] = d1 - tr; a[8] = d2 - tr; a[9] = 0;
+#pragma unroll
+  for (int k = 0; k < 10; k++) m[k] = a[k];
+}
+
+// ---- direct gather: one thread per (site, parity), the direction in blockIdx.y.  Running product, loaded link and accumulator are
+// the three live matrices (54 fp64 = 108 VGPRs); arithmetic in fp64 whatever the link precision ----
+template <typename T, int R>
+__global__ void __launch_bounds__(128) gauge_force_kernel(double *mom, GaugeView g, double eb3, int Vh) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= 2 * Vh) return;
+  const int mu = blockIdx.y;
+  const int parity = gid >= Vh, idx = gid - parity * Vh;
+  int x[4];
+  {
+    const int Xh = g.X[0] >> 1;
+    int l = idx;
+    const int xh = l % Xh; l /= Xh;
+    x[1] = l % g.X[1]; l /= g.X[1];
+    x[2] = l % g.X[2]; x[3] = l / g.X[2];
+    x[0] = 2 * xh + ((x[1] + x[2] + x[3] + parity) & 1);
+  }
+  M3 V;
+#pragma unroll
+  for (int k = 0; k < 9; k++) V.re[k] = V.im[k] = 0;
+  const int n = c_force.num_paths;
+  for (int i = 0; i < n; i++) {
+    const double c = c_force.coeff[i];
+    if (c == 0) continue;
+    int y[4] = {x[0], x[1], x[2], x[3]};
+    hop(y, mu, +1, g);
+    M3 A, B;
+    const int len = c_force.length[i];
+    for (int j = 0; j < len; j++) {
+      const int d = c_force.step[mu][i][j];
+      const bool fwd = d < 4;
+      const int dir = fwd ? d : 7 - d;
+      if (!fwd) hop(y, dir, -1, g);
+      load_link<T, R>(B, g, dir, y);
+      if (j == 0) {
+        if (fwd) A = B; else m3_dag(A, B);
+      } else {
+        if (fwd) m3_mul_right(A, B); else m3_mul_right_dag(A, B);
+      }
+      if (fwd) hop(y, dir, +1, g);
+    }
+    if (len > 0) {
+#pragma unroll
+      for (int k = 0; k < 9; k++) { V.re[k] += c * A.re[k]; V.im[k] += c * A.im[k]; }
+    }
+  }
+  M3 U;
+  load_link<T, R>(U, g, mu, x);
+  force_epilogue(mom + ((size_t)gid * 4 + mu) * 10, U, V, eb3);
+}
+
+// ---- transport ----
+__global__ void mf_identity_kernel(MatField out, int Vh) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= 2 * Vh) return;
+  const int par = gid >= Vh, idx = gid - par * Vh;
+  M3 m;
+#pragma unroll
+  for (int k = 0; k < 9; k++) { m.re[k] = (k % 4 == 0) ? 1.0 : 0.0; m.im[k] = 0; }
+  mf_store(m, out, par, idx);
+}
+// acc += c in
+__global__ void mf_axpy_kernel(MatField acc, double c, MatField in, int Vh) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= 2 * Vh) return;
+  const int par = gid >= Vh, idx = gid - par * Vh;
+  M3 a, b;
+  mf_load(a, acc, par, idx); mf_load(b, in, par, idx);
+#pragma unroll
+  for (int k = 0; k < 9; k++) { a.re[k] += c * b.re[k]; a.im[k] += c * b.im[k]; }
+  mf_store(a, acc, par, idx);
+}
+__global__ void __launch_bounds__(128) force_epilogue_kernel(double *mom, MatField U, MatField V, int mu, double eb3, int Vh) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= 2 * Vh) return;
+  const int par = gid >= Vh, idx = gid - par * Vh;
+  M3 u, v;
+  mf_load(u, U, par, idx); mf_load(v, V, par, idx);
+  force_epilogue(mom + ((size_t)gid * 4 + mu) * 10, u, v, eb3);
+}
+
+// R_{n+1} = 1; a forward step d gives R_k(y) = U_d(y) R_{k+1}(y + d), a backward step R_k(y) = [U_d^dag R_{k+1}](y - d); the path's
+// product seen from x is R_1(x + mu).  One shift and one product per link, every shift a single hop.
+static void gaugeForceTransport(MomField &mom, const GaugeField &U, double eb3, int ***path, const int *length, const double *coeff, int num_paths) {
+  const LatticeGeom &geom = U.geom;
+  const int Vh = geom.Vh, bs = 128, nb = (2 * Vh + bs - 1) / bs;
+  const size_t fieldDoubles = (size_t)2 * 24 * Vh;
+  double *pool = nullptr;
+  HIP_CHECK(qaMalloc((void **)&pool, 8 * fieldDoubles * sizeof(double)));
+  MatField F[4], Rf, T, acc, Vf;
+  for (int i = 0; i < 4; i++) F[i] = {pool + i * fieldDoubles, Vh};
+  Rf = {pool + 4 * fieldDoubles, Vh}; T = {pool + 5 * fieldDoubles, Vh}; acc = {pool + 6 * fieldDoubles, Vh}; Vf = {pool + 7 * fieldDoubles, Vh};
+  hipStream_t s = computeStream();
+  for (int mu = 0; mu < 4; mu++) extractForwardLinks(F[mu], U, mu);
+  for (int mu = 0; mu < 4; mu++) {
+    HIP_CHECK(hipMemsetAsync(acc.p, 0, fieldDoubles * sizeof(double), s));
+    for (int i = 0; i < num_paths; i++) {
+      if (coeff[i] == 0 || length[i] <= 0) continue;
+      hipLaunchKernelGGL(mf_identity_kernel, dim3(nb), dim3(bs), 0, s, Rf, Vh);
+      HIP_CHECK(hipGetLastError());
+      for (int j = length[i] - 1; j >= 0; j--) {
+        const int d = path[mu][i][j];
+        if (d < 4) {
+          shiftField(T, Rf, geom, 2 * d);         // R(y + d)
+          mfMul(Rf, F[d], T, 0, 0, 0);
+        } else {
+          mfMul(T, F[7 - d], Rf, 1, 0, 0);        // U_d(y)^dag R(y), wanted at y + d
+          shiftField(Rf, T, geom, 2 * (7 - d) + 1);
+        }
+      }
+      hipLaunchKernelGGL(mf_axpy_kernel, dim3(nb), dim3(bs), 0, s, acc, coeff[i], Rf, Vh);
+      HIP_CHECK(hipGetLastError());
+    }
+    shiftField(Vf, acc, geom, 2 * mu);
+    hipLaunchKernelGGL(force_epilogue_kernel, dim3(nb), dim3(bs), 0, s, mom.data, F[mu], Vf, mu, eb3, Vh);
+    HIP_CHECK(hipGetLastError());
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+  HIP_CHECK(hipFree(pool));
+}
+
+bool gaugeForceUsesTransport() {
+  bool transport = false;
+  for (int d = 0; d < 4; d++) transport = transport || commGrid().partitioned(d);
+  { const char *e = getenv("QUDA_AMD_GAUGE_FORCE_TRANSPORT"); if (e && atoi(e)) transport = true; }  // force the transport formulation (tests, timing)
+  return transport;
+}
+
+void gaugeForce(MomField &mom, const GaugeField &U, double eb3, int ***path, const int *length, const double *coeff, int num_paths, int max_length) {
+  if (!(U.geom == mom.geom)) errorQuda("gauge and momentum geometry differ");
+  if (max_length > kGaugeForceMaxLength) errorQuda("gauge force: max_length = %d exceeds the cap of %d links per path", max_length, kGaugeForceMaxLength);
+  if (num_paths < 0 || num_paths > kGaugeForceMaxPaths) errorQuda("gauge force: num_paths = %d outside 0..%d", num_paths, kGaugeForceMaxPaths);
+  for (int i = 0; i < num_paths; i++) {
+    if (length[i] < 0 || length[i] > max_length) errorQuda("gauge force: path %d has length %d, max_length = %d", i, length[i], max_length);
+    for (int mu = 0; mu < 4; mu++)
+      for (int j = 0; j < length[i]; j++)
+        if (path[mu][i][j] < 0 || path[mu][i][j] > 7) errorQuda("gauge force: path %d of direction %d, step %d = %d outside 0..7", i, mu, j, path[mu][i][j]);
+  }
+  if (gaugeForceUsesTransport()) { gaugeForceTransport(mom, U, eb3, path, length, coeff, num_paths); return; }
+  ForceTable tab;
+  memset(&tab, 0, sizeof(tab));
+  tab.num_paths = num_paths;
+  for (int i = 0; i < num_paths; i++) {
+    tab.length[i] = length[i]; tab.coeff[i] = coeff[i];
+    for (int mu = 0; mu < 4; mu++)
+      for (int j = 0; j < length[i]; j++) tab.step[mu][i][j] = (signed char)path[mu][i][j];
+  }
+  hipStream_t s = computeStream();
+  HIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_force), &tab, sizeof(tab), 0, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipStreamSynchronize(s));   // tab is a stack object
+  const GaugeView g = viewOf(U);
+  const int Vh = U.geom.Vh, bs = 128, nb = (2 * Vh + bs - 1) / bs;
+  const bool r12 = U.reconstruct == QUDA_RECONSTRUCT_12, r8 = U.reconstruct == QUDA_RECONSTRUCT_8;
+#define QA_GF(T) \
+  if (r12) hipLaunchKernelGGL((gauge_force_kernel<T, 12>), dim3(nb, 4), dim3(bs), 0, s, mom.data, g, eb3, Vh); \
+  else if (r8) hipLaunchKernelGGL((gauge_force_kernel<T, 8>), dim3(nb, 4), dim3(bs), 0, s, mom.data, g, eb3, Vh); \
+  else hipLaunchKernelGGL((gauge_force_kernel<T, 18>), dim3(nb, 4), dim3(bs), 0, s, mom.data, g, eb3, Vh);
+  switch (U.precision) {
+    case QUDA_DOUBLE_PRECISION: QA_GF(double) break;
+    case QUDA_SINGLE_PRECISION: QA_GF(float) break;
+    case QUDA_HALF_PRECISION: QA_GF(short) break;
+    default: errorQuda("bad gauge precision %d", U.precision);
+  }
+#undef QA_GF
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// ---- link update (lib/gauge_update_quda.cu:109-152): the trace of A removed; exact: U <- exp(dt A) U through su3_exp_iq with
+// Q = -i dt A; else the eighth-order Horner form R = (dt/r) A R + U, r = 8..1, from R = U.  conj_mom: the complex conjugate of A,
+// entry by entry (not A^dag).  One thread per (site, parity) of direction mu; the new links leave in host QDP order ----
+__global__ void __launch_bounds__(128) gauge_update_kernel(double *qdp, MatField F, const double *mom, int mu, double dt, int conj_mom, int exact, int Vh) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= 2 * Vh) return;
+  const int par = gid >= Vh, idx = gid - par * Vh;
+  M3 u, a, r;
+  mf_load(u, F, par, idx);
+  const double *m = mom + ((size_t)gid * 4 + mu) * 10;
+  const double cs = conj_mom ? -1.0 : 1.0;   // conj A: the imaginary parts change sign
+  const double tr = (m[6] + m[7] + m[8]) * (1.0 / 3.0);
+  a.re[0] = a.re[4] = a.re[8] = 0;
+  a.im[0] = cs * (m[6] - tr); a.im[4] = cs * (m[7] - tr); a.im[8] = cs * (m[8] - tr);
+  a.re[1] = m[0]; a.im[1] = cs * m[1]; a.re[3] = -m[0]; a.im[3] = cs * m[1];
+  a.re[2] = m[2]; a.im[2] = cs * m[3]; a.re[6] = -m[2]; a.im[6] = cs * m[3];
+  a.re[5] = m[4]; a.im[5] = cs * m[5]; a.re[7] = -m[4]; a.im[7] = cs * m[5];
+  if (exact) {
+    M3 q, e;
+#pragma unroll
+    for (int k = 0; k < 9; k++) { q.re[k] = dt * a.im[k]; q.im[k] = -(dt * a.re[k]); }
+    su3_exp_iq(e, q);
+    m3_mul(r, e, u);
+  } else {
+    r = u;
+    for (int o = 8; o >= 1; o--) {
+      M3 t;
+      m3_mul(t, a, r);
+      const double f = dt / o;
+#pragma unroll
+      for (int k = 0; k < 9; k++) { r.re[k] = f * t.re[k] + u.re[k]; r.im[k] = f * t.im[k] + u.im[k]; }
+    }
+  }
+  double *o = qdp + (size_t)gid * 18;
+#pragma unroll
+  for (int k = 0; k < 9; k++) { o[2 * k] = r.re[k]; o[2 * k + 1] = r.im[k]; }
+}
+
+// ---- SU(3) projection (lib/interface_quda.cpp:5187-5247): the polar projection and determinant phase of the APE step (polar_su3)
+// on every link; a link whose max |U^dag U - 1| still exceeds tol afterwards counts as a failure.  The anti-periodic sign of the
+// time links on the last time slice (det -1) is taken off before the projection and put back after it ----
+__global__ void __launch_bounds__(128) project_su3_kernel(double *qdp, int *failures, MatField F, int sign_t, double tol, int Vh) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= 2 * Vh) return;
+  const int par = gid >= Vh, idx = gid - par * Vh;
+  M3 u, d, p;
+  mf_load(u, F, par, idx);
+  const double sg = (sign_t >= 0 && idx >= sign_t) ? -1.0 : 1.0;   // sign_t: first checkerboard index of the last time slice (t runs slowest), or -1
+#pragma unroll
+  for (int k = 0; k < 9; k++) { u.re[k] *= sg; u.im[k] *= sg; }
+  polar_su3(u, 1e-15);
+  m3_dag(d, u);
+  m3_mul(p, d, u);
+  p.re[0] -= 1.0; p.re[4] -= 1.0; p.re[8] -= 1.0;
+  double dev = 0;
+#pragma unroll
+  for (int k = 0; k < 9; k++) dev = fmax(dev, fmax(fabs(p.re[k]), fabs(p.im[k])));
+  if (!(dev <= tol)) atomicAdd(failures, 1);
+  double *o = qdp + (size_t)gid * 18;
+#pragma unroll
+  for (int k = 0; k < 9; k++) { o[2 * k] = sg * u.re[k]; o[2 * k + 1] = sg * u.im[k]; }
+}
+
+// one direction at a time: forward links -> kernel -> host QDP array
+template <typename Launch> static void linksToHost(void *const h_out[4], const GaugeField &U, Launch launch) {
+  const LatticeGeom &geom = U.geom;
+  const int Vh = geom.Vh;
+  double *pool = nullptr;
+  HIP_CHECK(qaMalloc((void **)&pool, (size_t)2 * 24 * Vh * sizeof(double)));
+  MatField F = {pool, Vh};
+  double *stage = (double *)stagingBuffer((size_t)geom.V * 18 * sizeof(double));
+  hipStream_t s = computeStream();
+  for (int mu = 0; mu < 4; mu++) {
+    extractForwardLinks(F, U, mu);
+    launch(stage, F, mu);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(h_out[mu], stage, (size_t)geom.V * 18 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  HIP_CHECK(hipFree(pool));
+}
+
+void updateGaugeLinks(void *const h_out[4], const GaugeField &U, const MomField &mom, double dt, bool conj_mom, bool exact) {
+  if (!(U.geom == mom.geom)) errorQuda("gauge and momentum geometry differ");
+  const int Vh = U.geom.Vh, bs = 128, nb = (2 * Vh + bs - 1) / bs;
+  linksToHost(h_out, U, [&](double *stage, MatField F, int mu) {
+    hipLaunchKernelGGL(gauge_update_kernel, dim3(nb), dim3(bs), 0, computeStream(), stage, F, mom.data, mu, dt, conj_mom ? 1 : 0, exact ? 1 : 0, Vh);
+  });
+}
+
+long projectSU3Links(void *const h_out[4], const GaugeField &U, double tol) {
+  const int Vh = U.geom.Vh, bs = 128, nb = (2 * Vh + bs - 1) / bs;
+  int *d_fail = nullptr;
+  HIP_CHECK(qaMalloc((void **)&d_fail, sizeof(int)));
+  HIP_CHECK(hipMemsetAsync(d_fail, 0, sizeof(int), computeStream()));
+  const bool last_t = commGrid().coords[3] == commGrid().dims[3] - 1;
+  const int sliceCB = Vh / U.geom.X[3];
+  linksToHost(h_out, U, [&](double *stage, MatField F, int mu) {
+    const int sign_t = (mu == 3 && U.t_boundary == QUDA_ANTI_PERIODIC_T && last_t) ? sliceCB * (U.geom.X[3] - 1) : -1;
+    hipLaunchKernelGGL(project_su3_kernel, dim3(nb), dim3(bs), 0, computeStream(), stage, d_fail, F, sign_t, tol, Vh);
+  });
+  int fail = 0;
+  HIP_CHECK(hipMemcpy(&fail, d_fail, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipFree(d_fail));
+  double f = fail;
+  comm_allreduce(&f, 1);
+  return (long)f;
+}
+
+// ---- momentum action (lib/momentum.cu:31-48): sum over links of sum_{j<6} v_j^2 + (1/2) sum_{j=6..8} v_j^2 - 4 = tr(A^dag A)/2 - 4.
+// One thread per link, one partial per block in a fixed order (lanes by shuffle, the four waves through LDS), the partials added
+// in block order by the host as in topologicalCharge: the same field gives the same bits ----
+__global__ void __launch_bounds__(256) mom_action_kernel(double *partial, const double *mom, long nLinks) {
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  double v = 0;
+  if (gid < nLinks) {
+    const double *m = mom + gid * 10;
+    double off = 0, dia = 0;
+#pragma unroll
+    for (int j = 0; j < 6; j++) off += m[j] * m[j];
+#pragma unroll
+    for (int j = 6; j < 9; j++) dia += m[j] * m[j];
+    v = (off + 0.5 * dia) - 4.0;
+  }
+  __shared__ double lds[4];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+
+double momAction(const MomField &mom) {
+  const long nLinks = (long)mom.geom.V * 4;
+  const int bs = 256, nb = (int)((nLinks + bs - 1) / bs);
+  double *d_partial = nullptr;
+  HIP_CHECK(qaMalloc((void **)&d_partial, (size_t)nb * sizeof(double)));
+  hipStream_t s = computeStream();
+  hipLaunchKernelGGL(mom_action_kernel, dim3(nb), dim3(bs), 0, s, d_partial, mom.data, nLinks);
+  HIP_CHECK(hipGetLastError());
+  std::vector<double> partial(nb);
+  HIP_CHECK(hipMemcpyAsync(partial.data(), d_partial, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  HIP_CHECK(hipFree(d_partial));
+  double S = 0;
+  for (int b = 0; b < nb; b++) S += partial[b];
+  comm_allreduce(&S, 1);
+  return S;
+}
+
+}  // namespace quda

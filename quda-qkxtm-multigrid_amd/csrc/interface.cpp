@@ -25,6 +25,7 @@ void freeBlockTables();
 
 // resident fields (reference lib/interface_quda.cpp:119-145)
 GaugeField *gaugePrecise = nullptr, *gaugeSloppy = nullptr, *gaugePrecondition = nullptr, *gaugeSmeared = nullptr;
+MomField *momResident = nullptr;   // the momentum of gauge molecular dynamics (reference lib/interface_quda.cpp:128)
 CloverField *cloverPrecise = nullptr, *cloverSloppy = nullptr, *cloverPrecondition = nullptr;
 static bool g_initialized = false, g_comms_initialized = false;
 static int g_device = -1;
@@ -296,10 +297,14 @@ static void checkGaugeParam(const QudaGaugeParam *p) {
   if (p->type != QUDA_WILSON_LINKS) errorQuda("Parameter type = %d: only Wilson (SU(3)) links are on this path", p->type);
 }
 
-void loadGaugeQuda(void *h_gauge, QudaGaugeParam *param) {
-  if (!g_initialized) errorQuda("QUDA not initialized");
-  checkGaugeParam(param);
-  freeGaugeQuda();
+static void freeResidentLinks() {
+  delete gaugePrecise; delete gaugeSloppy; delete gaugePrecondition; delete gaugeSmeared;   // reference :1001-1008
+  gaugePrecise = gaugeSloppy = gaugePrecondition = gaugeSmeared = nullptr;
+}
+
+// the precise, sloppy and preconditioner copies from host QDP links; whatever was resident (a smeared field included) goes
+static void loadResidentLinks(void *h_gauge, QudaGaugeParam *param) {
+  freeResidentLinks();
   g_geom = LatticeGeom(param->X);
   g_gauge_param = *param;
   void **links = (void **)h_gauge;
@@ -324,9 +329,17 @@ void loadGaugeQuda(void *h_gauge, QudaGaugeParam *param) {
   param->gaugeGiB = gib;
 }
 
+void loadGaugeQuda(void *h_gauge, QudaGaugeParam *param) {
+  if (!g_initialized) errorQuda("QUDA not initialized");
+  checkGaugeParam(param);
+  freeGaugeQuda();
+  loadResidentLinks(h_gauge, param);
+}
+
 void freeGaugeQuda(void) {
-  delete gaugePrecise; delete gaugeSloppy; delete gaugePrecondition; delete gaugeSmeared;   // reference :1001-1008
-  gaugePrecise = gaugeSloppy = gaugePrecondition = gaugeSmeared = nullptr;
+  freeResidentLinks();
+  delete momResident;
+  momResident = nullptr;
 }
 
 // reference lib/interface_quda.cpp:694-728: the resident (precise) links back to the host in the order of param
@@ -420,6 +433,129 @@ void qudaAmdSaveSmearedGauge(void **h_gauge, int lexicographic) {
       memcpy(dst + iv * 18, &eo[d][((size_t)parity * g.Vh + iv / 2) * 18], 18 * sizeof(double));
     }
   }
+}
+
+// ---- gauge molecular dynamics (gauge_md.hip).  Host links in QUDA_QDP_GAUGE_ORDER and host momenta in the MILC ten-real layout
+// only, both fp64.  A call that makes new links resident rebuilds the precise, sloppy and preconditioner copies through the loader
+// and drops the smeared field; a resident clover term and multigrid hierarchy belong to the old links and are the caller's to
+// rebuild, as in the reference.  Unlike the reference, a resident field that a call uses without replacing it stays resident. ----
+static void checkMdParam(const char *fn, const QudaGaugeParam *p) {
+  if (!g_initialized) errorQuda("QUDA not initialized");
+  if (p->gauge_order != QUDA_QDP_GAUGE_ORDER)
+    errorQuda("%s: gauge_order = %d: only QUDA_QDP_GAUGE_ORDER host links (and MILC-order ten-real momenta) are supported", fn, p->gauge_order);
+  if (p->cpu_prec != QUDA_DOUBLE_PRECISION) errorQuda("%s: fp64 host fields only", fn);
+}
+// the links a call works on: the resident ones, or the host links loaded into a field of the precision and reconstruct of param
+static GaugeField *mdLinks(const char *fn, void *h_gauge, QudaGaugeParam *param, bool &owned) {
+  owned = false;
+  if (param->use_resident_gauge) {
+    if (!gaugePrecise) errorQuda("%s: No resident gauge field to use", fn);
+    return gaugePrecise;
+  }
+  checkGaugeParam(param);
+  GaugeField *U = new GaugeField(LatticeGeom(param->X), param->cuda_prec, param->reconstruct, param->t_boundary, param->anisotropy);
+  loadGaugeWithHalo(*U, (void **)h_gauge, param->cpu_prec);
+  owned = true;
+  return U;
+}
+static MomField *mdMomentum(const char *fn, void *h_mom, const QudaGaugeParam *param, const LatticeGeom &geom, bool load, bool &owned) {
+  owned = false;
+  if (param->use_resident_mom) {
+    if (!momResident) errorQuda("%s: No resident momentum field to use", fn);
+    if (!(momResident->geom == geom)) errorQuda("%s: the resident momentum differs in geometry from the links", fn);
+    return momResident;
+  }
+  MomField *m = new MomField(geom);
+  if (load) m->load(h_mom);
+  owned = true;
+  return m;
+}
+static void keepMomentum(MomField *m, bool owned, const QudaGaugeParam *param) {
+  if (param->make_resident_mom) {
+    if (momResident && momResident != m) delete momResident;
+    momResident = m;
+  } else if (owned) {
+    delete m;
+  }
+}
+// new host QDP links become the resident field, in the precisions of the resident field they replace (else of param)
+static void makeLinksResident(std::vector<std::vector<double>> &links, QudaGaugeParam *param, bool hadResident) {
+  void *ptr[4];
+  for (int d = 0; d < 4; d++) ptr[d] = links[d].data();
+  QudaGaugeParam gp = hadResident ? g_gauge_param : *param;
+  gp.cpu_prec = QUDA_DOUBLE_PRECISION;
+  gp.gauge_order = QUDA_QDP_GAUGE_ORDER;
+  if (!hadResident) checkGaugeParam(&gp);
+  loadResidentLinks(ptr, &gp);
+  param->gaugeGiB = gp.gaugeGiB;
+}
+
+// reference lib/interface_quda.cpp:3799-3935 (lib/gauge_force.cu)
+int computeGaugeForceQuda(void *mom, void *sitelink, int ***input_path_buf, int *path_length, double *loop_coeff, int num_paths, int max_length,
+                          double dt, QudaGaugeParam *qudaGaugeParam) {
+  QudaGaugeParam *param = qudaGaugeParam;
+  checkMdParam("computeGaugeForceQuda", param);
+  if (max_length > kGaugeForceMaxLength) errorQuda("computeGaugeForceQuda: max_length = %d exceeds the cap of %d links per path", max_length, kGaugeForceMaxLength);
+  bool ownU, ownM;
+  GaugeField *U;
+  if (!param->use_resident_gauge && param->make_resident_gauge) {   // the host links become the resident field first
+    checkGaugeParam(param);
+    loadResidentLinks(sitelink, param);
+    U = gaugePrecise; ownU = false;
+  } else {
+    U = mdLinks("computeGaugeForceQuda", sitelink, param, ownU);
+  }
+  MomField *M = mdMomentum("computeGaugeForceQuda", mom, param, U->geom, !param->overwrite_mom, ownM);
+  if (param->use_resident_mom && param->overwrite_mom) M->zero();
+  gaugeForce(*M, *U, dt, input_path_buf, path_length, loop_coeff, num_paths, max_length);
+  if (param->return_result_mom) M->save(mom);
+  if (ownU) delete U;
+  keepMomentum(M, ownM, param);
+  return 0;
+}
+
+// reference lib/interface_quda.cpp:5081-5185 (lib/gauge_update_quda.cu)
+void updateGaugeFieldQuda(void *gauge, void *momentum, double dt, int conj_mom, int exact, QudaGaugeParam *param) {
+  checkMdParam("updateGaugeFieldQuda", param);
+  bool ownU, ownM;
+  GaugeField *U = mdLinks("updateGaugeFieldQuda", gauge, param, ownU);
+  MomField *M = mdMomentum("updateGaugeFieldQuda", momentum, param, U->geom, true, ownM);
+  const size_t n = (size_t)U->geom.V * 18;
+  std::vector<std::vector<double>> links(4, std::vector<double>(n));
+  void *ptr[4];
+  for (int d = 0; d < 4; d++) ptr[d] = links[d].data();
+  updateGaugeLinks(ptr, *U, *M, dt, conj_mom != 0, exact != 0);
+  if (ownU) delete U;
+  if (param->return_result_gauge) for (int d = 0; d < 4; d++) memcpy(((void **)gauge)[d], ptr[d], n * sizeof(double));
+  if (param->make_resident_gauge) makeLinksResident(links, param, !ownU);
+  keepMomentum(M, ownM, param);
+}
+
+// reference lib/interface_quda.cpp:5187-5247
+void projectSU3Quda(void *gauge_h, double tol, QudaGaugeParam *param) {
+  checkMdParam("projectSU3Quda", param);
+  bool ownU;
+  GaugeField *U = mdLinks("projectSU3Quda", gauge_h, param, ownU);
+  const size_t n = (size_t)U->geom.V * 18;
+  std::vector<std::vector<double>> links(4, std::vector<double>(n));
+  void *ptr[4];
+  for (int d = 0; d < 4; d++) ptr[d] = links[d].data();
+  const long failures = projectSU3Links(ptr, *U, tol);
+  if (ownU) delete U;
+  if (failures > 0) errorQuda("Error in the SU(3) unitarization: %ld failures", failures);
+  if (param->return_result_gauge) for (int d = 0; d < 4; d++) memcpy(((void **)gauge_h)[d], ptr[d], n * sizeof(double));
+  if (param->make_resident_gauge) makeLinksResident(links, param, !ownU);
+}
+
+// reference lib/interface_quda.cpp:5310-5370 (lib/momentum.cu)
+double momActionQuda(void *momentum, QudaGaugeParam *param) {
+  checkMdParam("momActionQuda", param);
+  for (int d = 0; d < 4; d++) if (param->X[d] <= 0 || param->X[d] % 2) errorQuda("Parameter X[%d] = %d undefined or odd", d, param->X[d]);
+  bool ownM;
+  MomField *M = mdMomentum("momActionQuda", momentum, param, LatticeGeom(param->X), true, ownM);
+  const double action = momAction(*M);
+  keepMomentum(M, ownM, param);
+  return action;
 }
 
 // reference :730-930.  Host order: QUDA_PACKED_CLOVER_ORDER.  If the inverse is not supplied (or
