@@ -228,4 +228,16 @@ long projectSU3Links(void *const h_out[4], const GaugeField &U, double tol);
 // sum over links of tr(A^dag A)/2 - 4, global, in a fixed order
 double momAction(const MomField &mom);
 
+// ---- fermion force (ferm_force.hip) ----
+constexpr int kFermForceMaxFields = 16;   // (X, Y) pairs of one launch, a doublet counting two: more are chunked on the host
+// mom <- TA(mom - sum_i coeff[i] U O[X_i, Y_i]), O_mu[X, Y](x) = tr_spin[(1 - g_mu) X(x + mu) Y^dag(x) + (1 + g_mu) Y(x + mu) X^dag(x)]
+// summed over the flavours; X_i, Y_i full fp64 device fields of one or two flavours.  Any partition mask (ghost zones of X and Y)
+void fermionOprodForce(MomField &mom, const GaugeField &U, const std::vector<ColorSpinorField *> &X, const std::vector<ColorSpinorField *> &Y,
+                       const std::vector<double> &coeff);
+// mom <- mom + dt sum_i coeff[i] F[x_i], F the force of phi^dag (Mh^dag Mh)^-1 phi at the single-parity solutions x_i of the even-odd
+// operator Mh of inv (Wilson, twisted mass +-1, the doublet; the four matpc types; the mass normalisations of the solves)
+void tmForce(MomField &mom, const GaugeField &U, double dt, const std::vector<ColorSpinorField *> &x, const std::vector<double> &coeff, QudaInvertParam *inv);
+// seconds the last fermionOprodForce spent in its kernel launches (device events), for tools/ferm_force_timing.py
+double fermForceLastKernelSecs();
+
 }  // namespace quda

@@ -226,6 +226,27 @@ double qudaAmdQCharge(double *h_density, int lexicographic, int which);
 /* Test hook: out[k] = exp(i q[k]) for n traceless Hermitian 3x3 matrices, 18 doubles each (row-major, re/im), evaluated on the
  * device by the function the stout kernel calls (Cayley-Hamilton form). */
 void qudaAmdSu3ExpIQ(int n, const double *q, double *out);
+/* Fermion force of molecular dynamics for the actions this library solves (Wilson, degenerate twisted mass, the non-degenerate
+ * doublet); the reference's only Wilson-type fermion force, computeCloverForceQuda, belongs to the Wilson-clover action.  Conventions
+ * of the gauge force: U' = A U, momenta as ten reals per link [site (even, odd)][mu][10], TA(M) = (M - M^dag)/2 - tr(M - M^dag)/6.
+ * Both calls work on the resident links (an error if there are none), take fp64 host momenta under gauge_param with
+ * QUDA_QDP_GAUGE_ORDER, honour overwrite_mom, use_resident_mom, make_resident_mom and return_result_mom as computeGaugeForceQuda
+ * does, and run under any partition.  Refused: twisted clover (the derivative of the clover term is not part of this), cuda_prec
+ * other than fp64, solve_type other than QUDA_NORMOP_PC_SOLVE / QUDA_DIRECT_PC_SOLVE.
+ *
+ * qudaAmdFermionOprodForce: mom_mu(x) <- TA(mom_mu(x) - sum_i coeff[i] U_mu(x) O_mu[X_i, Y_i](x)) with
+ *   O_mu[X, Y](x) = tr_spin[(1 - g_mu) X(x + mu) Y^dag(x) + (1 + g_mu) Y(x + mu) X^dag(x)]
+ * for nvector pairs of full host fields h_x[i], h_y[i] in the layout, basis and precision MatQuda takes under inv_param (two flavours
+ * when twist_flavor is the doublet, summed over).  U is the link as the stencil sees it, anti-periodic sign included.
+ *
+ * qudaAmdComputeTMForce: mom <- mom + dt sum_i coeff[i] F[x_i], F the force of phi^dag (Mh^dag Mh)^-1 phi, for the single-parity
+ * solutions h_x[i] = (Mh^dag Mh + shift_i)^-1 phi that a QUDA_NORMOP_PC_SOLVE returns under inv_param (the shifts drop out of the force).
+ * Mh is the even-odd operator of inv_param: dslash_type Wilson or twisted mass, twist +-1 or the doublet with epsilon, the four
+ * matpc_type (Wilson: the two symmetric ones), every mass_normalization.  X_i and Y_i are built on the device. */
+void qudaAmdFermionOprodForce(void *mom, void **h_x, void **h_y, double *coeff, int nvector, QudaGaugeParam *gauge_param, QudaInvertParam *inv_param);
+void qudaAmdComputeTMForce(void *mom, double dt, void **h_x, double *coeff, int nvector, QudaGaugeParam *gauge_param, QudaInvertParam *inv_param);
+/* seconds the kernels of the last of these calls took on the device (tools/ferm_force_timing.py) */
+double qudaAmdFermForceLastKernelSecs(void);
 /* h_out = smear^nsmear(h_in) (QKXTM_Vector_Kepler::gaussianSmearing, lib/qudaQKXTM_Vector_Kepler.cpp:386-421); the lattice is
  * that of the resident gauge field */
 void qudaAmdGaussianSmear(void *h_out, const void *h_in, void **gauge_APE, int nsmear, double alpha);

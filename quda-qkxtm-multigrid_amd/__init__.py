@@ -130,7 +130,8 @@ EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLo
                  "qudaAmdBlasMultiShiftChunk", "qudaAmdDiracMdagMShift", "qudaAmdTimeMdagM", "qudaAmdTimeCGBlas", "qudaAmdTimeMultiShift",
                  "qudaAmdNdegTwist", "qudaAmdStoutSmear", "qudaAmdQCharge", "qudaAmdSu3ExpIQ",
                  "qudaAmdBlasApply", "qudaAmdBlasDevUpdate", "qudaAmdBlasMultiSupported", "qudaAmdBlasMultiDot", "qudaAmdBlasMultiCaxpyResidual",
-                 "qudaAmdBlasMultiCaxpy", "qudaAmdBlasHeavyQuarkResidualNorm"]
+                 "qudaAmdBlasMultiCaxpy", "qudaAmdBlasHeavyQuarkResidualNorm",
+                 "qudaAmdFermionOprodForce", "qudaAmdComputeTMForce", "qudaAmdFermForceLastKernelSecs"]
 
 _lib = None
 
@@ -319,6 +320,12 @@ def lib():
         L.projectSU3Quda.restype = None
         L.momActionQuda.argtypes = [_p, C.POINTER(QudaGaugeParam)]
         L.momActionQuda.restype = _d
+        L.qudaAmdFermionOprodForce.argtypes = [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_d), _i, C.POINTER(QudaGaugeParam), C.POINTER(QudaInvertParam)]
+        L.qudaAmdFermionOprodForce.restype = None
+        L.qudaAmdComputeTMForce.argtypes = [_p, _d, C.POINTER(_p), C.POINTER(_d), _i, C.POINTER(QudaGaugeParam), C.POINTER(QudaInvertParam)]
+        L.qudaAmdComputeTMForce.restype = None
+        L.qudaAmdFermForceLastKernelSecs.argtypes = []
+        L.qudaAmdFermForceLastKernelSecs.restype = _d
         L.qudaAmdGaussianSmear.argtypes = [_p, _p, C.POINTER(_p), _i, _d]
         L.qudaAmdCalcMGPropagators.argtypes = [_p, _p, C.POINTER(_p), C.POINTER(QudaInvertParam), C.POINTER(QudaAmdSourceParam)]
         L.qudaAmdTwopMomenta.argtypes = [_i, C.POINTER(_i), _i]
@@ -754,6 +761,53 @@ def mom_action(gp, mom=None, make_resident_mom=False):
     m = None if mom is None else np.ascontiguousarray(mom, dtype=np.float64)
     q = _md_param(gp, use_resident_mom=mom is None, make_resident_mom=make_resident_mom)
     return float(lib().momActionQuda(_vp(m), C.byref(q)))
+
+
+def _force_mom(gp, mom, overwrite, make_resident_mom, return_mom):
+    """(host momentum array, parameters) of a fermion-force call: mom None is the resident momentum, or none at all with overwrite"""
+    V = int(np.prod([gp.X[d] for d in range(4)]))
+    out = np.zeros((V, 4, 10)) if mom is None else np.ascontiguousarray(mom, dtype=np.float64).reshape(V, 4, 10).copy()
+    q = _md_param(gp, overwrite_mom=overwrite, use_resident_gauge=True, use_resident_mom=mom is None and not overwrite,
+                  make_resident_mom=make_resident_mom, return_result_mom=return_mom)
+    return out, q
+
+
+def _field_ptrs(fields):
+    fields = [np.ascontiguousarray(f, dtype=np.float64) for f in fields]
+    return fields, (_p * len(fields))(*[_vp(f) for f in fields])
+
+
+def ferm_oprod_force(gp, ip, xs, ys, coeff, mom=None, overwrite=False, make_resident_mom=False, return_mom=True):
+    """qudaAmdFermionOprodForce: mom <- TA(mom - sum_i coeff[i] U O[xs[i], ys[i]]) on the resident links, O_mu[X, Y](x) =
+    tr_spin[(1 - g_mu) X(x + mu) Y^dag(x) + (1 + g_mu) Y(x + mu) X^dag(x)].  xs, ys: full host fields as MatQuda takes them under ip
+    (two flavours for the doublet).  mom: (V, 4, 10) host momentum, None: the resident momentum (or, with overwrite, none at all).
+    Returns the new momentum unless return_mom is False"""
+    n = len(coeff)
+    if len(xs) != n or len(ys) != n:
+        raise ValueError("one coefficient per pair of fields")
+    out, q = _force_mom(gp, mom, overwrite, make_resident_mom, return_mom)
+    xs, px = _field_ptrs(xs)
+    ys, py = _field_ptrs(ys)
+    lib().qudaAmdFermionOprodForce(_vp(out), px, py, (_d * max(n, 1))(*[float(c) for c in coeff]), n, C.byref(q), C.byref(ip))
+    return out if return_mom else None
+
+
+def tm_force(gp, ip, xs, coeff, dt, mom=None, overwrite=False, make_resident_mom=False, return_mom=True):
+    """qudaAmdComputeTMForce: mom <- mom + dt sum_i coeff[i] F[xs[i]] on the resident links, F the force of phi^dag (Mh^dag Mh)^-1 phi at
+    the single-parity solutions xs[i] of a QUDA_NORMOP_PC_SOLVE under ip (Wilson, twisted mass +-1 or the doublet; any matpc type and
+    mass normalisation).  Momentum arguments as in ferm_oprod_force"""
+    n = len(coeff)
+    if len(xs) != n:
+        raise ValueError("one coefficient per solution")
+    out, q = _force_mom(gp, mom, overwrite, make_resident_mom, return_mom)
+    xs, px = _field_ptrs(xs)
+    lib().qudaAmdComputeTMForce(_vp(out), float(dt), px, (_d * max(n, 1))(*[float(c) for c in coeff]), n, C.byref(q), C.byref(ip))
+    return out if return_mom else None
+
+
+def ferm_force_kernel_secs():
+    """device seconds the kernels of the last fermion-force call took"""
+    return float(lib().qudaAmdFermForceLastKernelSecs())
 
 
 def project_su3(gp, tol, gauge=None, make_resident_gauge=False, return_gauge=True):

@@ -52,13 +52,15 @@ inline void fillStencilGeom(StencilGeom &a, const GaugeField &U, const LatticeGe
   for (int mu = 0; mu < 4; mu++) { a.faceCB[mu] = g.faceCB[mu]; a.ghostOff[mu] = -1; }
 }
 
+// the two parity blocks (even, odd) of one full 24-real fp64 planar field and their stride: a ColorSpinorField, or one flavour of a doublet
+struct FullFieldView { const double *par[2]; int stride; };
+
 // The ghost zones of n full fields in ONE buffer, exchanged for every (field, parity of the reading site, partitioned mu, fwd / bwd);
 // fills ghost / ghostOff of the argument and frees the buffer when it goes out of scope.  Collective.
 class GhostZones {
   double *buf = nullptr;
 
-public:
-  GhostZones(StencilGeom &a, const std::vector<const ColorSpinorField *> &fields, const LatticeGeom &g, const CommGrid &cg) {
+  void fill(StencilGeom &a, const std::vector<FullFieldView> &fields, const LatticeGeom &g, const CommGrid &cg) {
     const size_t n = fields.size();
     size_t doubles = 0;
     for (int mu = 0; mu < 4; mu++) {
@@ -74,12 +76,18 @@ public:
       const size_t zone = (size_t)g.faceCB[mu] * 24;
       for (size_t f = 0; f < n; f++)
         for (int parity = 0; parity < 2; parity++)
-          for (int d = 0; d < 2; d++) {
-            const ColorSpinorField &other = parity ? fields[f]->Even() : fields[f]->Odd();
-            exchangeFullFace(buf + a.ghostOff[mu] + ((f * 2 + parity) * 2 + d) * zone, (const double *)other.V(), g, other.Stride(), parity, 2 * mu + d);
-          }
+          for (int d = 0; d < 2; d++)   // a site of `parity` reads the other parity's block
+            exchangeFullFace(buf + a.ghostOff[mu] + ((f * 2 + parity) * 2 + d) * zone, fields[f].par[1 - parity], g, fields[f].stride, parity, 2 * mu + d);
     }
   }
+
+public:
+  GhostZones(StencilGeom &a, const std::vector<const ColorSpinorField *> &fields, const LatticeGeom &g, const CommGrid &cg) {
+    std::vector<FullFieldView> views;
+    for (const ColorSpinorField *f : fields) views.push_back({{(const double *)f->Even().V(), (const double *)f->Odd().V()}, f->Even().Stride()});
+    fill(a, views, g, cg);
+  }
+  GhostZones(StencilGeom &a, const FullFieldView *fields, size_t n, const LatticeGeom &g, const CommGrid &cg) { fill(a, std::vector<FullFieldView>(fields, fields + n), g, cg); }
   ~GhostZones() { if (buf) (void)hipFree(buf); }
   GhostZones(const GhostZones &) = delete;
   GhostZones &operator=(const GhostZones &) = delete;

@@ -61,57 +61,6 @@ __device__ __forceinline__ void hop(int *y, int dir, int s, const GaugeView &g) 
       y[k] = v < 0 ? v + g.X[k] : (v >= g.X[k] ? v - g.X[k] : v);
     }
 }
-// A <- A B in place, row by row: a row of the product needs that row of A only, so six reals of scratch registers are enough
-__device__ __forceinline__ void m3_mul_right(M3 &a, const M3 &b) {
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    double r[3], m[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      r[j] = 0; m[j] = 0;
-#pragma unroll
-      for (int k = 0; k < 3; k++) { r[j] += a.re[i * 3 + k] * b.re[k * 3 + j] - a.im[i * 3 + k] * b.im[k * 3 + j]; m[j] += a.re[i * 3 + k] * b.im[k * 3 + j] + a.im[i * 3 + k] * b.re[k * 3 + j]; }
-    }
-#pragma unroll
-    for (int j = 0; j < 3; j++) { a.re[i * 3 + j] = r[j]; a.im[i * 3 + j] = m[j]; }
-  }
-}
-// A <- A B^dag in place
-__device__ __forceinline__ void m3_mul_right_dag(M3 &a, const M3 &b) {
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    double r[3], m[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      r[j] = 0; m[j] = 0;
-#pragma unroll
-      for (int k = 0; k < 3; k++) { r[j] += a.re[i * 3 + k] * b.re[j * 3 + k] + a.im[i * 3 + k] * b.im[j * 3 + k]; m[j] += a.im[i * 3 + k] * b.re[j * 3 + k] - a.re[i * 3 + k] * b.im[j * 3 + k]; }
-    }
-#pragma unroll
-    for (int j = 0; j < 3; j++) { a.re[i * 3 + j] = r[j]; a.im[i * 3 + j] = m[j]; }
-  }
-}
-
-// m (the ten reals of A_mu(x)) <- TA(A - eb3 U V), lib/gauge_force.cu:131-140.  The stored A is anti-Hermitian already, so only its
-// trace and the product W = U V go through the projection:
-//   off-diagonal  A_ij - eb3 (W_ij - conj W_ji)/2,   diagonal  d_i - (d_0 + d_1 + d_2)/3 with d_i = Im A_ii - eb3 Im W_ii
-__device__ __forceinline__ void force_epilogue(double *m, const M3 &U, const M3 &V, double eb3) {
-  M3 W;
-  m3_mul(W, U, V);
-  double a[10];
-#pragma unroll
-  for (int k = 0; k < 10; k++) a[k] = m[k];
-  const double h = 0.5 * eb3;
-  a[0] -= h * (W.re[1] - W.re[3]); a[1] -= h * (W.im[1] + W.im[3]);
-  a[2] -= h * (W.re[2] - W.re[6]); a[3] -= h * (W.im[2] + W.im[6]);
-  a[4] -= h * (W.re[5] - W.re[7]); a[5] -= h * (W.im[5] + W.im[7]);
-  const double d0 = a[6] - eb3 * W.im[0], d1 = a[7] - eb3 * W.im[4], d2 = a[8] - eb3 * W.im[8];
-  const double tr = (d0 + d1 + d2) * (1.0 / 3.0);
-  a[6] = d0 - tr; a[7] = d1 - tr; a[8] = d2 - tr; a[9] = 0;
-#pragma unroll
-  for (int k = 0; k < 10; k++) m[k] = a[k];
-}
-
 // ---- direct gather: one thread per (site, parity), the direction in blockIdx.y.  Running product, loaded link and accumulator are
 // the three live matrices (54 fp64 = 108 VGPRs); arithmetic in fp64 whatever the link precision ----
 template <typename T, int R>

@@ -4,6 +4,7 @@
 // :1716 MatQuda, :1796 MatDagMatQuda) on top of the CDNA4 field/operator classes.
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <sys/time.h>
 
 #include "blas.h"
@@ -557,6 +558,61 @@ double momActionQuda(void *momentum, QudaGaugeParam *param) {
   keepMomentum(M, ownM, param);
   return action;
 }
+
+// ---- fermion force (ferm_force.hip; include/quda_amd_ext.h).  Every refusal comes before any device work ----
+static void meetRanksBeforeOperator();
+static void checkFermForceParam(const char *fn, int nvector, const QudaGaugeParam *gp, const QudaInvertParam *inv) {
+  checkMdParam(fn, gp);
+  if (inv->dslash_type == QUDA_TWISTED_CLOVER_DSLASH) errorQuda("%s: twisted clover: the derivative of the clover term is not part of this force", fn);
+  if (inv->dslash_type != QUDA_WILSON_DSLASH && inv->dslash_type != QUDA_TWISTED_MASS_DSLASH) errorQuda("%s: dslash_type %d: Wilson and twisted mass only", fn, inv->dslash_type);
+  if (inv->cuda_prec != QUDA_DOUBLE_PRECISION) errorQuda("%s: cuda_prec = %d: fp64 spinor fields only", fn, inv->cuda_prec);
+  if (inv->solve_type != QUDA_NORMOP_PC_SOLVE && inv->solve_type != QUDA_DIRECT_PC_SOLVE)
+    errorQuda("%s: solve_type = %d: the force is that of the even-odd operator (QUDA_NORMOP_PC_SOLVE or QUDA_DIRECT_PC_SOLVE)", fn, inv->solve_type);
+  if (nvector < 1) errorQuda("%s: nvector = %d", fn, nvector);
+  if (!gaugePrecise) errorQuda("%s: No resident gauge field to use", fn);
+  for (int d = 0; d < 4; d++) if (gp->X[d] != g_geom.X[d]) errorQuda("%s: X[%d] = %d differs from the resident links' %d", fn, d, gp->X[d], g_geom.X[d]);
+}
+// n host fields under inv (parity fields, or full ones) as fp64 device fields
+static std::vector<ColorSpinorField *> uploadForceFields(void **h, int n, QudaInvertParam *inv, bool parity) {
+  ColorSpinorParam dp = deviceSpinorParam(QUDA_DOUBLE_PRECISION, parity ? QUDA_PARITY_SITE_SUBSET : QUDA_FULL_SITE_SUBSET, fieldTwistFlavor(*inv));
+  std::vector<ColorSpinorField *> out(n);
+  for (int i = 0; i < n; i++) {
+    ColorSpinorParam cpuParam(h[i], *inv, g_geom.X, parity);
+    ColorSpinorField host(cpuParam);
+    out[i] = new ColorSpinorField(dp);
+    *out[i] = host;
+  }
+  return out;
+}
+static void fermForceCall(const char *fn, void *mom, QudaGaugeParam *param, const std::function<void(MomField &)> &force) {
+  bool ownM;
+  MomField *M = mdMomentum(fn, mom, param, gaugePrecise->geom, !param->overwrite_mom, ownM);
+  if (param->use_resident_mom && param->overwrite_mom) M->zero();
+  meetRanksBeforeOperator();
+  force(*M);
+  if (param->return_result_mom) M->save(mom);
+  keepMomentum(M, ownM, param);
+}
+
+void qudaAmdFermionOprodForce(void *mom, void **h_x, void **h_y, double *coeff, int nvector, QudaGaugeParam *gauge_param, QudaInvertParam *inv_param) {
+  checkFermForceParam("qudaAmdFermionOprodForce", nvector, gauge_param, inv_param);
+  fermForceCall("qudaAmdFermionOprodForce", mom, gauge_param, [&](MomField &M) {
+    std::vector<ColorSpinorField *> X = uploadForceFields(h_x, nvector, inv_param, false), Y = uploadForceFields(h_y, nvector, inv_param, false);
+    fermionOprodForce(M, *gaugePrecise, X, Y, std::vector<double>(coeff, coeff + nvector));
+    for (int i = 0; i < nvector; i++) { delete X[i]; delete Y[i]; }
+  });
+}
+
+void qudaAmdComputeTMForce(void *mom, double dt, void **h_x, double *coeff, int nvector, QudaGaugeParam *gauge_param, QudaInvertParam *inv_param) {
+  checkFermForceParam("qudaAmdComputeTMForce", nvector, gauge_param, inv_param);
+  fermForceCall("qudaAmdComputeTMForce", mom, gauge_param, [&](MomField &M) {
+    std::vector<ColorSpinorField *> x = uploadForceFields(h_x, nvector, inv_param, true);
+    tmForce(M, *gaugePrecise, dt, x, std::vector<double>(coeff, coeff + nvector), inv_param);
+    for (int i = 0; i < nvector; i++) delete x[i];
+  });
+}
+
+double qudaAmdFermForceLastKernelSecs(void) { return fermForceLastKernelSecs(); }
 
 // reference :730-930.  Host order: QUDA_PACKED_CLOVER_ORDER.  If the inverse is not supplied (or
 // compute_clover_inverse is set) it is computed on the device; for twisted clover it is (A^2 + 4 kappa^2 mu^2)^-1
