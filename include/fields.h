@@ -189,7 +189,16 @@ class CloverField {
   double GiB() const { return 2.0 * bytes / (double)(1 << 30); }
 };
 
-// gauge tools on the device (fields.hip): APE smearing of the spatial links (a new fp64 field), the plaquette averages, and the
+// fp64 host links in QDP order: the four arrays of 18 V reals and the pointers to them, as loadQDP and saveGaugeQDP take them
+struct HostLinks {
+  std::vector<std::vector<double>> links;
+  void *ptr[4];
+  explicit HostLinks(size_t V) : links(4, std::vector<double>(V * 18)) { for (int d = 0; d < 4; d++) ptr[d] = links[d].data(); }
+  HostLinks(const HostLinks &) = delete;
+  HostLinks &operator=(const HostLinks &) = delete;
+};
+
+// gauge tools on the device (gauge_obs.hip): APE smearing of the spatial links (a new fp64 field), the plaquette averages, and the
 // forward links back in host QDP order
 GaugeField *apeSmear(const GaugeField &U, unsigned nSteps, double alpha);
 // stout smearing of the first ndir directions (3: spatial links from spatial staples, 4: all links, all six planes); a new fp64 field

@@ -11,6 +11,7 @@
 // one launch, so the link and the momentum are read and written once.  A doublet enters as two pairs (its two flavours) with the same coefficient.
 // Neighbours of a partitioned direction come from the ghost zones of the contractions (GhostZones / load_site).
 #include "contract_stencil.h"
+#include "dispatch.h"
 #include "dslash_arg.h"
 #include "gauge_device.h"
 
@@ -122,7 +123,6 @@ void fermionOprodForce(MomField &mom, const GaugeField &U, const std::vector<Col
   for (size_t i = 0; i < n; i++) { checkForceField(*X[i], *X[0], geom); checkForceField(*Y[i], *X[0], geom); }
   const int nf = X[0]->Nflavor(), Vh = geom.Vh, bs = 256, nb = (2 * Vh + 63) / 64;
   const size_t perLaunch = kFermForceMaxFields / nf;
-  const bool r12 = U.reconstruct == QUDA_RECONSTRUCT_12, r8 = U.reconstruct == QUDA_RECONSTRUCT_8;
   hipStream_t s = computeStream();
   hipEvent_t ev[2];
   for (int k = 0; k < 2; k++) HIP_CHECK(hipEventCreate(&ev[k]));
@@ -148,17 +148,7 @@ void fermionOprodForce(MomField &mom, const GaugeField &U, const std::vector<Col
       }
     GhostZones ghosts(arg, views.data(), views.size(), geom, cg);
     HIP_CHECK(hipEventRecord(ev[0], s));
-#define QA_FF(T) \
-  if (r12) hipLaunchKernelGGL((ferm_force_kernel<T, 12>), dim3(nb), dim3(bs), 0, s, arg); \
-  else if (r8) hipLaunchKernelGGL((ferm_force_kernel<T, 8>), dim3(nb), dim3(bs), 0, s, arg); \
-  else hipLaunchKernelGGL((ferm_force_kernel<T, 18>), dim3(nb), dim3(bs), 0, s, arg);
-    switch (U.precision) {
-      case QUDA_DOUBLE_PRECISION: QA_FF(double) break;
-      case QUDA_SINGLE_PRECISION: QA_FF(float) break;
-      case QUDA_HALF_PRECISION: QA_FF(short) break;
-      default: errorQuda("bad gauge precision %d", U.precision);
-    }
-#undef QA_FF
+    forLinkType(U, [&](auto t, auto r) { hipLaunchKernelGGL((ferm_force_kernel<decltype(t), decltype(r)::value>), dim3(nb), dim3(bs), 0, s, arg); });
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(ev[1], s));
     HIP_CHECK(hipStreamSynchronize(s));   // the ghost zones go out of scope

@@ -1,7 +1,8 @@
-// gauge_device.h — the 3x3 colour-matrix device code that fields.hip (clover construction, smearing, plaquette, topological charge) and
-// gauge_md.hip (gauge force, link update, SU(3) projection) share, and ferm_force.hip with them: the matrix type and its products, the
-// resident-link loader, the epilogue of both force kernels, matrix fields with their load/store, the polar SU(3) projection and
-// exp(iQ); and the host helpers of the transport formulation.
+// gauge_device.h — the 3x3 colour-matrix device code that clover.hip (clover construction), gauge_obs.hip (smearing, plaquette,
+// topological charge) and gauge_md.hip (gauge force, link update, SU(3) projection) share, and ferm_force.hip with them: the matrix
+// type and its products, the resident-link loader, the epilogue of both force kernels, matrix fields with their load/store, the
+// polar SU(3) projection, exp(iQ), the clover-leaf sum with its scatter into the clover blocks and the block sum of the reductions;
+// and the host helpers of the transport formulation: pools of matrix fields, links to the host, ordered sums.
 #pragma once
 
 #include "fields.h"
@@ -236,11 +237,122 @@ __device__ __forceinline__ void su3_exp_iq(M3 &E, const M3 &Q) {
   E.im[0] += fi[0]; E.im[4] += fi[0]; E.im[8] += fi[0];
 }
 
-// host side (fields.hip): the view of a resident field, its forward links of one direction as a matrix field, out(x) = in(x + dhat(dir))
-// (dir = 2 mu: forward, 2 mu + 1: backward; ghost-aware), and out (+)= op(A) op(B) site by site
+// ---- the clover leaves: field strength, its scatter into the colour blocks of the clover term, the packed chiral block ----
+// F = (Q - Q^dag) / 8
+__device__ __forceinline__ void m3_fmunu(M3 &F, const M3 &Q) {
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      F.re[i * 3 + j] = 0.125 * (Q.re[i * 3 + j] - Q.re[j * 3 + i]);
+      F.im[i * 3 + j] = 0.125 * (Q.im[i * 3 + j] + Q.im[j * 3 + i]);
+    }
+}
+// F = (Q - Q^dag) / 8 of the leaf sum Q = P + A + B + C at site (par, idx)
+__device__ __forceinline__ void leaf_sum_fmunu(M3 &F, const MatField &P, const MatField &A, const MatField &B, const MatField &C, int par, int idx) {
+  M3 Q, m;
+  mf_load(Q, P, par, idx);
+  mf_load(m, A, par, idx);
+#pragma unroll
+  for (int k = 0; k < 9; k++) { Q.re[k] += m.re[k]; Q.im[k] += m.im[k]; }
+  mf_load(m, B, par, idx);
+#pragma unroll
+  for (int k = 0; k < 9; k++) { Q.re[k] += m.re[k]; Q.im[k] += m.im[k]; }
+  mf_load(m, C, par, idx);
+#pragma unroll
+  for (int k = 0; k < 9; k++) { Q.re[k] += m.re[k]; Q.im[k] += m.im[k]; }
+  m3_fmunu(F, Q);
+}
+// F_mu_nu (index fi = mu (mu - 1) / 2 + nu) folded into the colour blocks of the two chiral blocks ch: B1[ch] = i c (F0 -/+ F5),
+// B2[ch] = c (F1 +/- F4 - i (F2 -/+ F3)).   i c F = c (-fm + i fr);   c F = c (fr + i fm);   -i c F = c (fm - i fr)
+__device__ __forceinline__ void clover_add_fmunu(M3 *b1, M3 *b2, int fi, double coeff, const M3 &F) {
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+    const double fr = F.re[k], fm = F.im[k];
+    switch (fi) {
+      case 0: b1[0].re[k] += -coeff * fm; b1[0].im[k] += coeff * fr; b1[1].re[k] += -coeff * fm; b1[1].im[k] += coeff * fr; break;
+      case 5: b1[0].re[k] -= -coeff * fm; b1[0].im[k] -= coeff * fr; b1[1].re[k] += -coeff * fm; b1[1].im[k] += coeff * fr; break;
+      case 1: b2[0].re[k] += coeff * fr; b2[0].im[k] += coeff * fm; b2[1].re[k] += coeff * fr; b2[1].im[k] += coeff * fm; break;
+      case 4: b2[0].re[k] += coeff * fr; b2[0].im[k] += coeff * fm; b2[1].re[k] -= coeff * fr; b2[1].im[k] -= coeff * fm; break;
+      case 2: b2[0].re[k] += coeff * fm; b2[0].im[k] -= coeff * fr; b2[1].re[k] += coeff * fm; b2[1].im[k] -= coeff * fr; break;
+      default: b2[0].re[k] -= coeff * fm; b2[0].im[k] += coeff * fr; b2[1].re[k] += coeff * fm; b2[1].im[k] -= coeff * fr; break;  // fi == 3
+    }
+  }
+}
+// one chiral block [[1 - B1, B2^dag], [B2, 1 + B1]] in packed order: 6 diagonal reals, then the 15 strictly-lower entries column by
+// column (tests/clover_reference.cpp:45-53)
+__device__ __forceinline__ void clover_pack_block(double *A, const M3 &b1, const M3 &b2) {
+  for (int i = 0; i < 3; i++) { A[i] = 1.0 - b1.re[i * 3 + i]; A[i + 3] = 1.0 + b1.re[i * 3 + i]; }
+  int k = 0;
+  for (int col = 0; col < 6; col++)
+    for (int row = col + 1; row < 6; row++, k++) {
+      double re, im;
+      const int rs = row / 3, rc = row % 3, cs = col / 3, cc = col % 3;
+      if (rs == 0) { re = -b1.re[rc * 3 + cc]; im = -b1.im[rc * 3 + cc]; }          // spin 0 x spin 0: -B1
+      else if (cs == 1) { re = b1.re[rc * 3 + cc]; im = b1.im[rc * 3 + cc]; }       // spin 1 x spin 1: +B1
+      else { re = b2.re[rc * 3 + cc]; im = b2.im[rc * 3 + cc]; }                    // spin 1 x spin 0: B2
+      A[6 + 2 * k] = re; A[6 + 2 * k + 1] = im;
+    }
+}
+
+// the sum of v over the 256 threads of a block, in thread 0: the lanes of a wave by shuffle, the four wave sums through LDS and
+// added left to right, so the same values give the same bits
+__device__ __forceinline__ double block_sum_256(double v) {
+  __shared__ double lds[4];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+
+// ---- host side (gauge_obs.hip) ----
+// the view of a resident field, its forward links of one direction as a matrix field, out(x) = in(x + dhat(dir)) (dir = 2 mu: forward,
+// 2 mu + 1: backward; ghost-aware), and out (+)= op(A) op(B) site by site
 GaugeView viewOf(const GaugeField &U);
 void extractForwardLinks(MatField F, const GaugeField &U, int mu);
 void shiftField(MatField out, MatField in, const LatticeGeom &geom, int dir);
 void mfMul(MatField out, MatField A, MatField B, int dagA, int dagB, int accumulate);
+// the four clover leaves of the mu-nu plane by transport: on return W[4] = P, W[1] = T_mu P, W[2] = T_nu P, W[3] = T_nu T_mu P
+// (W[0] is scratch)
+void cloverLeaves(MatField W[5], const GaugeField &U, int mu, int nu);
+// any direction partitioned, or the environment variable envName set and not 0: the transport formulation instead of direct gathers
+bool usesTransport(const char *envName);
+// the nb per-block partial sums of a reduction kernel, added in block order by the host (this rank's part); synchronises the stream
+double sumPartials(const double *d_partial, int nb);
+
+int gaugePadSites();                  // fields.hip: plane padding (sites) of the link and clover fields
+void *stagingBuffer(size_t bytes);    // fields.hip: the library's one grow-only device buffer; valid until the next call
+inline size_t alignUp(size_t n, size_t a) { return (n + a - 1) / a * a; }
+
+// n matrix fields, and `extra` doubles behind them, in one device allocation that lives as long as the pool
+struct MatPool {
+  double *pool = nullptr;
+  const int Vh;
+  MatPool(int Vh, int n, size_t extra = 0) : Vh(Vh) { HIP_CHECK(qaMalloc((void **)&pool, (n * fieldDoubles() + extra) * sizeof(double))); }
+  ~MatPool() { (void)hipFree(pool); }
+  MatPool(const MatPool &) = delete;
+  MatPool &operator=(const MatPool &) = delete;
+  size_t fieldDoubles() const { return (size_t)2 * 24 * Vh; }
+  MatField operator[](int i) const { return {pool + i * fieldDoubles(), Vh}; }   // i = n: the extra doubles begin at its p
+};
+
+// One direction at a time: the matrix field links(mu) -> launch(stage, F, mu), which writes host QDP order (even sites then odd, 18
+// reals per site) into the staging buffer -> host array h_out[mu]
+template <typename Links, typename Launch> void matFieldsToHost(void *const h_out[4], const LatticeGeom &geom, Links links, Launch launch) {
+  const size_t bytes = (size_t)geom.V * 18 * sizeof(double);
+  double *stage = (double *)stagingBuffer(bytes);
+  hipStream_t s = computeStream();
+  for (int mu = 0; mu < 4; mu++) {
+    launch(stage, links(mu), mu);
+    HIP_CHECK(hipMemcpyAsync(h_out[mu], stage, bytes, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+}
+// the same from the forward links of a resident field
+template <typename Launch> void linksToHost(void *const h_out[4], const GaugeField &U, Launch launch) {
+  MatPool pool(U.geom.Vh, 1);
+  matFieldsToHost(h_out, U.geom, [&](int mu) { extractForwardLinks(pool[0], U, mu); return pool[0]; }, launch);
+}
 
 }  // namespace quda

@@ -16,11 +16,10 @@
 //   transport  the partial products R_k(y) = L_k(y) R_{k+1}(y') are matrix fields carried one hop at a time by the ghost-aware
 //              shift, so no rank ever needs more than its nearest neighbours' links; any partition mask or rank grid.
 // Both end in force_epilogue, which multiplies with U_mu(x), takes TA, accumulates into the momentum and packs it.
+#include "dispatch.h"
 #include "gauge_device.h"
-#include "qkxtm_internal.h"
 
 #include <cstring>
-#include <vector>
 
 namespace quda {
 
@@ -146,21 +145,15 @@ __global__ void __launch_bounds__(128) force_epilogue_kernel(double *mom, MatFie
 // product seen from x is R_1(x + mu).  One shift and one product per link, every shift a single hop.
 static void gaugeForceTransport(MomField &mom, const GaugeField &U, double eb3, int ***path, const int *length, const double *coeff, int num_paths) {
   const LatticeGeom &geom = U.geom;
-  const int Vh = geom.Vh, bs = 128, nb = (2 * Vh + bs - 1) / bs;
-  const size_t fieldDoubles = (size_t)2 * 24 * Vh;
-  double *pool = nullptr;
-  HIP_CHECK(qaMalloc((void **)&pool, 8 * fieldDoubles * sizeof(double)));
-  MatField F[4], Rf, T, acc, Vf;
-  for (int i = 0; i < 4; i++) F[i] = {pool + i * fieldDoubles, Vh};
-  Rf = {pool + 4 * fieldDoubles, Vh}; T = {pool + 5 * fieldDoubles, Vh}; acc = {pool + 6 * fieldDoubles, Vh}; Vf = {pool + 7 * fieldDoubles, Vh};
-  hipStream_t s = computeStream();
+  const int Vh = geom.Vh;
+  MatPool pool(Vh, 8);
+  const MatField F[4] = {pool[0], pool[1], pool[2], pool[3]}, Rf = pool[4], T = pool[5], acc = pool[6], Vf = pool[7];
   for (int mu = 0; mu < 4; mu++) extractForwardLinks(F[mu], U, mu);
   for (int mu = 0; mu < 4; mu++) {
-    HIP_CHECK(hipMemsetAsync(acc.p, 0, fieldDoubles * sizeof(double), s));
+    HIP_CHECK(hipMemsetAsync(acc.p, 0, pool.fieldDoubles() * sizeof(double), computeStream()));
     for (int i = 0; i < num_paths; i++) {
       if (coeff[i] == 0 || length[i] <= 0) continue;
-      hipLaunchKernelGGL(mf_identity_kernel, dim3(nb), dim3(bs), 0, s, Rf, Vh);
-      HIP_CHECK(hipGetLastError());
+      launchSites(mf_identity_kernel, Vh, 128, Rf, Vh);
       for (int j = length[i] - 1; j >= 0; j--) {
         const int d = path[mu][i][j];
         if (d < 4) {
@@ -171,23 +164,15 @@ static void gaugeForceTransport(MomField &mom, const GaugeField &U, double eb3, 
           shiftField(Rf, T, geom, 2 * (7 - d) + 1);
         }
       }
-      hipLaunchKernelGGL(mf_axpy_kernel, dim3(nb), dim3(bs), 0, s, acc, coeff[i], Rf, Vh);
-      HIP_CHECK(hipGetLastError());
+      launchSites(mf_axpy_kernel, Vh, 128, acc, coeff[i], Rf, Vh);
     }
     shiftField(Vf, acc, geom, 2 * mu);
-    hipLaunchKernelGGL(force_epilogue_kernel, dim3(nb), dim3(bs), 0, s, mom.data, F[mu], Vf, mu, eb3, Vh);
-    HIP_CHECK(hipGetLastError());
+    launchSites(force_epilogue_kernel, Vh, 128, mom.data, F[mu], Vf, mu, eb3, Vh);
   }
-  HIP_CHECK(hipStreamSynchronize(s));
-  HIP_CHECK(hipFree(pool));
+  HIP_CHECK(hipStreamSynchronize(computeStream()));
 }
 
-bool gaugeForceUsesTransport() {
-  bool transport = false;
-  for (int d = 0; d < 4; d++) transport = transport || commGrid().partitioned(d);
-  { const char *e = getenv("QUDA_AMD_GAUGE_FORCE_TRANSPORT"); if (e && atoi(e)) transport = true; }  // force the transport formulation (tests, timing)
-  return transport;
-}
+bool gaugeForceUsesTransport() { return usesTransport("QUDA_AMD_GAUGE_FORCE_TRANSPORT"); }   // the variable: for tests and timing
 
 void gaugeForce(MomField &mom, const GaugeField &U, double eb3, int ***path, const int *length, const double *coeff, int num_paths, int max_length) {
   if (!(U.geom == mom.geom)) errorQuda("gauge and momentum geometry differ");
@@ -213,18 +198,9 @@ void gaugeForce(MomField &mom, const GaugeField &U, double eb3, int ***path, con
   HIP_CHECK(hipStreamSynchronize(s));   // tab is a stack object
   const GaugeView g = viewOf(U);
   const int Vh = U.geom.Vh, bs = 128, nb = (2 * Vh + bs - 1) / bs;
-  const bool r12 = U.reconstruct == QUDA_RECONSTRUCT_12, r8 = U.reconstruct == QUDA_RECONSTRUCT_8;
-#define QA_GF(T) \
-  if (r12) hipLaunchKernelGGL((gauge_force_kernel<T, 12>), dim3(nb, 4), dim3(bs), 0, s, mom.data, g, eb3, Vh); \
-  else if (r8) hipLaunchKernelGGL((gauge_force_kernel<T, 8>), dim3(nb, 4), dim3(bs), 0, s, mom.data, g, eb3, Vh); \
-  else hipLaunchKernelGGL((gauge_force_kernel<T, 18>), dim3(nb, 4), dim3(bs), 0, s, mom.data, g, eb3, Vh);
-  switch (U.precision) {
-    case QUDA_DOUBLE_PRECISION: QA_GF(double) break;
-    case QUDA_SINGLE_PRECISION: QA_GF(float) break;
-    case QUDA_HALF_PRECISION: QA_GF(short) break;
-    default: errorQuda("bad gauge precision %d", U.precision);
-  }
-#undef QA_GF
+  forLinkType(U, [&](auto t, auto r) {
+    hipLaunchKernelGGL((gauge_force_kernel<decltype(t), decltype(r)::value>), dim3(nb, 4), dim3(bs), 0, s, mom.data, g, eb3, Vh);
+  });
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(s));
 }
@@ -292,35 +268,14 @@ __global__ void __launch_bounds__(128) project_su3_kernel(double *qdp, int *fail
   for (int k = 0; k < 9; k++) { o[2 * k] = sg * u.re[k]; o[2 * k + 1] = sg * u.im[k]; }
 }
 
-// one direction at a time: forward links -> kernel -> host QDP array
-template <typename Launch> static void linksToHost(void *const h_out[4], const GaugeField &U, Launch launch) {
-  const LatticeGeom &geom = U.geom;
-  const int Vh = geom.Vh;
-  double *pool = nullptr;
-  HIP_CHECK(qaMalloc((void **)&pool, (size_t)2 * 24 * Vh * sizeof(double)));
-  MatField F = {pool, Vh};
-  double *stage = (double *)stagingBuffer((size_t)geom.V * 18 * sizeof(double));
-  hipStream_t s = computeStream();
-  for (int mu = 0; mu < 4; mu++) {
-    extractForwardLinks(F, U, mu);
-    launch(stage, F, mu);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(h_out[mu], stage, (size_t)geom.V * 18 * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
-  HIP_CHECK(hipFree(pool));
-}
-
 void updateGaugeLinks(void *const h_out[4], const GaugeField &U, const MomField &mom, double dt, bool conj_mom, bool exact) {
   if (!(U.geom == mom.geom)) errorQuda("gauge and momentum geometry differ");
-  const int Vh = U.geom.Vh, bs = 128, nb = (2 * Vh + bs - 1) / bs;
-  linksToHost(h_out, U, [&](double *stage, MatField F, int mu) {
-    hipLaunchKernelGGL(gauge_update_kernel, dim3(nb), dim3(bs), 0, computeStream(), stage, F, mom.data, mu, dt, conj_mom ? 1 : 0, exact ? 1 : 0, Vh);
-  });
+  const int Vh = U.geom.Vh;
+  linksToHost(h_out, U, [&](double *stage, MatField F, int mu) { launchSites(gauge_update_kernel, Vh, 128, stage, F, mom.data, mu, dt, conj_mom ? 1 : 0, exact ? 1 : 0, Vh); });
 }
 
 long projectSU3Links(void *const h_out[4], const GaugeField &U, double tol) {
-  const int Vh = U.geom.Vh, bs = 128, nb = (2 * Vh + bs - 1) / bs;
+  const int Vh = U.geom.Vh;
   int *d_fail = nullptr;
   HIP_CHECK(qaMalloc((void **)&d_fail, sizeof(int)));
   HIP_CHECK(hipMemsetAsync(d_fail, 0, sizeof(int), computeStream()));
@@ -328,7 +283,7 @@ long projectSU3Links(void *const h_out[4], const GaugeField &U, double tol) {
   const int sliceCB = Vh / U.geom.X[3];
   linksToHost(h_out, U, [&](double *stage, MatField F, int mu) {
     const int sign_t = (mu == 3 && U.t_boundary == QUDA_ANTI_PERIODIC_T && last_t) ? sliceCB * (U.geom.X[3] - 1) : -1;
-    hipLaunchKernelGGL(project_su3_kernel, dim3(nb), dim3(bs), 0, computeStream(), stage, d_fail, F, sign_t, tol, Vh);
+    launchSites(project_su3_kernel, Vh, 128, stage, d_fail, F, sign_t, tol, Vh);
   });
   int fail = 0;
   HIP_CHECK(hipMemcpy(&fail, d_fail, sizeof(int), hipMemcpyDeviceToHost));
@@ -339,8 +294,8 @@ long projectSU3Links(void *const h_out[4], const GaugeField &U, double tol) {
 }
 
 // ---- momentum action (lib/momentum.cu:31-48): sum over links of sum_{j<6} v_j^2 + (1/2) sum_{j=6..8} v_j^2 - 4 = tr(A^dag A)/2 - 4.
-// One thread per link, one partial per block in a fixed order (lanes by shuffle, the four waves through LDS), the partials added
-// in block order by the host as in topologicalCharge: the same field gives the same bits ----
+// One thread per link, one partial per block in a fixed order (block_sum_256), the partials added in block order by the host as in
+// topologicalCharge: the same field gives the same bits ----
 __global__ void __launch_bounds__(256) mom_action_kernel(double *partial, const double *mom, long nLinks) {
   const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   double v = 0;
@@ -353,12 +308,8 @@ __global__ void __launch_bounds__(256) mom_action_kernel(double *partial, const 
     for (int j = 6; j < 9; j++) dia += m[j] * m[j];
     v = (off + 0.5 * dia) - 4.0;
   }
-  __shared__ double lds[4];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = ((lds[0] + lds[1]) + lds[2]) + lds[3];
+  v = block_sum_256(v);
+  if (threadIdx.x == 0) partial[blockIdx.x] = v;
 }
 
 double momAction(const MomField &mom) {
@@ -366,15 +317,10 @@ double momAction(const MomField &mom) {
   const int bs = 256, nb = (int)((nLinks + bs - 1) / bs);
   double *d_partial = nullptr;
   HIP_CHECK(qaMalloc((void **)&d_partial, (size_t)nb * sizeof(double)));
-  hipStream_t s = computeStream();
-  hipLaunchKernelGGL(mom_action_kernel, dim3(nb), dim3(bs), 0, s, d_partial, mom.data, nLinks);
+  hipLaunchKernelGGL(mom_action_kernel, dim3(nb), dim3(bs), 0, computeStream(), d_partial, mom.data, nLinks);
   HIP_CHECK(hipGetLastError());
-  std::vector<double> partial(nb);
-  HIP_CHECK(hipMemcpyAsync(partial.data(), d_partial, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
+  double S = sumPartials(d_partial, nb);
   HIP_CHECK(hipFree(d_partial));
-  double S = 0;
-  for (int b = 0; b < nb; b++) S += partial[b];
   comm_allreduce(&S, 1);
   return S;
 }

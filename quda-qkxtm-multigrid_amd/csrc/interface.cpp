@@ -388,6 +388,17 @@ void qudaAmdStoutSmear(unsigned int nSteps, double rho, int smear_time) {
 }
 void performSTOUTnStep(unsigned int nSteps, double rho) { qudaAmdStoutSmear(nSteps, rho, 0); }
 
+// dst[lexicographic site] = eo[even sites, then odd], realsPerSite reals a site
+static void eoToLex(double *dst, const double *eo, const LatticeGeom &g, int realsPerSite) {
+  for (long iv = 0; iv < g.V; iv++) {
+    long l = iv / g.X[0];
+    const int x = (int)(iv % g.X[0]), y = (int)(l % g.X[1]); l /= g.X[1];
+    const int z = (int)(l % g.X[2]), t = (int)(l / g.X[2]);
+    const int parity = (x + y + z + t) & 1;
+    memcpy(dst + iv * realsPerSite, eo + ((size_t)parity * g.Vh + iv / 2) * realsPerSite, realsPerSite * sizeof(double));
+  }
+}
+
 // reference lib/interface_quda.cpp:5940-5991 (lib/field_strength_tensor.cu, lib/qcharge_quda.cu)
 double qudaAmdQCharge(double *h_density, int lexicographic, int which) {
   if (!g_initialized) errorQuda("QUDA not initialized");
@@ -399,13 +410,7 @@ double qudaAmdQCharge(double *h_density, int lexicographic, int which) {
   const LatticeGeom &g = U->geom;
   std::vector<double> eo((size_t)g.V);
   const double Q = topologicalCharge(*U, eo.data());
-  for (long iv = 0; iv < g.V; iv++) {
-    long l = iv / g.X[0];
-    const int x = (int)(iv % g.X[0]), y = (int)(l % g.X[1]); l /= g.X[1];
-    const int z = (int)(l % g.X[2]), t = (int)(l / g.X[2]);
-    const int parity = (x + y + z + t) & 1;
-    h_density[iv] = eo[(size_t)parity * g.Vh + iv / 2];
-  }
+  eoToLex(h_density, eo.data(), g, 1);
   return Q;
 }
 double qChargeCuda(void) { return qudaAmdQCharge(nullptr, 0, -1); }
@@ -420,20 +425,9 @@ void qudaAmdSaveSmearedGauge(void **h_gauge, int lexicographic) {
   if (!gaugeSmeared) errorQuda("qudaAmdSaveSmearedGauge: no smeared field (call performAPEnStep first)");
   if (!lexicographic) { saveGaugeQDP(*gaugeSmeared, (void *const *)h_gauge, QUDA_DOUBLE_PRECISION); return; }
   const LatticeGeom &g = gaugeSmeared->geom;
-  std::vector<std::vector<double>> eo(4, std::vector<double>((size_t)g.V * 18));
-  void *ptr[4];
-  for (int d = 0; d < 4; d++) ptr[d] = eo[d].data();
-  saveGaugeQDP(*gaugeSmeared, ptr, QUDA_DOUBLE_PRECISION);
-  for (int d = 0; d < 4; d++) {
-    double *dst = (double *)h_gauge[d];
-    for (long iv = 0; iv < g.V; iv++) {
-      long l = iv / g.X[0];
-      const int x = (int)(iv % g.X[0]), y = (int)(l % g.X[1]); l /= g.X[1];
-      const int z = (int)(l % g.X[2]), t = (int)(l / g.X[2]);
-      const int parity = (x + y + z + t) & 1;
-      memcpy(dst + iv * 18, &eo[d][((size_t)parity * g.Vh + iv / 2) * 18], 18 * sizeof(double));
-    }
-  }
+  HostLinks eo(g.V);
+  saveGaugeQDP(*gaugeSmeared, eo.ptr, QUDA_DOUBLE_PRECISION);
+  for (int d = 0; d < 4; d++) eoToLex((double *)h_gauge[d], eo.links[d].data(), g, 18);
 }
 
 // ---- gauge molecular dynamics (gauge_md.hip).  Host links in QUDA_QDP_GAUGE_ORDER and host momenta in the MILC ten-real layout
@@ -480,14 +474,12 @@ static void keepMomentum(MomField *m, bool owned, const QudaGaugeParam *param) {
   }
 }
 // new host QDP links become the resident field, in the precisions of the resident field they replace (else of param)
-static void makeLinksResident(std::vector<std::vector<double>> &links, QudaGaugeParam *param, bool hadResident) {
-  void *ptr[4];
-  for (int d = 0; d < 4; d++) ptr[d] = links[d].data();
+static void makeLinksResident(HostLinks &links, QudaGaugeParam *param, bool hadResident) {
   QudaGaugeParam gp = hadResident ? g_gauge_param : *param;
   gp.cpu_prec = QUDA_DOUBLE_PRECISION;
   gp.gauge_order = QUDA_QDP_GAUGE_ORDER;
   if (!hadResident) checkGaugeParam(&gp);
-  loadResidentLinks(ptr, &gp);
+  loadResidentLinks(links.ptr, &gp);
   param->gaugeGiB = gp.gaugeGiB;
 }
 
@@ -522,12 +514,10 @@ void updateGaugeFieldQuda(void *gauge, void *momentum, double dt, int conj_mom, 
   GaugeField *U = mdLinks("updateGaugeFieldQuda", gauge, param, ownU);
   MomField *M = mdMomentum("updateGaugeFieldQuda", momentum, param, U->geom, true, ownM);
   const size_t n = (size_t)U->geom.V * 18;
-  std::vector<std::vector<double>> links(4, std::vector<double>(n));
-  void *ptr[4];
-  for (int d = 0; d < 4; d++) ptr[d] = links[d].data();
-  updateGaugeLinks(ptr, *U, *M, dt, conj_mom != 0, exact != 0);
+  HostLinks links(U->geom.V);
+  updateGaugeLinks(links.ptr, *U, *M, dt, conj_mom != 0, exact != 0);
   if (ownU) delete U;
-  if (param->return_result_gauge) for (int d = 0; d < 4; d++) memcpy(((void **)gauge)[d], ptr[d], n * sizeof(double));
+  if (param->return_result_gauge) for (int d = 0; d < 4; d++) memcpy(((void **)gauge)[d], links.ptr[d], n * sizeof(double));
   if (param->make_resident_gauge) makeLinksResident(links, param, !ownU);
   keepMomentum(M, ownM, param);
 }
@@ -538,13 +528,11 @@ void projectSU3Quda(void *gauge_h, double tol, QudaGaugeParam *param) {
   bool ownU;
   GaugeField *U = mdLinks("projectSU3Quda", gauge_h, param, ownU);
   const size_t n = (size_t)U->geom.V * 18;
-  std::vector<std::vector<double>> links(4, std::vector<double>(n));
-  void *ptr[4];
-  for (int d = 0; d < 4; d++) ptr[d] = links[d].data();
-  const long failures = projectSU3Links(ptr, *U, tol);
+  HostLinks links(U->geom.V);
+  const long failures = projectSU3Links(links.ptr, *U, tol);
   if (ownU) delete U;
   if (failures > 0) errorQuda("Error in the SU(3) unitarization: %ld failures", failures);
-  if (param->return_result_gauge) for (int d = 0; d < 4; d++) memcpy(((void **)gauge_h)[d], ptr[d], n * sizeof(double));
+  if (param->return_result_gauge) for (int d = 0; d < 4; d++) memcpy(((void **)gauge_h)[d], links.ptr[d], n * sizeof(double));
   if (param->make_resident_gauge) makeLinksResident(links, param, !ownU);
 }
 

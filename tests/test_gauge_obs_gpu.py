@@ -207,6 +207,29 @@ def test_charge_follows_the_resident_smeared_field(qa, oracle, cases, X):
     assert abs(qa.q_charge() - Q_thin) <= 1e-12 * scale
 
 
+# max |plaquette - reference| over (total, spatial, temporal) of the hot 4^4 field, measured on the commit before the link-type
+# dispatcher (forLinkType) existed, three loads each with the same figure; fp64 gave 0, 2.8e-17 and 2.8e-17 (18, 12, 8 reals)
+PLAQ_DEVIATION = {(4, 18): 2.025643e-10, (4, 12): 9.265036e-10, (4, 8): 2.406853e-08,
+                  (2, 18): 5.678953e-07, (2, 12): 1.874196e-07, (2, 8): 8.310244e-07}
+
+
+@pytest.mark.parametrize("recon", [18, 12, 8])
+@pytest.mark.parametrize("prec", [8, 4, 2])
+def test_plaquette_of_every_link_type(qa, oracle, cases, prec, recon):
+    """Every (precision, reconstruct) pair walks its own branch of the link-type dispatcher (through extractForwardLinks) and of the
+    loader; a swapped branch reads the links in the wrong format and moves the plaquette by 0.1 or more.  Bounds: fp64 1e-12, as the
+    other fp64 comparisons of this file; fp32 and 16-bit four times the measured deviation of that pair (the atomicAdd of the
+    plaquette sum lets the last bits vary from run to run)"""
+    X = LATTICES[0]
+    c = cases[X]
+    want = np.array(ref.plaq(c["hot_lex"]))
+    _load(qa, c["hot"], X, prec=prec, recon=recon)
+    err = np.max(np.abs(np.array(qa.plaquette()) - want))
+    tol = 1e-12 if prec == 8 else 4.0 * PLAQ_DEVIATION[prec, recon]
+    print("plaquette, precision %d, %d reals: max|delta| = %.6e (bound %.3e)" % (prec, recon, err, tol))
+    assert err <= tol
+
+
 @pytest.mark.parametrize("case,message", [("charge_of_missing_smeared_field", "no smeared field"), ("stout_without_gauge", "Gauge field must be loaded"),
                                           ("charge_without_gauge", "Gauge field must be loaded")])
 def test_error_cases(case, message):
