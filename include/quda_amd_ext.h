@@ -97,6 +97,46 @@ void qudaAmdBlasMultiCaxpyResidual(int k, void *f[], const double *c, double sca
 void qudaAmdBlasMultiCaxpy(int k, void *f[], const double *c, void *y);
 /* result = (|x|^2, |r|^2, mean over sites of |r(site)|^2 / |x(site)|^2, a site with x = 0 counting 1) */
 void qudaAmdBlasHeavyQuarkResidualNorm(const void *x, const void *r, double result[3]);
+/* ---- test hooks onto the multi-right-hand-side ("block") path (include/block.h, csrc/block_hooks.cpp) ----
+ * A block field handle is a BlockField of nSites panels of ncomp x nrhs complex numbers (nrhs <= 32) plus nGhost ghost panels; it needs
+ * no lattice.  Load / Save copy the raw device image, (nSites + nGhost) * ncomp * nrhs float2 in device order: rhs-fastest,
+ * float2 index (site * ncomp + j) * nrhs + i, or for ncomp == 12 pair-major, ((site * 6 + j / 2) * nrhs + i) * 2 + j % 2 (block.h). */
+void *qudaAmdBlockFieldCreate(int nSites, int ncomp, int nrhs, int nGhost);
+void qudaAmdBlockFieldDestroy(void *field);
+void qudaAmdBlockFieldLoad(void *field, const float *h_src);
+void qudaAmdBlockFieldSave(const void *field, float *h_dst);
+/* qudaAmdBlockBlasApply calls the function of namespace blockblas named op (its name in block.h) on block field handles of one shape.
+ * a, b, c: nrhs complex coefficients each as (re, im) pairs, or NULL.  The operands of block.h go to the slots x, y, z, w, u as follows
+ * (slots an operation does not take may be NULL):
+ *   norm2(x)  cDot(x, y)  caxpy(a; x, y)  xmy(x, y)  negate(x)  zero(x)  copy(dst = y, src = x)
+ *   cDotNormA(t = x, r = y)
+ *   bicgstabUpdate(alpha = a, omega = b; p = x, r = y, solution x = z, t = w, r0 = u)
+ *   cxpaypbz(a, b; r = x, v = y, p = z)
+ *   bicgstabDots(t = x, s = y, r0 = u)
+ *   bicgstabFused(alpha = a, omega = b, beta = c; p = x, r = y, solution x = z, t = w, v = u)
+ * result[k * nrhs + i] is sum k of right-hand side i in the order block.h lists them, a complex one as two sums (re, im): cDot 2, cDotNormA 3
+ * (dot, norm), bicgstabUpdate 3 (rho, r2), bicgstabDots 7 (ts, tt, r0s, r0t), norm2 and bicgstabFused 1.  Returns the sums per right-hand side. */
+int qudaAmdBlockBlasApply(const char *op, const double *a, const double *b, const double *c, void *x, void *y, void *z, void *w, void *u, double *result);
+/* the minimal-residual updates with their sums as INPUTS: s3[3 nrhs] = [Re (w1, r) | Im (w1, r) | |w1|^2] and, for steps = 2,
+ * s7[7 nrhs] = [Re, Im (w2, w1) | |w2|^2 | Re, Im (r, w1) | Re, Im (r, w2)] are copied to device memory, then steps = 1 calls
+ * blockblas::mrUpdateDev(x, r, rin, Ar = w1) and steps = 2 blockblas::mr2UpdateDev(x, r, rin, w1, w2) (12-component fields, 4 or 8 right-hand sides) */
+void qudaAmdBlockMrUpdate(int steps, double omega, int fresh, int needResidual, const double *s3, const double *s7, void *x, void *r, void *rin, void *w1, void *w2);
+/* blockPack / blockUnpack between n >= nrhs full fp32 qudaAmdSpinor fields and a block (parity -1: both halves, nSites = volume; 0 / 1: that
+ * half, nSites = volumeCB), and blockPackParity / blockUnpackParity between n <= nrhs single-parity fp32 fields and a 12-component block of
+ * volumeCB sites: a NULL entry is a column of zeros on pack and is left alone on unpack; accumulate != 0: block += fields */
+void qudaAmdBlockPack(void *block, void *spinors[], int n, int parity);
+void qudaAmdBlockUnpack(void *block, void *spinors[], int n, int parity);
+void qudaAmdBlockPackParity(void *block, void *spinors[], int n, int accumulate);
+void qudaAmdBlockUnpackParity(void *block, void *spinors[], int n);
+/* ghost panels a block field needs behind its local ones to be the hop input of the fine stencil under the current partition:
+ * blockGhost(X, parityField).nGhost of the resident lattice (0 on an unpartitioned one) */
+int qudaAmdBlockGhostPanels(int parityField);
+/* one launch of applyFineBlockParity on the resident precise links (fp32: cuda_prec = 4), single-parity 12-component block fields:
+ * out = s0 (1 + i a0 g5) in_same + k1 (1 + i a1 g5) [8 hops of in_other] on the sites of `parity`; in_same may be NULL with s0 = 0; on a
+ * partitioned lattice in_other must carry qudaAmdBlockGhostPanels(1) ghost panels (they are filled here).  mode 0: no inner products.
+ * mode 1, 2, 3 (dslash.h FineBlockDots, a = dotA; NULL for mode 3): the epilogue sums, finished by fineBlockDotsFinish (deviceSums = 0) or
+ * by fineBlockDotsFinishDev into device memory and copied back (deviceSums != 0), in sums[k * nrhs + i] */
+void qudaAmdBlockFineApply(void *out, void *in_same, void *in_other, void *dotA, int parity, double s0, double a0, double k1, double a1, int mode, int deviceSums, double *sums);
 /* out = (M^dag M + shift) in through the DiracMdagM functor the solvers use; shift = 0 launches exactly what qudaAmdDiracMdagM does */
 void qudaAmdDiracMdagMShift(void *dirac, void *out, const void *in, double shift);
 /* device-event timed loops for tools/cg_timing.py, seconds per pass:

@@ -131,6 +131,9 @@ EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLo
                  "qudaAmdNdegTwist", "qudaAmdStoutSmear", "qudaAmdQCharge", "qudaAmdSu3ExpIQ",
                  "qudaAmdBlasApply", "qudaAmdBlasDevUpdate", "qudaAmdBlasMultiSupported", "qudaAmdBlasMultiDot", "qudaAmdBlasMultiCaxpyResidual",
                  "qudaAmdBlasMultiCaxpy", "qudaAmdBlasHeavyQuarkResidualNorm",
+                 "qudaAmdBlockFieldCreate", "qudaAmdBlockFieldDestroy", "qudaAmdBlockFieldLoad", "qudaAmdBlockFieldSave", "qudaAmdBlockBlasApply",
+                 "qudaAmdBlockMrUpdate", "qudaAmdBlockPack", "qudaAmdBlockUnpack", "qudaAmdBlockPackParity", "qudaAmdBlockUnpackParity",
+                 "qudaAmdBlockGhostPanels", "qudaAmdBlockFineApply",
                  "qudaAmdFermionOprodForce", "qudaAmdComputeTMForce", "qudaAmdFermForceLastKernelSecs"]
 
 _lib = None
@@ -242,6 +245,28 @@ def lib():
         L.qudaAmdBlasMultiCaxpy.restype = None
         L.qudaAmdBlasHeavyQuarkResidualNorm.argtypes = [_p, _p, C.POINTER(_d)]
         L.qudaAmdBlasHeavyQuarkResidualNorm.restype = None
+        if hasattr(L, "qudaAmdBlockFieldCreate"):   # absent from a build of an earlier commit loaded through QUDA_AMD_LIBRARY
+            L.qudaAmdBlockFieldCreate.argtypes = [_i, _i, _i, _i]
+            L.qudaAmdBlockFieldCreate.restype = _p
+            L.qudaAmdBlockFieldDestroy.argtypes = [_p]
+            L.qudaAmdBlockFieldDestroy.restype = None
+            L.qudaAmdBlockFieldLoad.argtypes = [_p, _p]
+            L.qudaAmdBlockFieldLoad.restype = None
+            L.qudaAmdBlockFieldSave.argtypes = [_p, _p]
+            L.qudaAmdBlockFieldSave.restype = None
+            L.qudaAmdBlockBlasApply.argtypes = [C.c_char_p, _p, _p, _p, _p, _p, _p, _p, _p, _p]
+            L.qudaAmdBlockBlasApply.restype = _i
+            L.qudaAmdBlockMrUpdate.argtypes = [_i, _d, _i, _i, _p, _p, _p, _p, _p, _p, _p]
+            L.qudaAmdBlockMrUpdate.restype = None
+            for name in ("qudaAmdBlockPack", "qudaAmdBlockUnpack", "qudaAmdBlockPackParity"):
+                getattr(L, name).argtypes = [_p, C.POINTER(_p), _i, _i]
+                getattr(L, name).restype = None
+            L.qudaAmdBlockUnpackParity.argtypes = [_p, C.POINTER(_p), _i]
+            L.qudaAmdBlockUnpackParity.restype = None
+            L.qudaAmdBlockGhostPanels.argtypes = [_i]
+            L.qudaAmdBlockGhostPanels.restype = _i
+            L.qudaAmdBlockFineApply.argtypes = [_p, _p, _p, _p, _i, _d, _d, _d, _d, _i, _i, _p]
+            L.qudaAmdBlockFineApply.restype = None
         L.qudaAmdDiracMdagMShift.argtypes = [_p, _p, _p, _d]
         L.qudaAmdDiracMdagMShift.restype = None
         L.qudaAmdTimeMdagM.argtypes = [_p, _p, _p, _i]
@@ -611,6 +636,104 @@ def heavy_quark_residual_norm(x, r):
     s = (_d * 3)()
     lib().qudaAmdBlasHeavyQuarkResidualNorm(x.h, r.h, s)
     return s[0], s[1], s[2]
+
+
+class BlockField:
+    """qudaAmdBlockField*: a multi-right-hand-side field (include/block.h) of nsites panels of ncomp x nrhs complex numbers and nghost ghost
+    panels, free of any lattice.  load / save move the raw device image: float32, (nsites + nghost) * ncomp * nrhs * 2 reals in device order"""
+
+    def __init__(self, nsites, ncomp, nrhs, nghost=0):
+        self.nsites, self.ncomp, self.nrhs, self.nghost = int(nsites), int(ncomp), int(nrhs), int(nghost)
+        self.nreal = 2 * (self.nsites + self.nghost) * self.ncomp * self.nrhs
+        self.h = lib().qudaAmdBlockFieldCreate(self.nsites, self.ncomp, self.nrhs, self.nghost)
+
+    def load(self, image):
+        image = np.ascontiguousarray(image, dtype=np.float32)
+        if image.size != self.nreal:
+            raise ValueError("device image of %d reals, the field holds %d" % (image.size, self.nreal))
+        lib().qudaAmdBlockFieldLoad(self.h, _vp(image))
+        return self
+
+    def save(self):
+        out = np.empty(self.nreal, dtype=np.float32)
+        lib().qudaAmdBlockFieldSave(self.h, _vp(out))
+        return out
+
+    def free(self):
+        if self.h:
+            lib().qudaAmdBlockFieldDestroy(self.h)
+            self.h = None
+
+
+# operand of include/block.h -> slot of qudaAmdBlockBlasApply (quda_amd_ext.h)
+BLOCK_BLAS_SLOTS = {"norm2": {"x": "x"}, "cDot": {"x": "x", "y": "y"}, "caxpy": {"x": "x", "y": "y"}, "cDotNormA": {"t": "x", "r": "y"},
+                    "bicgstabUpdate": {"p": "x", "r": "y", "x": "z", "t": "w", "r0": "u"}, "cxpaypbz": {"r": "x", "v": "y", "p": "z"},
+                    "bicgstabDots": {"t": "x", "s": "y", "r0": "u"}, "bicgstabFused": {"p": "x", "r": "y", "x": "z", "t": "w", "v": "u"},
+                    "xmy": {"x": "x", "y": "y"}, "negate": {"x": "x"}, "copy": {"src": "x", "dst": "y"}, "zero": {"x": "x"}}
+
+
+def block_blas_apply(op, a=None, b=None, c=None, **fields):
+    """qudaAmdBlockBlasApply: blockblas::<op> on BlockFields given under their names in include/block.h (BLOCK_BLAS_SLOTS); a, b, c: one
+    complex coefficient per right-hand side, in the order of the function's coefficient arguments.  Returns the sums as an array [sum][rhs]"""
+    slots = BLOCK_BLAS_SLOTS[op]
+    if set(fields) != set(slots):
+        raise ValueError("%s takes the operands %s" % (op, sorted(slots)))
+    h = {slots[n]: f.h for n, f in fields.items()}
+    nrhs = next(iter(fields.values())).nrhs
+    co = [None if v is None else _complex_list(list(v)) for v in (a, b, c)]
+    if any(v is not None and len(v) != nrhs for v in (a, b, c)):
+        raise ValueError("one coefficient per right-hand side")
+    r = (_d * (8 * 32))()
+    n = lib().qudaAmdBlockBlasApply(op.encode(), co[0], co[1], co[2], *[h.get(k) for k in "xyzwu"], r)
+    return np.array(r[:n * nrhs], dtype=np.float64).reshape(n, nrhs)
+
+
+def block_mr_update(steps, omega, fresh, need_residual, s3, s7, x, r, rin, w1, w2=None):
+    """qudaAmdBlockMrUpdate: blockblas::mrUpdateDev (steps 1) / mr2UpdateDev (steps 2) with the sums s3[3][nrhs], s7[7][nrhs] given by the caller"""
+    s3 = np.ascontiguousarray(s3, dtype=np.float64).reshape(-1)
+    s7 = None if s7 is None else np.ascontiguousarray(s7, dtype=np.float64).reshape(-1)
+    if s3.size != 3 * x.nrhs or (s7 is not None and s7.size != 7 * x.nrhs):
+        raise ValueError("s3 holds 3 and s7 7 sums per right-hand side")
+    lib().qudaAmdBlockMrUpdate(int(steps), float(omega), int(bool(fresh)), int(bool(need_residual)), _vp(s3), None if s7 is None else _vp(s7),
+                               x.h, r.h, rin.h, w1.h, w2.h if w2 is not None else None)
+
+
+def _spinor_handles(spinors):
+    return (_p * max(len(spinors), 1))(*[f.h if f is not None else None for f in spinors])
+
+
+def block_pack(block, spinors, parity=-1):
+    """qudaAmdBlockPack: full fp32 Spinors -> the columns of block (parity -1: both halves, 0 / 1: that half only)"""
+    lib().qudaAmdBlockPack(block.h, _spinor_handles(spinors), len(spinors), int(parity))
+
+
+def block_unpack(block, spinors, parity=-1):
+    lib().qudaAmdBlockUnpack(block.h, _spinor_handles(spinors), len(spinors), int(parity))
+
+
+def block_pack_parity(block, spinors, accumulate=False):
+    """qudaAmdBlockPackParity: single-parity fp32 Spinors (None: a column of zeros) -> the first len(spinors) columns of a 12-component block"""
+    lib().qudaAmdBlockPackParity(block.h, _spinor_handles(spinors), len(spinors), int(bool(accumulate)))
+
+
+def block_unpack_parity(block, spinors):
+    """qudaAmdBlockUnpackParity: the columns of block -> single-parity fp32 Spinors (None: that column is skipped)"""
+    lib().qudaAmdBlockUnpackParity(block.h, _spinor_handles(spinors), len(spinors))
+
+
+def block_ghost_panels(parity_field=True):
+    """qudaAmdBlockGhostPanels: ghost panels a hop input of the multi-right-hand-side stencil carries under the current partition"""
+    return int(lib().qudaAmdBlockGhostPanels(int(bool(parity_field))))
+
+
+def block_fine_apply(out, in_same, in_other, parity, s0, a0, k1, a1, mode=0, dot_a=None, device_sums=False):
+    """qudaAmdBlockFineApply: one parity launch of the multi-right-hand-side fine stencil on the resident fp32 links; mode 1, 2, 3: returns
+    its epilogue sums [sum][rhs] (through fineBlockDotsFinishDev if device_sums), mode 0: None"""
+    ns = {0: 0, 1: 2, 2: 7, 3: 3}[int(mode)]
+    sums = np.zeros(max(ns, 1) * out.nrhs, dtype=np.float64)
+    lib().qudaAmdBlockFineApply(out.h, in_same.h if in_same is not None else None, in_other.h, dot_a.h if dot_a is not None else None, int(parity),
+                                float(s0), float(a0), float(k1), float(a1), int(mode), int(bool(device_sums)), _vp(sums))
+    return sums.reshape(-1, out.nrhs) if ns else None
 
 
 def multi_src_stats():

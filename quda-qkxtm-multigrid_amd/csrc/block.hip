@@ -139,6 +139,9 @@ template <int MODE> __global__ void __launch_bounds__(256) block_fine_pack_kerne
 }
 static FinePtrs finePtrs(const ColorSpinorField *const *f, int n, const BlockField &b, int &stride) {
   if (n > b.nrhs || b.ncomp != 12 || !b.pairMajor) errorQuda("%d fine fields for a block of %d right-hand sides x %d components", n, b.nrhs, b.ncomp);
+  // block_fine_pack_kernel stages 64 sites x (6 nrhs + 1) words in LDS: past 10 right-hand sides that is more than the 64 KiB a launch may ask
+  // for without raising the kernel's limit, and the launch would fail.  Its callers pack 4 or 8.
+  if ((size_t)64 * (6 * b.nrhs + 1) * sizeof(float4) > ((size_t)64 << 10)) errorQuda("single-parity pack of %d right-hand sides: the staging buffer does not fit 64 KiB of LDS (at most 10)", b.nrhs);
   FinePtrs p;
   memset(&p, 0, sizeof(p));
   stride = 0;

@@ -102,7 +102,7 @@ template <int NRHS, int CL = 0, int XY = 0> __global__ void __launch_bounds__(25
   constexpr int SPB = NRHS == 24 ? 8 : 256 / NRHS;   // sites per work-group (192 threads for 24 right-hand sides, else 256)
   constexpr int USTR = 8 * 18 + 4;                    // floats per site of staged links: 148 = 20 mod 32, the up to 8 sites of a wave start on 8 different banks
   constexpr int TSTR = 144 + 4;                       // the dense clover-twist matrices of a site: 2 x 36 complex, same bank spread
-  __shared__ float ulds[SPB * USTR];
+  __shared__ __attribute__((aligned(16))) float ulds[SPB * USTR];
   __shared__ __attribute__((aligned(16))) float tlds[CL ? SPB * TSTR : 4];
   const int s = threadIdx.x / NRHS, i = threadIdx.x - s * NRHS;
   extern __shared__ __attribute__((aligned(16))) float plds[];   // XY: staged x / y neighbour panels
@@ -389,32 +389,34 @@ template <int NRHS, int CL = 0, int XY = 0> __global__ void __launch_bounds__(25
       unpack_panel(av, ra);
     }
     const int ns = arg.dotMode == 1 ? 2 : (arg.dotMode == 3 ? 3 : 7);
-    float sm[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (arg.dotMode == 3) {
+    // the products of two fp32 numbers are exact in fp64 and the site sums are taken in fp64: the sums carry only the rounding of their fp64
+    // additions.  (Site sums in fp32 were off by ~2e-8 of the sum of the absolute values of their terms; the minimal-residual coefficients
+    // formed from them then differ from the exact ones in BOTH parts by that much of |alpha|, which an element-wise comparison of the update
+    // with its reference sees amplified by |alpha| / |Im alpha|.)
+    double sm[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    // one component at a time, its operands taken through an opaque copy and fenced: the conversions to fp64 stay next to their use
+    auto dbl = [](float v) -> double { asm volatile("" : "+v"(v)); return (double)v; };
 #pragma unroll
-      for (int j = 0; j < 12; j++) {
-        const float orr = outv[2 * j], oi = outv[2 * j + 1], sr = same[2 * j], si = same[2 * j + 1];
+    for (int j = 0; j < 12; j++) {
+      const double orr = dbl(outv[2 * j]), oi = dbl(outv[2 * j + 1]);
+      if (arg.dotMode != 1) {
+        const double sr = dbl(same[2 * j]), si = dbl(same[2 * j + 1]);
         sm[0] += orr * sr + oi * si; sm[1] += orr * si - oi * sr;    // conj(out) same
         sm[2] += orr * orr + oi * oi;
+        if (arg.dotMode == 2) {
+          const double ar = dbl(av[2 * j]), ai = dbl(av[2 * j + 1]);
+          sm[3] += ar * sr + ai * si; sm[4] += ar * si - ai * sr;      // conj(a) same
+          sm[5] += ar * orr + ai * oi; sm[6] += ar * oi - ai * orr;    // conj(a) out
+        }
+      } else {
+        const double ar = dbl(av[2 * j]), ai = dbl(av[2 * j + 1]);
+        sm[0] += ar * orr + ai * oi; sm[1] += ar * oi - ai * orr;      // conj(a) out
       }
-    } else if (arg.dotMode == 1) {
-#pragma unroll
-      for (int j = 0; j < 12; j++) {
-        sm[0] += av[2 * j] * outv[2 * j] + av[2 * j + 1] * outv[2 * j + 1];       // conj(a) out
-        sm[1] += av[2 * j] * outv[2 * j + 1] - av[2 * j + 1] * outv[2 * j];
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 12; j++) {
-        const float orr = outv[2 * j], oi = outv[2 * j + 1], sr = same[2 * j], si = same[2 * j + 1], ar = av[2 * j], ai = av[2 * j + 1];
-        sm[0] += orr * sr + oi * si; sm[1] += orr * si - oi * sr;    // conj(out) same
-        sm[2] += orr * orr + oi * oi;
-        sm[3] += ar * sr + ai * si; sm[4] += ar * si - ai * sr;      // conj(a) same
-        sm[5] += ar * orr + ai * oi; sm[6] += ar * oi - ai * orr;    // conj(a) out
-      }
+      __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();   // every wave is through its hops: the staged links are dead, their LDS holds the partial sums now
-    float *red = ulds;
+    static_assert(NRHS > 8 || sizeof(ulds) >= 7 * 256 * sizeof(double), "the partial sums must fit the staged links' LDS");
+    double *red = reinterpret_cast<double *>(ulds);   // 7 x 256 doubles = 14 KB of the >= 18.5 KB of staged links
     for (int k = 0; k < ns; k++) red[k * 256 + threadIdx.x] = sm[k];
     __syncthreads();
     if ((int)threadIdx.x < ns * NRHS) {
@@ -422,7 +424,7 @@ template <int NRHS, int CL = 0, int XY = 0> __global__ void __launch_bounds__(25
       int nact = SPB;
       if (!arg.tile) { const int left = arg.Vh - idx0; nact = left < SPB ? left : SPB; }
       double t = 0.0;
-      for (int ss = 0; ss < nact; ss++) t += (double)red[k * 256 + ss * NRHS + ii];
+      for (int ss = 0; ss < nact; ss++) t += red[k * 256 + ss * NRHS + ii];
       arg.dotPart[((size_t)blockIdx.x * ns + k) * NRHS + ii] = t;
     }
   }
@@ -600,6 +602,9 @@ void applyFineBlockParity(float2 *out, const float2 *in_same, const float2 *in_o
     if (dots->mode < 1 || dots->mode > 3) errorQuda("inner-product mode %d", dots->mode);
     if (dots->mode >= 2 && s0 == 0.0) errorQuda("inner products with the same-parity input, but that input is switched off");
     const int ns = fbDotSums(dots->mode);
+    // the first ns * nrhs threads of a work-group write its row of partial sums, and the threads of sites past Vh have left the kernel by
+    // then: a last work-group with fewer than ns live sites would leave part of its row unwritten.  Vh of an even lattice is a multiple of 8 > ns.
+    if (g.Vh % spb && g.Vh % spb < ns) errorQuda("inner products in the stencil epilogue: the last work-group holds %d sites, mode %d needs %d", g.Vh % spb, dots->mode, ns);
     const size_t need = (size_t)nb * ns * nrhs * sizeof(double);
     if (need > g_fbPartBytes) {
       if (g_fbPart) poolDeviceFree(g_fbPart, 0);
