@@ -127,6 +127,9 @@ class cpuColorSpinorField : public ColorSpinorField {
 };
 
 void copyColorSpinor(ColorSpinorField &dst, const ColorSpinorField &src);
+// uniform(0,1) random spinor from a counter-based generator keyed by (seed, global site, component): the same field for
+// any process grid (reference uses a private rand48 clone, lib/color_spinor_util.cu:12-22)
+void spinorRandom(ColorSpinorField &f, unsigned long long seed);
 
 // ------------------------------------------------------------------------------------------------
 // Fine-grid SU(3) gauge field in the bidirectional device layout described at the top of this file.

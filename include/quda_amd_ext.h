@@ -182,6 +182,16 @@ void qudaAmdMultigridGetCoarseLinks(void *mg_instance, int level, float *h_Y, fl
 /* op 0: R (level -> level+1; lib/restrictor.cu), 1: P (level+1 -> level; lib/prolongator.cu), 2: M of `level`,
  * 3: one multigrid cycle of `level`, x = K b (MG::operator(), lib/multigrid.cpp:488-604) */
 void qudaAmdMultigridApply(void *mg_instance, int level, int op, float *h_out, const float *h_in);
+/* The transfer operators of `level` one by one, on host vectors in the layout of qudaAmdMultigridApply; several vectors lie back to back.
+ * parity -1: full fine fields.  parity 0 / 1: Transfer::setSiteSubset(QUDA_PARITY_SITE_SUBSET, parity) for the call (the previous subset
+ * is restored), single-parity fine fields: the other parity of a fine input is ignored, that of a fine result is reported as zeros.
+ *   op 0  R        1 fine -> 1 coarse                     op 1  P        1 coarse -> 1 fine
+ *   op 2  R4       4 fine -> 4 coarse                     op 3  P4       4 coarse -> 4 fine
+ *   op 4  R4Block  4 fine -> 4 coarse; the sources go through blockPackParity into columns 4..7 of an 8-column parity block field whose
+ *                  columns 0..3 hold the same sources in reverse order (parity >= 0 only)
+ *   op 5  P4Block  accumulate = 0, op 6: accumulate = 1.  h_in: 4 coarse vectors, then the 8 fine vectors the 8-column parity block
+ *                  field is preloaded with; the prolongation goes to columns 4..7; h_out: all 8 columns as fine vectors (parity >= 0 only) */
+void qudaAmdMultigridApplyTransfer(void *mg_instance, int level, int op, int parity, float *h_out, const float *h_in);
 /* The operator of a COARSE level applied to nrhs (8, 16, 24 or 32) host vectors at once through the multi-right-hand-side kernel
  * on the matrix cores (v_mfma_f32_16x16x4_f32; the reference's multi-source coarse Dslash, lib/dslash_coarse.cu:294-333): the
  * vectors lie back to back in h_in / h_out, each in the layout of qudaAmdMultigridApply.  niter > 0 additionally times niter

@@ -22,7 +22,7 @@ class Transfer {
   int fineSpin, fineColor;     // of the level this transfer starts from
   int Xf[4], Xc[4];            // fine / coarse full lattice extents
   int blockVol;                // sites per aggregate
-  bool parityMajor = false;    // sites of an aggregate numbered even half first (transfer.hip block_coords), else lexicographically
+  bool parityMajor = false;    // sites of an aggregate numbered even half first (transfer_device.h block_coords), else lexicographically
   int lastGsFallbackBlocks = 0; // (aggregate, chirality) blocks the CholeskyQR2 orthonormalisation handed to Gram-Schmidt (ill-conditioned in fp32)
   int nAgg;                    // aggregates = coarse volume
   long fineVol;
@@ -56,7 +56,7 @@ class Transfer {
   void RSplit(ColorSpinorField &leaving, ColorSpinorField &staying, const ColorSpinorField &fine, int dir) const;
   // the same for four fine vectors (each with its own direction) in ONE pass over V; fine level only (canSplit4)
   bool canSplit4() const;
-  // direct Galerkin construction of the first coarse level on the matrix cores (transfer.hip galerkin_vuv_kernel; reference ComputeVUV,
+  // direct Galerkin construction of the first coarse level on the matrix cores (transfer_setup.hip galerkin_vuv_kernel; reference ComputeVUV,
   // lib/coarse_op.cuh:487-600): forward link 2 mu and in-aggregate part S (slot 8, accumulated over the directions) of every coarse site
   // from UV = dslash.h galerkinUV(V); 4^4 aggregates of a 4 x 3 fine level, Nvec 8 / 24, unpartitioned
   bool canDirectGalerkin() const;
@@ -77,10 +77,6 @@ class Transfer {
   void createGeoMap();
   void fillAndOrthonormalise(const std::vector<ColorSpinorField *> &B);
 };
-
-// uniform(0,1) random spinor from a counter-based generator keyed by (seed, global site, component): the same field for
-// any process grid (reference uses a private rand48 clone, lib/color_spinor_util.cu:12-22)
-void spinorRandom(ColorSpinorField &f, unsigned long long seed);
 
 // half-precision storage switch of the hierarchy (coarse.hip): R, P and the coarse operators stream fp16 mirrors of V / Y when set
 void setCoarseHalfStorage(bool on);

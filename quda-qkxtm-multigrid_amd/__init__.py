@@ -120,7 +120,7 @@ EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLo
                  "qudaAmdSetPartitionMask", "qudaAmdComputeStream", "qudaAmdDeviceSynchronize", "qudaAmdHaloTransport", "qudaAmdHaloWireFormat", "qudaAmdSetDslashTune", "qudaAmdCommGetUniqueId",
                  "qudaAmdCommInit", "qudaAmdCommRank", "qudaAmdCommSize", "qudaAmdCommCoords", "qudaAmdCommBarrier", "qudaAmdCommAllreduce", "qudaAmdCommAllreduceMax",
                  "qudaAmdMultigridVerify", "qudaAmdMultigridCycle", "qudaAmdTimeAxpy", "qudaAmdMultigridLevels", "qudaAmdMultigridLevelInfo",
-                 "qudaAmdMultigridSetHalfStorage", "qudaAmdMultigridGetNullVector", "qudaAmdMultigridGetV", "qudaAmdMultigridGetCoarseLinks", "qudaAmdMultigridApply", "qudaAmdMultigridApplyBlock",
+                 "qudaAmdMultigridSetHalfStorage", "qudaAmdMultigridGetNullVector", "qudaAmdMultigridGetV", "qudaAmdMultigridGetCoarseLinks", "qudaAmdMultigridApply", "qudaAmdMultigridApplyTransfer", "qudaAmdMultigridApplyBlock",
                  "qudaAmdMultigridTimeApply", "qudaAmdMultigridTimeTransfer", "qudaAmdSetExitLine", "qudaAmdDiracPrepare", "qudaAmdDiracReconstruct", "qudaAmdSpinorRawInfo", "qudaAmdGaugeRawInfo", "qudaAmdCloverRawInfo", "qudaAmdRawDeviceCopy",
                  "qudaAmdSetSolutionSink", "qudaAmdCommStats", "qudaAmdDescribeHaloError", "qudaAmdMultigridOrthoFallbackBlocks", "qudaAmdProfileMarker", "qudaAmdAccountStart", "qudaAmdAccountDump", "qudaAmdWriteSpinorFields", "qudaAmdReadSpinorFields", "qudaAmdMultigridRefine", "qudaAmdMultigridSetFused", "qudaAmdMultigridFusedStats", "qudaAmdMultiSrcStats", "qudaAmdTwopMomenta", "qudaAmdTwopTimeExtent", "qudaAmdContractTwop", "qudaAmdSetTwopOutput",
                  "qudaAmdLoopMomenta", "qudaAmdContractLoop", "qudaAmdSetLoopOutput", "qudaAmdLoopLastTimings",
@@ -305,6 +305,7 @@ def lib():
         L.qudaAmdMultigridGetV.argtypes = [_p, _i, _p]
         L.qudaAmdMultigridGetCoarseLinks.argtypes = [_p, _i, _p, _p]
         L.qudaAmdMultigridApply.argtypes = [_p, _i, _i, _p, _p]
+        L.qudaAmdMultigridApplyTransfer.argtypes = [_p, _i, _i, _i, _p, _p]
         L.qudaAmdMultigridSetFused.argtypes = [_i]
         L.qudaAmdMultigridSetFused.restype = None
         L.qudaAmdMultigridFusedStats.argtypes = [_p, _i, _p]
@@ -1461,6 +1462,25 @@ class Multigrid:
         out = np.zeros(shape_out, dtype=np.complex64)
         lib().qudaAmdMultigridApply(self.h, level, {"R": 0, "P": 1, "M": 2, "K": 3}[op], _vp(out), _vp(h_in))
         return out
+
+    TRANSFER_OPS = {"R": 0, "P": 1, "R4": 2, "P4": 3, "R4Block": 4, "P4Block": 5, "P4Block+": 6}
+
+    def apply_transfer(self, level, op, h_in, parity=-1, preload=None):
+        """one transfer operator of `level` on host vectors (qudaAmdMultigridApplyTransfer): 'R' / 'P' on one vector, 'R4' / 'P4' and
+        'R4Block' on four (leading axis 4), 'P4Block' / 'P4Block+' (accumulate) on four coarse vectors with `preload` = the eight fine
+        vectors the block field holds beforehand, returning all eight columns.  parity 0 / 1: single-parity fine fields"""
+        i = self.level_info(level)
+        fine_shape = (int(np.prod(i["Xf"])), i["fineSpin"], i["fineColor"])
+        coarse_shape = (int(np.prod(i["Xc"])), 2, i["Nvec"])
+        code = self.TRANSFER_OPS[op]
+        n = 1 if code < 2 else 4
+        restrict = op.startswith("R")
+        h_in = np.ascontiguousarray(h_in, dtype=np.complex64).reshape((n,) + (fine_shape if restrict else coarse_shape))
+        if code >= 5:
+            h_in = np.concatenate([h_in.reshape(-1), np.ascontiguousarray(preload, dtype=np.complex64).reshape((8,) + fine_shape).reshape(-1)])
+        out = np.zeros(((8 if code >= 5 else n),) + (coarse_shape if restrict else fine_shape), dtype=np.complex64)
+        lib().qudaAmdMultigridApplyTransfer(self.h, int(level), code, int(parity), _vp(out), _vp(h_in))
+        return out[0] if n == 1 else out
 
     def fused_stats(self, level):
         """None if `level` does not run its cycle as one persistent kernel (coarse_cycle.h), else the last launch's counters"""

@@ -178,6 +178,62 @@ void qudaAmdMultigridApply(void *mg_instance, int level, int op, float *h_out, c
   delete fin; delete fout;
 }
 
+// The transfer operators of `level` one by one (quda_amd_ext.h lists the ops): the quad and block-column variants and the single-parity route,
+// which the library itself reaches only from inside a solve.  parity 0 / 1: the transfer is set to that parity subset for the call, the fine
+// operands are the parity views of full device fields (the other half of an input stays loaded and must be ignored, the other half of an
+// output stays zero).
+void qudaAmdMultigridApplyTransfer(void *mg_instance, int level, int op, int parity, float *h_out, const float *h_in) {
+  MG *m = levelOf(mg_instance, level);
+  Transfer *T = const_cast<Transfer *>(m->getTransfer());
+  if (!T) errorQuda("level %d is the coarsest level: no transfer", level);
+  if (op < 0 || op > 6) errorQuda("unknown transfer op %d", op);
+  if (parity < -1 || parity > 1) errorQuda("parity %d (-1: full fields, 0 / 1)", parity);
+  const bool block = op >= 4, isR = op == 0 || op == 2 || op == 4;
+  if (block && parity < 0) errorQuda("the block-column transfers work on one parity");
+  const int nsrc = op < 2 ? 1 : 4, col0 = 4, nrhs = 8;
+  const int nfine = block ? nrhs : nsrc;   // fine fields on the device: the block ops fill / return all eight columns
+  const ColorSpinorField &proto = *m->nullVectors()[0];
+  std::vector<ColorSpinorField *> fine(nfine), coarse(nsrc);
+  for (auto &f : fine) { ColorSpinorParam p = proto.param(); p.create = QUDA_ZERO_FIELD_CREATE; f = new ColorSpinorField(p); }
+  for (auto &c : coarse) c = T->createCoarseField();
+  const size_t flen = (size_t)proto.Volume() * proto.Nspin() * proto.Ncolor() * 2, clen = (size_t)T->nAgg * 2 * T->Nvec * 2;
+  // host -> device.  Restrictors: nsrc fine vectors.  Prolongators: nsrc coarse vectors, for the block op followed by the eight fine
+  // vectors the block field is preloaded with.
+  for (int s = 0; s < nsrc; s++) {
+    ColorSpinorField &d = isR ? *fine[block ? col0 + s : s] : *coarse[s];
+    d = hostView(d, const_cast<float *>(h_in) + s * (isR ? flen : clen));
+  }
+  if (block && isR) for (int s = 0; s < 4; s++) blas::copy(*fine[s], *fine[col0 + 3 - s]);   // columns 0..3: the sources in reverse order
+  if (block && !isR) for (int i = 0; i < nrhs; i++) *fine[i] = hostView(*fine[i], const_cast<float *>(h_in) + 4 * clen + i * flen);
+  const QudaSiteSubset subset0 = T->site_subset;
+  const QudaParity parity0 = T->subset_parity;
+  if (parity >= 0) T->setSiteSubset(QUDA_PARITY_SITE_SUBSET, parity ? QUDA_ODD_PARITY : QUDA_EVEN_PARITY);
+  std::vector<ColorSpinorField *> f(nfine);
+  for (int i = 0; i < nfine; i++) f[i] = parity < 0 ? fine[i] : (parity ? &fine[i]->Odd() : &fine[i]->Even());
+  if (op == 0) T->R(*coarse[0], *f[0]);
+  else if (op == 1) T->P(*f[0], *coarse[0]);
+  else if (op == 2) T->R4(coarse.data(), f.data());
+  else if (op == 3) T->P4(f.data(), coarse.data());
+  else {
+    BlockField b(proto.VolumeCB(), 12, nrhs);
+    blockPackParity(b, f.data(), nrhs);
+    if (isR) T->R4Block(coarse.data(), b.v, nrhs, col0);
+    else { T->P4Block(b.v, nrhs, col0, op == 6, coarse.data()); blockUnpackParity(f.data(), nrhs, b); }
+    HIP_CHECK(hipStreamSynchronize(computeStream()));   // b returns to the pool at the end of this scope
+  }
+  T->setSiteSubset(subset0, parity0);
+  if (!isR && parity >= 0 && block)   // only the parity views came back from the block: the other half reports as zero
+    for (int i = 0; i < nrhs; i++) blas::zero(parity ? fine[i]->Even() : fine[i]->Odd());
+  const int nout = isR ? nsrc : nfine;
+  for (int s = 0; s < nout; s++) {
+    ColorSpinorField &d = isR ? *coarse[s] : *fine[s];
+    ColorSpinorField h = hostView(d, h_out + s * (isR ? clen : flen));
+    h = d;
+  }
+  for (auto p : fine) delete p;
+  for (auto p : coarse) delete p;
+}
+
 // the cycle below a coarse level as one persistent kernel (coarse_cycle.h): process-wide switch and the statistics of the last launch of `level`
 void qudaAmdMultigridSetFused(int on) { coarseCycleSetEnabled(on); }
 int qudaAmdMultigridFusedStats(void *mg_instance, int level, long long out[5]) {

@@ -1,154 +1,14 @@
-// transfer.hip — restrictor / prolongator / block Gram-Schmidt kernels and the Transfer host class (see transfer.h).
-#include "transfer.h"
+// transfer.hip — the transfer operators of the solve phase: restrictor / prolongator kernels and the Transfer methods that launch them (see transfer.h; V: transfer_setup.hip)
+#include "transfer_device.h"
 #include "device_io.h"   // pk:: packed fp32 complex arithmetic
 
 #include <cstring>
+#include <type_traits>
 
 namespace quda {
 
-constexpr int kMaxVec = 32;
-
-// fine-vector element access: complex number sc of site x in one parity block of a planar field with NV reals per vector
-template <int NV> __device__ __forceinline__ size_t fidx(int stride, int x, int sc) {
-  const int r = 2 * sc;
-  return ((size_t)(r / NV) * stride + x) * NV + (r % NV);
-}
-
-// the K complex components of fine site x into r[]: for the float4-plane order (NV = 4: components 2m, 2m + 1 share a plane entry)
-// with one 16-byte load per pair — as 4-byte loads the gather of the four fine vectors of restrict4_kernel was 96 instructions per
-// thread, each touching 32 cache lines per wave
-template <int NV, int K> __device__ __forceinline__ void load_fine_site(float2 *r, const float *base, int stride, int x) {
-  if (NV == 4 && K % 2 == 0) {
-#pragma unroll
-    for (int m = 0; m < K / 2; m++) {
-      const float4 v = reinterpret_cast<const float4 *>(base)[(size_t)m * stride + x];
-      r[2 * m] = make_float2(v.x, v.y); r[2 * m + 1] = make_float2(v.z, v.w);
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < K; k++) { const size_t i = fidx<NV>(stride, x, k); r[k] = make_float2(base[i], base[i + 1]); }
-  }
-}
-
-struct FineVec {
-  float *v[2];  // even / odd parity block
-  int stride, Vh;
-};
-struct CoarseVec {
-  float *v[2];
-  int stride, Vh;
-};
-
-// parity >= 0: `f` is a single-parity field holding that parity; the other parity is absent (nullptr): it restricts as zero
-// and is not written by the prolongator (reference Transfer::setSiteSubset, lib/transfer.cpp:276-290)
-static FineVec fineVec(const ColorSpinorField &f, int parity = -1) {
-  if (f.Location() != QUDA_CUDA_FIELD_LOCATION || f.Precision() != QUDA_SINGLE_PRECISION)
-    errorQuda("transfer operators work on fp32 device fields (precision %d)", f.Precision());
-  ColorSpinorField &g = const_cast<ColorSpinorField &>(f);
-  FineVec r;
-  if (f.SiteSubset() == QUDA_FULL_SITE_SUBSET) {
-    r.v[0] = (float *)g.Even().V(); r.v[1] = (float *)g.Odd().V();
-  } else {
-    if (parity != 0 && parity != 1) errorQuda("single-parity field without Transfer::setSiteSubset(QUDA_PARITY_SITE_SUBSET, parity)");
-    r.v[parity] = (float *)g.V(); r.v[1 - parity] = nullptr;
-  }
-  r.stride = f.Stride(); r.Vh = f.VolumeCB();
-  return r;
-}
-
-struct MaskArg {
-  int dir;       // -1: no mask
-  int boundary;  // 1: keep sites whose dir-neighbour is outside the aggregate, 0: inside
-  int bs[4];
-  int single[4]; // coarse extent 1 in that dimension: the neighbour always wraps into the same aggregate
-  int pm;        // parity-major order of the sites inside an aggregate (Transfer::parityMajor), else lexicographic
-};
-// coordinates of site b of an aggregate.  Lexicographic (x fastest), or — parity-major, all block extents even — the even sites of the
-// aggregate first, then the odd ones, each half in lexicographic order halved (the checkerboard numbering of the lattice applied to
-// the block): a single-parity fine field (Transfer::setSiteSubset) then meets ONE contiguous half of every (component, vector pair)
-// row of V, and the waves that own the absent parity issue no loads at all — half the V bytes for R and P of an even-odd cycle.
-__device__ __forceinline__ void block_coords(int *y, const MaskArg &m, int b) {
-  int l = b, p = 0;
-  if (m.pm) {
-    const int half = (m.bs[0] * m.bs[1] * m.bs[2] * m.bs[3]) >> 1;
-    p = b >= half;
-    l = 2 * (b - p * half);
-  }
-  y[0] = l % m.bs[0]; l /= m.bs[0];
-  y[1] = l % m.bs[1]; l /= m.bs[1];
-  y[2] = l % m.bs[2]; y[3] = l / m.bs[2];
-  if (m.pm) y[0] += (p + y[1] + y[2] + y[3]) & 1;   // y[0] is even here: the site of the pair that has parity p
-}
-
-__device__ __forceinline__ bool mask_keep(const MaskArg &m, int b) {
-  if (m.dir < 0) return true;
-  const int mu = m.dir >> 1, fwd = !(m.dir & 1);
-  int y[4];
-  block_coords(y, m, b);
-  const bool out = !m.single[mu] && (fwd ? y[mu] == m.bs[mu] - 1 : y[mu] == 0);
-  return out == (m.boundary != 0);
-}
-
-// ---- block reduction of one float4 across the work-group (wave64 shuffles, then LDS across waves) ----
-__device__ __forceinline__ float4 block_sum4(float4 v, float4 *lds) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    v.x += __shfl_down(v.x, off, 64); v.y += __shfl_down(v.y, off, 64);
-    v.z += __shfl_down(v.z, off, 64); v.w += __shfl_down(v.w, off, 64);
-  }
-  const int wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) lds[wave] = v;
-  __syncthreads();
-  float4 r = lds[0];
-  for (int w = 1; w < nw; w++) { r.x += lds[w].x; r.y += lds[w].y; r.z += lds[w].z; r.w += lds[w].w; }
-  return r;
-}
-
 // ---- restrictor: one work-group per aggregate, one thread per fine site of it.  DUAL (Galerkin construction): the sites whose
 // mask.dir neighbour leaves the aggregate go into `out`, the others into `out2`, in ONE pass over V (V is the whole cost) ----
-__device__ __forceinline__ bool mask_outside(const MaskArg &m, int b) {
-  const int mu = m.dir >> 1, fwd = !(m.dir & 1);
-  int y[4];
-  block_coords(y, m, b);
-  return !m.single[mu] && (fwd ? y[mu] == m.bs[mu] - 1 : y[mu] == 0);
-}
-
-typedef _Float16 vhalf4_t __attribute__((ext_vector_type(4)));
-template <bool HALF> __device__ __forceinline__ float4 load_v(const void *V, size_t i) {
-  if (HALF) {
-    const vhalf4_t h = reinterpret_cast<const vhalf4_t *>(V)[i];
-    return make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w);
-  }
-  // V is streamed once per kernel (24.5 GB at 48^3 x 96): non-temporal loads keep it from displacing the fine and coarse vectors the
-  // same kernel reads and writes (prolongator 0.58 -> 0.76 of the HBM roofline at 32^4)
-  typedef float f32x4_nt __attribute__((ext_vector_type(4)));
-  const f32x4_nt t = __builtin_nontemporal_load(reinterpret_cast<const f32x4_nt *>(V) + i);
-  return make_float4(t.x, t.y, t.z, t.w);
-}
-
-// work-group -> aggregate.  xgroup > 0: the four aggregates that are neighbours along x (xgroup = Xc[0] / 4 such groups per row) take
-// four consecutive slots of ONE XCD (work-groups b, b + 8, b + 16, b + 24).  An aggregate 4 sites wide covers 2 consecutive
-// checkerboard sites per row and parity, i.e. a 32-byte piece of every 128-byte line of the fine field; written a quarter at a
-// time by work-groups far apart in the grid (neighbours along x differ in coarse parity: half a grid apart) every line went to
-// memory in pieces once the field no longer fits the Infinity Cache — prolongator at 48^3 x 96: 0.56 of the HBM roofline against
-// 0.76 at 32^4.  With the four quarters written from one L2 within microseconds the line leaves it whole.  The restrictors READ the
-// fine vectors in the same 32-byte pieces (restrict4_kernel four of them at once): same order, so that three of the four pieces of a
-// line are L2 hits.
-struct AggMap { int xgroup, X0, X1, X2, Vh; };
-__device__ __forceinline__ int aggregate_of_block(const AggMap &m) {
-  const int b = blockIdx.x;
-  if (!m.xgroup) return b;
-  const int xcd = b & 7, within = b >> 3;
-  int g = xcd + 8 * (within >> 2);
-  const int r = within & 3;
-  const int xg = g % m.xgroup; g /= m.xgroup;
-  const int y = g % m.X1; g /= m.X1;
-  const int z = g % m.X2; const int t = g / m.X2;
-  const int x = 4 * xg + r;
-  return ((x + y + z + t) & 1) * m.Vh + ((((t * m.X2 + z) * m.X1 + y) * m.X0 + x) >> 1);
-}
-
 template <int NSF, int NCF, int NVEC, int NV, bool DUAL, bool HALF = false>
 __global__ void restrict_kernel(CoarseVec out, CoarseVec out2, FineVec in, const void *V, const int *block_to_fine, int blockVol, int spin_bs, MaskArg mask, AggMap amap) {
   constexpr int K = NSF * NCF;
@@ -211,16 +71,6 @@ load_fine_site<NV, K>(r, base, in.stride, x);
 // in flight (raw register images, converted at their use), sums four steps at a time with a reduce-scatter butterfly (17 cross-lane
 // moves per four steps instead of 96) into its own LDS row, and the work-group meets at ONE barrier.  A wave without a site of the
 // present parity (parity-major V) issues nothing.
-typedef float f32x4_raw_t __attribute__((ext_vector_type(4)));
-template <bool HALF> struct VRaw { typedef f32x4_raw_t type; };
-template <> struct VRaw<true> { typedef vhalf4_t type; };
-template <bool HALF> __device__ __forceinline__ typename VRaw<HALF>::type load_v_raw(const void *V, size_t i) {
-  if constexpr (HALF) return reinterpret_cast<const vhalf4_t *>(V)[i];
-  else return __builtin_nontemporal_load(reinterpret_cast<const f32x4_raw_t *>(V) + i);
-}
-__device__ __forceinline__ float4 v_unpack(const f32x4_raw_t &t) { return make_float4(t.x, t.y, t.z, t.w); }
-__device__ __forceinline__ float4 v_unpack(const vhalf4_t &h) { return make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w); }
-
 template <int NSF, int NCF, int NVEC, int NV, bool HALF>
 __global__ void __launch_bounds__(256) restrict_stream_kernel(CoarseVec out, FineVec in, const void *V, const int *block_to_fine, int blockVol, MaskArg mask, AggMap amap) {
   constexpr int K = NSF * NCF, KH = K / 2, NVP = NVEC / 2, NST = 2 * NVP;
@@ -624,37 +474,6 @@ load_fine_site<NV, K>(r[q], base, a.in[q].stride, x);
   }
 }
 
-// phi = P e_j for the coarse unit vector j = (chirality, vector) at every coarse site: column j of V, copied out of the
-// aggregate-major layout (1/12 of V is touched instead of the whole of it by a prolongation)
-template <int NSF, int NCF, int NV>
-__global__ void column_kernel(FineVec out, const float4 *V, const int *block_to_fine, int blockVol, int spin_bs, int NVEC, int j, long total) {
-  constexpr int K = NSF * NCF;
-  const long t = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  const long A = t / blockVol;
-  const int b = (int)(t - A * blockVol);
-  const int f = block_to_fine[t];
-  const int parity = f >= out.Vh, x = f - parity * out.Vh;
-  float *base = out.v[parity];
-  const int chi = j / NVEC, v = j - chi * NVEC;
-  float2 c[K];
-#pragma unroll
-  for (int k = 0; k < K; k++) {
-    c[k] = make_float2(0.f, 0.f);
-    if ((k / NCF) / spin_bs == chi) {
-      const float4 w = V[(((size_t)A * K + k) * (NVEC / 2) + (v >> 1)) * blockVol + b];
-      c[k] = (v & 1) ? make_float2(w.z, w.w) : make_float2(w.x, w.y);
-    }
-  }
-  if (NV == 4 && K % 2 == 0) {   // two components per plane entry: one 16-byte store instead of four 4-byte ones
-#pragma unroll
-    for (int m = 0; m < K / 2; m++) reinterpret_cast<float4 *>(base)[(size_t)m * out.stride + x] = make_float4(c[2 * m].x, c[2 * m].y, c[2 * m + 1].x, c[2 * m + 1].y);
-  } else {
-#pragma unroll
-    for (int k = 0; k < K; k++) { const size_t i = fidx<NV>(out.stride, x, k); base[i] = c[k].x; base[i + 1] = c[k].y; }
-  }
-}
-
 // ---- small aggregates (blockVol <= 32, the coarse levels: 2^4 = 16 sites).  One thread per site leaves most of a wave idle and
 // runs the (chirality, vector pair) iterations one after the other behind block-wide reductions — 0.28 ms for a 37 MB
 // transfer.  Here a wave holds 64 / GS groups of GS lanes (GS = blockVol rounded up to a power of two), every group takes its
@@ -830,644 +649,48 @@ __global__ void __launch_bounds__(512) prolong_kernel(FineVec out, CoarseVec in,
   }
 }
 
-// ---- V fill + block Gram-Schmidt ----
-struct VecList { const float *ev[kMaxVec]; const float *od[kMaxVec]; };
-
-template <int NV> __global__ void fillv_kernel(float *V, VecList B, int stride, int Vh, const int *block_to_fine, int blockVol, int K, int nvec, long total) {
-  const long t = blockIdx.x * (long)blockDim.x + threadIdx.x;  // over (A, b)
-  if (t >= total) return;
-  const long A = t / blockVol;
-  const int b = (int)(t - A * blockVol);
-  const int f = block_to_fine[t];
-  const int parity = f >= Vh, x = f - parity * Vh;
-  if (NV == 4 && K % 2 == 0) {
-    // 16-byte reads (two components of one vector share a plane entry) and 16-byte writes (the two vectors of a pair share a V entry)
-    float4 *V4 = reinterpret_cast<float4 *>(V);
-    for (int vp = 0; vp < nvec / 2; vp++) {
-      const float4 *b0 = reinterpret_cast<const float4 *>(parity ? B.od[2 * vp] : B.ev[2 * vp]);
-      const float4 *b1 = reinterpret_cast<const float4 *>(parity ? B.od[2 * vp + 1] : B.ev[2 * vp + 1]);
-      for (int m = 0; m < K / 2; m++) {
-        const float4 u = b0[(size_t)m * stride + x], w = b1[(size_t)m * stride + x];
-        V4[(((size_t)A * K + 2 * m) * (nvec / 2) + vp) * blockVol + b] = make_float4(u.x, u.y, w.x, w.y);
-        V4[(((size_t)A * K + 2 * m + 1) * (nvec / 2) + vp) * blockVol + b] = make_float4(u.z, u.w, w.z, w.w);
-      }
-    }
-    return;
-  }
-  for (int v = 0; v < nvec; v++) {
-    const float *base = parity ? B.od[v] : B.ev[v];
-    for (int k = 0; k < K; k++) {
-      const size_t i = fidx<NV>(stride, x, k);
-      const size_t o = ((((size_t)A * K + k) * (nvec / 2) + v / 2) * blockVol + b) * 4 + (v & 1) * 2;
-      V[o] = base[i]; V[o + 1] = base[i + 1];
-    }
-  }
-}
-
-__device__ __forceinline__ double2 block_sum2d(double2 v, double2 *lds) {
-  for (int off = 32; off > 0; off >>= 1) { v.x += __shfl_down(v.x, off, 64); v.y += __shfl_down(v.y, off, 64); }
-  const int wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) lds[wave] = v;
-  __syncthreads();
-  double2 r = lds[0];
-  for (int w = 1; w < nw; w++) { r.x += lds[w].x; r.y += lds[w].y; }
-  return r;
-}
-
-// modified Gram-Schmidt over the nvec vectors of one (aggregate, chirality) block, sums in fp64
-// (reference blockGramSchmidt, lib/transfer_util.cu:328-363)
-__global__ void block_gs_kernel(float *V, int blockVol, int K, int ncf, int spin_bs, int nvec, const int *only) {
-  if (only && !only[blockIdx.x]) return;   // fall-back of the CholeskyQR kernel: just the blocks it flagged
-  __shared__ double2 lds[16];
-  const int A = blockIdx.x >> 1, chi = blockIdx.x & 1;
-  const int Kc = K / 2, n = Kc * blockVol;
-  // element e of this block -> (k, b)
-  auto addr = [&](int e, int v) -> size_t {
-    const int kk = e / blockVol, b = e - kk * blockVol;
-    // the kk-th fine spin-colour index whose chirality is chi
-    const int nsc = spin_bs * ncf;             // spin-colour values per chirality are contiguous in k = s*ncf + c
-    const int k = chi * nsc + kk;
-    return ((((size_t)A * K + k) * (nvec / 2) + v / 2) * blockVol + b) * 4 + (v & 1) * 2;
-  };
-  for (int jc = 0; jc < nvec; jc++) {
-    for (int ic = 0; ic < jc; ic++) {
-      double2 dot = make_double2(0.0, 0.0);
-      for (int e = threadIdx.x; e < n; e += blockDim.x) {
-        const size_t ai = addr(e, ic), aj = addr(e, jc);
-        const double ar = V[ai], aim = V[ai + 1], br = V[aj], bim = V[aj + 1];
-        dot.x += ar * br + aim * bim; dot.y += ar * bim - aim * br;
-      }
-      dot = block_sum2d(dot, lds);
-      for (int e = threadIdx.x; e < n; e += blockDim.x) {
-        const size_t ai = addr(e, ic), aj = addr(e, jc);
-        const double ar = V[ai], aim = V[ai + 1];
-        V[aj] = (float)(V[aj] - (dot.x * ar - dot.y * aim));
-        V[aj + 1] = (float)(V[aj + 1] - (dot.x * aim + dot.y * ar));
-      }
-      __syncthreads();
-    }
-    double2 nrm = make_double2(0.0, 0.0);
-    for (int e = threadIdx.x; e < n; e += blockDim.x) { const size_t aj = addr(e, jc); nrm.x += (double)V[aj] * V[aj] + (double)V[aj + 1] * V[aj + 1]; }
-    nrm = block_sum2d(nrm, lds);
-    const float scale = nrm.x > 0.0 ? (float)(1.0 / sqrt(nrm.x)) : 0.f;
-    for (int e = threadIdx.x; e < n; e += blockDim.x) { const size_t aj = addr(e, jc); V[aj] *= scale; V[aj + 1] *= scale; }
-    __syncthreads();
-  }
-}
-
-// ---- CholeskyQR: the same block orthonormalisation in two passes over the block instead of nvec (nvec - 1) / 2 -----------------
-// Q R = V with R upper triangular and a positive diagonal is unique, so Q = V R^-1 with R from the Cholesky factorisation of the
-// Gram matrix G = V^dagger V (= R^dagger R) IS the Gram-Schmidt result — but G needs one sweep over the block (all 300 inner
-// products of 24 vectors at once, fp64 sums, the block staged through LDS in chunks of 256 elements) and V R^-1 a second one,
-// where modified Gram-Schmidt makes 276 dependent sweeps with two block reductions each (0.44 - 0.6 s at 48^3 x 96).  Run twice
-// (CholeskyQR2): the second round removes the orthogonality the first one loses to the conditioning of the block — as long as
-// eps cond(V)^2 < 1 with the eps of the Gram matrix, which is fp32 here (V is fp32 and a chunk's 256-term sum is fp32: ~1e-6
-// relative).  Two guards, both matched to that precision: a Cholesky pivot below kQrPivot x G_jj is round-off, not data, and a
-// first-round result whose Gram matrix is further than kQrRound2 from the identity is beyond what the second round repairs.  A block
-// that trips either one is flagged and goes to the Gram-Schmidt kernel — that block only; what the first round may already have
-// written is V T with T upper triangular with a positive diagonal, which has the same Q.
-// Reference semantics: blockGramSchmidt, lib/transfer_util.cu:328-363.
-constexpr int kQrChunk = 256;
-constexpr double kQrPivot = 1e-5, kQrRound2 = 5e-2;
-template <int NVEC> __global__ void __launch_bounds__(256) block_cholqr_kernel(float *V, int blockVol, int K, int ncf, int spin_bs, int *failed, int *failedBlock) {
-  constexpr int nvec = NVEC;
-  extern __shared__ double smem[];
-  // layout: tile [kQrChunk][nvec + 1] float2 | G / L [nvec][nvec] double2 | Rinv [nvec][nvec] float2 | flag
-  float2 *tile = reinterpret_cast<float2 *>(smem);
-  constexpr int tstride = nvec + 1;
-  double2 *G = reinterpret_cast<double2 *>(tile + (size_t)kQrChunk * tstride + (kQrChunk * tstride & 1));
-  float2 *Rinv = reinterpret_cast<float2 *>(G + nvec * nvec);
-  int *bad = reinterpret_cast<int *>(Rinv + nvec * nvec);
-  const int A = blockIdx.x >> 1, chi = blockIdx.x & 1;
-  const int Kc = K / 2, n = Kc * blockVol, nsc = spin_bs * ncf;
-  constexpr int nvp = nvec / 2, npairs = nvec * (nvec + 1) / 2;
-  auto addr4 = [&](int e, int vp) -> size_t {   // float4 index of (element e, vector pair vp)
-    const int kk = e / blockVol, b = e - kk * blockVol;
-    return (((size_t)A * K + chi * nsc + kk) * nvp + vp) * blockVol + b;
-  };
-  float4 *V4 = reinterpret_cast<float4 *>(V);
-  if (threadIdx.x == 0) *bad = 0;
-  for (int round = 0; round < 2; round++) {
-    // ---- Gram matrix: pair p = (i <= j) per thread (up to 3 pairs for nvec = 32) ----
-    int pi[3], pj[3];
-    double2 acc[3];
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-      const int p = threadIdx.x + 256 * q;
-      acc[q] = make_double2(0.0, 0.0);
-      pi[q] = pj[q] = -1;
-      if (p < npairs) {   // row-major enumeration of the upper triangle
-        int i = 0, rem = p;
-        while (rem >= nvec - i) { rem -= nvec - i; i++; }
-        pi[q] = i; pj[q] = i + rem;
-      }
-    }
-    for (int c0 = 0; c0 < n; c0 += kQrChunk) {
-      __syncthreads();
-      const int e = c0 + threadIdx.x;
-#pragma unroll
-      for (int vp = 0; vp < nvp; vp++) {
-        const float4 w = e < n ? V4[addr4(e, vp)] : make_float4(0.f, 0.f, 0.f, 0.f);
-        tile[threadIdx.x * tstride + 2 * vp] = make_float2(w.x, w.y);
-        tile[threadIdx.x * tstride + 2 * vp + 1] = make_float2(w.z, w.w);
-      }
-      __syncthreads();
-#pragma unroll
-      for (int q = 0; q < 3; q++) {
-        if (pi[q] < 0) continue;
-        // fp32 inside a chunk (packed: conj(a) b = two v_pk_fma_f32), fp64 across the chunks: the per-term conversions and fp64
-        // multiply-adds made this loop the most expensive part of the kernel (59.5 ms per pass at 48^3 x 96); a chunk's 256-term
-        // sum is good to ~1e-6 relative, the second CholeskyQR round and the fp64 chunk sums keep the result at fp32 round-off
-        pkf2 part = {0.f, 0.f};
-        for (int t = 0; t < kQrChunk; t++) {
-          const float2 a = tile[t * tstride + pi[q]], b = tile[t * tstride + pj[q]];
-          part = pk::cmac_conj(part, (pkf2){a.x, a.y}, (pkf2){b.x, b.y});
-        }
-        acc[q].x += (double)part.x; acc[q].y += (double)part.y;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 3; q++)
-      if (pi[q] >= 0) {
-        G[pi[q] * nvec + pj[q]] = acc[q]; G[pj[q] * nvec + pi[q]] = make_double2(acc[q].x, -acc[q].y);
-        // second round: the first one must have left something close to orthonormal
-        if (round == 1 && (fabs(acc[q].x - (pi[q] == pj[q] ? 1.0 : 0.0)) > kQrRound2 || fabs(acc[q].y) > kQrRound2)) *bad = 1;
-      }
-    __syncthreads();
-    if (*bad) break;
-    // ---- Cholesky G = L L^dagger in place (lower triangle), column by column; thread i owns row i ----
-    for (int j = 0; j < nvec; j++) {
-      if ((int)threadIdx.x == j) {
-        double d = G[j * nvec + j].x;
-        for (int k = 0; k < j; k++) { const double2 l = G[j * nvec + k]; d -= l.x * l.x + l.y * l.y; }
-        if (!(d > kQrPivot * G[j * nvec + j].x) || !(d > 0.0)) { *bad = 1; d = 1.0; }
-        G[j * nvec + j] = make_double2(sqrt(d), 0.0);
-      }
-      __syncthreads();
-      const int i = threadIdx.x;
-      if (i > j && i < nvec) {
-        double2 v = G[i * nvec + j];
-        for (int k = 0; k < j; k++) {   // -= L[i][k] conj(L[j][k])
-          const double2 a = G[i * nvec + k], b = G[j * nvec + k];
-          v.x -= a.x * b.x + a.y * b.y; v.y -= a.y * b.x - a.x * b.y;
-        }
-        const double inv = 1.0 / G[j * nvec + j].x;
-        G[i * nvec + j] = make_double2(v.x * inv, v.y * inv);
-      }
-      __syncthreads();
-    }
-    if (*bad) break;
-    // ---- R = L^dagger (upper); column j of R^-1 by back substitution, thread j ----
-    if ((int)threadIdx.x < nvec) {
-      const int j = threadIdx.x;
-      double2 x[NVEC];
-#pragma unroll
-      for (int i = nvec - 1; i >= 0; i--) {
-        double2 v = make_double2(i == j ? 1.0 : 0.0, 0.0);
-#pragma unroll
-        for (int k = i + 1; k < nvec; k++) {   // R[i][k] = conj(L[k][i])
-          if (k > j) continue;
-          const double2 r = G[k * nvec + i];
-          v.x -= r.x * x[k].x + r.y * x[k].y; v.y -= r.x * x[k].y - r.y * x[k].x;
-        }
-        const double inv = 1.0 / G[i * nvec + i].x;
-        x[i] = i <= j ? make_double2(v.x * inv, v.y * inv) : make_double2(0.0, 0.0);
-      }
-#pragma unroll
-      for (int i = 0; i < nvec; i++) Rinv[i * nvec + j] = make_float2((float)x[i].x, (float)x[i].y);
-    }
-    __syncthreads();
-    // ---- V <- V R^-1: thread per element ----
-    for (int c0 = 0; c0 < n; c0 += 256) {
-      const int e = c0 + threadIdx.x;
-      if (e >= n) continue;
-      float2 v[NVEC];
-#pragma unroll
-      for (int vp = 0; vp < nvp; vp++) { const float4 w = V4[addr4(e, vp)]; v[2 * vp] = make_float2(w.x, w.y); v[2 * vp + 1] = make_float2(w.z, w.w); }
-#pragma unroll
-      for (int vp = nvp - 1; vp >= 0; vp--) {   // columns from the right: column j only needs v[0..j], so v can be overwritten in place
-        float2 o[2];
-#pragma unroll
-        for (int h = 1; h >= 0; h--) {
-          const int j = 2 * vp + h;
-          pkf2 a = {0.f, 0.f};
-#pragma unroll
-          for (int i = 0; i <= j; i++) { const float2 r = Rinv[i * nvec + j]; a = pk::cmac(a, (pkf2){v[i].x, v[i].y}, (pkf2){r.x, r.y}); }
-          o[h] = make_float2(a.x, a.y);
-        }
-        v[2 * vp] = o[0]; v[2 * vp + 1] = o[1];
-        V4[addr4(e, vp)] = make_float4(o[0].x, o[0].y, o[1].x, o[1].y);
-      }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && *bad) { atomicAdd(failed, 1); failedBlock[blockIdx.x] = 1; }
-}
-
-// ================================================================================================
-// Direct Galerkin construction, step 2 ("VUV", reference ComputeVUV lib/coarse_op.cuh:487-600) on the matrix cores: for one forward
-// direction mu and every aggregate A
-//     Y[(chi, v)][(chi', v')] = sum_{x in A} sum_{s in chi, c} conj(V(x)[s, c; v]) [ (1 - gamma_mu) UV(x) ]^{chi'}[s, c; v']      (UV from galerkin_uv_kernel)
-// — the sites whose mu-neighbour lies in the next aggregate give the coarse link Y_{2 mu}(A), all others the part S(A) of the local
-// matrix (hermitian completion by the caller, coarse.hip).  The probing path gets the same numbers from 2 Nvec passes over V with a
-// block reduction per coefficient; here the sum over the 256 sites of the aggregate IS the K dimension of a GEMM:
-// per row block chi a real GEMM  M = Nvec rows (v; padded to 16 / 32), N = 4 Nvec real columns ((chi', v') x re / im), K = 256 x 6 x 2
-// on v_mfma_f32_16x16x4_f32 (exact fp32).  The projector is applied on the fly: a column of chirality chi' = chi sees UV[s, c] itself, one of the
-// other chirality phi(mu, s) UV[partner(mu, s), c] with phi in {+-1, +-i} (table below, read off spin_project / spin_reconstruct of dslash.hip).
-// One work-group per aggregate, 8 waves: wave = 4 chi + w takes row block chi of the 64 sites with block coordinate y_mu = w, so the
-// class-3 waves hold the link and classes 0..2 the local part without any masking.  A k-step is 4 sites of one (spin-colour, re/im):
-//     A operand  lane (row v, kq): Re or Im of V(x_kq)[s, c; v]                      one 8-byte load serves the re and the im step
-//     B operand  lane (col (j, o), kq): from w = phi UV(x_kq)[s', c; v'(j)] = (wr, wi):   re step: o ? wi : wr     im step: o ? -wr : wi
-// so that column (j, re) collects Vr Wr + Vi Wi and (j, im) Vr Wi - Vi Wr, i.e. conj(V) W.  Operands come straight from global memory
-// (every 16-byte word of the aggregate's V / UV rows is used by lanes of the work-group within microseconds: L1 / L2 absorb the pieces);
-// partial tiles are summed through LDS and written in the link layout [site][matrix][column pair][row] float4.
-// local = 1: UV is a chirality-diagonal site term (twisted clover, galerkin_local_uv_kernel): no cross columns, every class is local.
-// Fine level only: 4 x 3 spin-colour, 4^4 aggregates, Nvec 8, 24 or 32, unpartitioned.
-// ================================================================================================
-typedef float gf32x4 __attribute__((ext_vector_type(4)));
-// forward hop (1 - gamma_mu) in the chiral basis of dslash.hip: row s of the OTHER chirality's contribution is i^k UV[partner]
-__device__ __constant__ int kGalPartner[4][4] = {{3, 2, 1, 0}, {3, 2, 1, 0}, {2, 3, 0, 1}, {2, 3, 0, 1}};
-__device__ __constant__ int kGalPhase[4][4] = {{3, 3, 1, 1}, {0, 2, 2, 0}, {3, 1, 1, 3}, {2, 2, 2, 2}};
-// the K loop of one wave (row block CHI, its class of 64 sites).  Branch-free on purpose: the first version selected same / cross rows, the
-// phase and the padding rows with conditionals, which the compiler turned into ~300 branches with an s_waitcnt vmcnt(0) behind every load —
-// 37 ms per direction at 48^3 x 96, no faster with two work-groups per CU.  Here every lane multiplies what it loads by a complex
-// constant fixed before the loop: i^(3 o) for a column of the wave's own chirality (o: the lane's real / imaginary column), i^(phase + 3 o)
-// for the other chirality (0 in local mode), 0 for a padding row of A — so that (bre, bim) = c w and the two MFMA steps follow.
-template <int NVEC, int CHI, typename SiteB>
-__device__ __forceinline__ void galerkin_vuv_accumulate(gf32x4 (&acc)[(NVEC + 15) / 16][NVEC / 4], const float2 *V, const float2 *UV, int A, int Aloc, int mu, int local, int row16, int kq, SiteB site_b, int cmBase) {
-  constexpr int NVP = NVEC / 2, MT = (NVEC + 15) / 16, NT = NVEC / 4, BV = 256;
-#pragma unroll
-  for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-    for (int nt = 0; nt < NT; nt++) acc[mt][nt] = (gf32x4){0.f, 0.f, 0.f, 0.f};
-  const int o = row16 & 1;
-  // i^k as (re, im)
-  auto ipow = [](int k) -> float2 { k &= 3; return make_float2(k == 0 ? 1.f : (k == 2 ? -1.f : 0.f), k == 1 ? 1.f : (k == 3 ? -1.f : 0.f)); };
-  const float2 cSame = ipow(3 * o);
-  float2 cCross[2];
-#pragma unroll
-  for (int h = 0; h < 2; h++) {
-    cCross[h] = ipow(kGalPhase[mu][2 * CHI + h] + 3 * o);
-    if (local) cCross[h] = make_float2(0.f, 0.f);
-  }
-  // per-lane element offsets (float2 units) inside a (spin-colour) row of the aggregate: A rows v = 16 mt + row16 (padding rows: clamped, scaled by 0)
-  int aOff[MT]; float aScale[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; mt++) {
-    const int v = 16 * mt + row16, vv = v < NVEC ? v : NVEC - 1;
-    aOff[mt] = (vv >> 1) * BV * 2 + (vv & 1);
-    aScale[mt] = v < NVEC ? 1.f : 0.f;
-  }
-  int bOff[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; nt++) {
-    const int j = 8 * nt + (row16 >> 1), vc = j - (nt >= NT / 2 ? NVEC : 0);
-    bOff[nt] = (vc >> 1) * BV * 2 + (vc & 1);
-  }
-  const float2 *Va = V + (size_t)A * 12 * NVP * BV * 2, *Ua = UV + (size_t)Aloc * 12 * NVP * BV * 2;
-  constexpr int ROW = NVP * BV * 2;   // float2 elements per (spin-colour) row
-  // spin-colour row outermost, the wave's 64 sites (16 k-steps of 4) inside: with UV in class-major order (cmBase >= 0: the wave's sites are entries
-  // cmBase .. cmBase + 63 of every UV row) consecutive k-steps read consecutive 64-byte pieces — every 128-byte line of UV is fetched once
-#pragma unroll
-  for (int s6 = 0; s6 < 6; s6++) {
-    for (int g = 0; g < 16; g++) {
-      const int b2 = 2 * site_b(4 * g + kq), u2 = cmBase >= 0 ? 2 * (cmBase + 4 * g + kq) : b2;
-      {
-      const int spin = 2 * CHI + s6 / 3, col = s6 % 3;
-      const int rowSame = (3 * spin + col) * ROW, rowCross = (3 * kGalPartner[mu][spin] + col) * ROW;
-      float are[MT], aim[MT], bre[NT], bim[NT];
-#pragma unroll
-      for (int mt = 0; mt < MT; mt++) {
-        const float2 a = Va[rowSame + aOff[mt] + b2];
-        are[mt] = aScale[mt] * a.x; aim[mt] = aScale[mt] * a.y;
-      }
-#pragma unroll
-      for (int nt = 0; nt < NT; nt++) {
-        constexpr int dummy = 0; (void)dummy;
-        const bool same = (nt >= NT / 2) == (CHI == 1);
-        const float2 w = Ua[(same ? rowSame : rowCross) + bOff[nt] + u2];
-        const float2 c = same ? cSame : cCross[s6 / 3];
-        bre[nt] = c.x * w.x - c.y * w.y;
-        bim[nt] = c.x * w.y + c.y * w.x;
-      }
-      // all re steps, then all im steps: consecutive matrix instructions on different accumulators
-#pragma unroll
-      for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-        for (int nt = 0; nt < NT; nt++) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(are[mt], bre[nt], acc[mt][nt], 0, 0, 0);
-#pragma unroll
-      for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-        for (int nt = 0; nt < NT; nt++) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(aim[mt], bim[nt], acc[mt][nt], 0, 0, 0);
-      }
-    }
-  }
-}
-template <int NVEC> __global__ void __launch_bounds__(512) galerkin_vuv_kernel(float *G, const float2 *V, const float2 *UV, int mu, int accumulateLocal, int pm, int local, int aggOffset, int classMajor) {
-  constexpr int NVP = NVEC / 2, MT = (NVEC + 15) / 16, NT = NVEC / 4, n = 2 * NVEC, BV = 256;
-  extern __shared__ float glds[];   // [class][mt][nt][reg][lane], one row block at a time
-  const int A = blockIdx.x + aggOffset, lane = threadIdx.x & 63;   // UV holds the aggregates [aggOffset, aggOffset + gridDim) only
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int cls = wave & 3, chiR = wave >> 2;
-  const int row16 = lane & 15, kq = lane >> 4;
-  // site list of this wave: y_mu = cls, the other three coordinates from pos = 0 .. 63; b = place of the site inside the aggregate
-  auto site_b = [&](int pos) -> int {
-    int y[4], q = pos;
-    for (int d = 0; d < 4; d++) if (d != mu) { y[d] = q & 3; q >>= 2; }
-    y[mu] = cls;
-    const int lex = ((y[3] * 4 + y[2]) * 4 + y[1]) * 4 + y[0];
-    return pm ? ((y[0] + y[1] + y[2] + y[3]) & 1) * (BV / 2) + (lex >> 1) : lex;
-  };
-  gf32x4 acc[MT][NT];
-  const int cmBase = classMajor ? cls * 64 : -1;
-  if (chiR == 0) galerkin_vuv_accumulate<NVEC, 0>(acc, V, UV, A, (int)blockIdx.x, mu, local, row16, kq, site_b, cmBase);
-  else galerkin_vuv_accumulate<NVEC, 1>(acc, V, UV, A, (int)blockIdx.x, mu, local, row16, kq, site_b, cmBase);
-  // ---- partial tiles -> LDS, one row block (chi) at a time so that the buffer is 4 waves x 12 KB and two work-groups share a CU;
-  // classes 0..2 summed = local part, class 3 = link ----
-  constexpr int TILE = MT * NT * 4 * 64;   // floats per wave
-  float4 *G4 = reinterpret_cast<float4 *>(G);
-  for (int chi = 0; chi < 2; chi++) {
-    if (chi) __syncthreads();
-    if (chiR == chi) {
-#pragma unroll
-      for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-        for (int nt = 0; nt < NT; nt++)
-#pragma unroll
-          for (int r = 0; r < 4; r++) glds[cls * TILE + ((mt * NT + nt) * 4 + r) * 64 + lane] = acc[mt][nt][r];
-    }
-    __syncthreads();
-    // output element (row i = (chi, v), complex column j): tile (v / 16, j / 8); D layout: row = 4 (lane / 16) + reg, col = lane & 15
-    // local (site-diagonal term of the fine operator): every class belongs to the local matrix, no link is written
-    constexpr int HALF = NVEC * (n / 2);   // (row v, column pair) elements of one row block
-    for (int e = threadIdx.x + (local ? HALF : 0); e < 2 * HALF; e += blockDim.x) {
-      const int which = e / HALF, r2 = e - which * HALF;   // 0: link (class 3), 1: local (classes 0..2)
-      const int jp = r2 / NVEC, v = r2 - jp * NVEC, i = chi * NVEC + v, mt = v >> 4, rr = v & 15;
-      float val[4];
-#pragma unroll
-      for (int h = 0; h < 2; h++) {
-        const int j = 2 * jp + h, nt = j >> 3;
-#pragma unroll
-        for (int oo = 0; oo < 2; oo++) {
-          const int col = 2 * (j & 7) + oo;
-          const int off = ((mt * NT + nt) * 4 + (rr & 3)) * 64 + (rr >> 2) * 16 + col;
-          val[2 * h + oo] = which ? glds[off] + glds[TILE + off] + glds[2 * TILE + off] + (local ? glds[3 * TILE + off] : 0.f) : glds[3 * TILE + off];
-        }
-      }
-      const size_t dst = (((size_t)A * 9 + (which ? 8 : 2 * mu)) * (n / 2) + jp) * n + i;
-      if (which && accumulateLocal) { const float4 old = G4[dst]; val[0] += old.x; val[1] += old.y; val[2] += old.z; val[3] += old.w; }
-      G4[dst] = make_float4(val[0], val[1], val[2], val[3]);
-    }
-  }
-}
-
-bool Transfer::canDirectGalerkin() const {
-  static int off = -1;
-  if (off < 0) { const char *e = getenv("QUDA_AMD_GALERKIN_DIRECT"); off = (e && !atoi(e)) ? 1 : 0; }
-  if (off || fineSpin != 4 || fineColor != 3 || spin_bs != 2 || (Nvec != 8 && Nvec != 24 && Nvec != 32)) return false;
-  for (int d = 0; d < 4; d++) if (geo_bs[d] != 4 || Xc[d] == 1 || commGrid().partitioned(d)) return false;
-  return true;
-}
-// forward link Y_{2 mu} and the in-aggregate part S of all coarse sites from UV = galerkinUV(V): slots 2 mu and 8 of the coarse links
-void Transfer::directGalerkinVUV(float *links, const float *UV, int mu, bool accumulateLocal, bool local, int aggOffset, int nAggChunk, bool classMajor) const {
-  if (!canDirectGalerkin()) errorQuda("direct Galerkin construction not available for this transfer operator");
-  const size_t lds = (size_t)4 * ((Nvec + 15) / 16) * (Nvec / 4) * 4 * 64 * sizeof(float);
-#define QA_VUV(NV) { static bool attr = false; \
-    if (!attr) { HIP_CHECK(hipFuncSetAttribute((const void *)galerkin_vuv_kernel<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = true; } \
-    hipLaunchKernelGGL((galerkin_vuv_kernel<NV>), dim3(nAggChunk > 0 ? nAggChunk : (int)nAgg), dim3(512), lds, computeStream(), links, (const float2 *)V, (const float2 *)UV, mu, accumulateLocal ? 1 : 0, parityMajor ? 1 : 0, local ? 1 : 0, aggOffset, classMajor ? 1 : 0); }
-  if (Nvec == 24) QA_VUV(24) else if (Nvec == 32) QA_VUV(32) else QA_VUV(8)
-#undef QA_VUV
-  HIP_CHECK(hipGetLastError());
-}
-
-// ---- random source ----
-__device__ __forceinline__ float hash_uniform(unsigned long long seed, unsigned long long i) {
-  unsigned long long z = seed + 0x9E3779B97F4A7C15ULL * (i + 1);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-  z ^= z >> 31;
-  return (float)((z >> 40) * (1.0 / 16777216.0));
-}
-// vec reals per 16-byte (8-byte) plane element: the padding sites [Vh, stride) of every plane stay zero — the flat BLAS kernels run over them
-template <typename real> __global__ void random_kernel(real *v, long n, unsigned long long seed, unsigned long long offset, int vec, int stride, int Vh) {
-  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i < n) v[i] = (int)((i / vec) % stride) < Vh ? (real)hash_uniform(seed, offset + i) : (real)0;
-}
-void spinorRandom(ColorSpinorField &f, unsigned long long seed) {
-  if (f.Location() != QUDA_CUDA_FIELD_LOCATION) errorQuda("device field required");
-  const int nseg = f.SiteSubset() == QUDA_FULL_SITE_SUBSET ? 2 : 1;
-  const long n = (long)f.Stride() * f.Nspin() * f.Ncolor() * 2;
-  const unsigned long long rank_off = (unsigned long long)commGrid().rank << 40;
-  for (int s = 0; s < nseg; s++) {
-    void *p = nseg == 2 ? (s ? f.Odd().V() : f.Even().V()) : f.V();
-    const int bs = 256; const long nb = (n + bs - 1) / bs;
-    const int vec = f.Nspin() == 4 && f.Precision() == QUDA_SINGLE_PRECISION ? 4 : 2;
-    if (f.Precision() == QUDA_DOUBLE_PRECISION) hipLaunchKernelGGL((random_kernel<double>), dim3(nb), dim3(bs), 0, computeStream(), (double *)p, n, seed, rank_off + (unsigned long long)s * n, vec, f.Stride(), f.VolumeCB());
-    else if (f.Precision() == QUDA_SINGLE_PRECISION) hipLaunchKernelGGL((random_kernel<float>), dim3(nb), dim3(bs), 0, computeStream(), (float *)p, n, seed, rank_off + (unsigned long long)s * n, vec, f.Stride(), f.VolumeCB());
-    else errorQuda("random source needs fp64/fp32 storage");
-  }
-  HIP_CHECK(hipGetLastError());
-}
-
-// ================================================================================================
-Transfer::Transfer(const std::vector<ColorSpinorField *> &B, int Nvec_, int *gbs, int spin_bs_)
-    : Nvec(Nvec_), spin_bs(spin_bs_), V(nullptr), V_h(nullptr), block_to_fine(nullptr), fine_to_block(nullptr), flops_(0),
-      site_subset(QUDA_FULL_SITE_SUBSET), subset_parity(QUDA_INVALID_PARITY) {
-  if ((int)B.size() < Nvec) errorQuda("need %d null vectors, got %zu", Nvec, B.size());
-  if (Nvec % 2 || Nvec > kMaxVec) errorQuda("Nvec = %d must be even and <= %d", Nvec, kMaxVec);
-  const ColorSpinorField &b0 = *B[0];
-  if (b0.SiteSubset() != QUDA_FULL_SITE_SUBSET) errorQuda("null vectors must be full fields");
-  fineSpin = b0.Nspin(); fineColor = b0.Ncolor();
-  if (fineSpin % spin_bs || fineSpin / spin_bs != 2) errorQuda("spin block %d does not leave two chiralities from %d spins", spin_bs, fineSpin);
-  for (int d = 0; d < 4; d++) Xf[d] = b0.X(d);
-  // block-size fallback, reference lib/transfer.cpp:31-44
-  for (int d = 0; d < 4; d++) {
-    while (gbs[d] > 0) {
-      if (d == 0 && Xf[0] == gbs[0]) warningQuda("X-dimension length %d cannot block length %d", Xf[0], gbs[0]);
-      else if ((Xf[d] / gbs[d] + 1) % 2 == 0) warningQuda("Indexing does not (yet) support odd coarse dimensions: X(%d) = %d", d, Xf[d] / gbs[d]);
-      else if ((Xf[d] / gbs[d]) * gbs[d] != Xf[d]) warningQuda("cannot block dim[%d]=%d with block size = %d", d, Xf[d], gbs[d]);
-      else break;
-      gbs[d] /= 2;
-    }
-    if (gbs[d] == 0) errorQuda("Unable to block dimension %d", d);
-  }
-  blockVol = 1; nAgg = 1; fineVol = 1;
-  for (int d = 0; d < 4; d++) { geo_bs[d] = gbs[d]; Xc[d] = Xf[d] / gbs[d]; blockVol *= gbs[d]; nAgg *= Xc[d]; fineVol *= Xf[d]; }
-  if (blockVol == 1) errorQuda("Total geometric block size is 1");
-  if (blockVol > 1024) errorQuda("aggregate of %d sites exceeds one work-group", blockVol);
-  if (getVerbosity() >= QUDA_VERBOSE) printfQuda("Transfer: using block size %d x %d x %d x %d\n", geo_bs[0], geo_bs[1], geo_bs[2], geo_bs[3]);
-  // order of the sites inside an aggregate: parity-major on the finest level when every block extent is even (block_coords above)
-  {
-    static int pmEnv = -1;
-    if (pmEnv < 0) { const char *e = getenv("QUDA_AMD_V_PARITY_MAJOR"); pmEnv = e ? atoi(e) : 1; }
-    parityMajor = pmEnv && fineSpin == 4 && geo_bs[0] % 2 == 0 && geo_bs[1] % 2 == 0 && geo_bs[2] % 2 == 0 && geo_bs[3] % 2 == 0;
-  }
-  createGeoMap();
-  // through the device pool: the next hierarchy (the other twist flavour, a refinement pass) takes the same 24.5 GB at 48^3 x 96 instead of
-  // a fresh hipMalloc + hipFree pair (~0.1 s, and the first touch of fresh pages slows every kernel that meets them)
-  V = (float *)poolDeviceMalloc(vBytes());
-  fillAndOrthonormalise(B);
-}
-
-__global__ void v_to_half_kernel(vhalf4_t *out, const float4 *in, size_t n) {
-  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float4 v = in[i];
-  vhalf4_t h;
-  h.x = (_Float16)v.x; h.y = (_Float16)v.y; h.z = (_Float16)v.z; h.w = (_Float16)v.w;
-  out[i] = h;
-}
-void Transfer::makeHalf() const {
-  if (V_h) return;
-  const size_t n4 = vBytes() / sizeof(float4);
-  V_h = poolDeviceMalloc(n4 * sizeof(vhalf4_t));
-  hipLaunchKernelGGL(v_to_half_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, computeStream(), (vhalf4_t *)V_h, (const float4 *)V, n4);
-  HIP_CHECK(hipGetLastError());
-}
-
-Transfer::~Transfer() {
-  if (V_h) poolDeviceFree(V_h, 0);
-  if (V) poolDeviceFree(V, 0);
-  if (block_to_fine) poolDeviceFree(block_to_fine, 0);
-  if (fine_to_block) poolDeviceFree(fine_to_block, 0);
-}
-
-// reference createGeoMap lib/transfer.cpp:220-258 (fine site -> coarse site), plus the position inside the aggregate
-struct GeoMapArg { int Xf[4], Xc[4], bs[4], blockVol, pm; long Vh, Vhc; };
-__global__ void geo_map_kernel(int *b2f, int *f2b, GeoMapArg a) {
-  const long f = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (f >= 2 * a.Vh) return;
-  const int parity = f >= a.Vh;
-  const long i = f - parity * a.Vh;
-  const long za = i / (a.Xf[0] / 2); const int xh = (int)(i - za * (a.Xf[0] / 2));
-  const long zb = za / a.Xf[1]; const int y = (int)(za - zb * a.Xf[1]);
-  const int t = (int)(zb / a.Xf[2]), z = (int)(zb - (long)t * a.Xf[2]);
-  const int x[4] = {2 * xh + ((y + z + t + parity) & 1), y, z, t};
-  int xc[4], yb[4];
-  for (int d = 0; d < 4; d++) { xc[d] = x[d] / a.bs[d]; yb[d] = x[d] % a.bs[d]; }
-  const int cpar = (xc[0] + xc[1] + xc[2] + xc[3]) & 1;
-  const long clex = ((long)(xc[3] * a.Xc[2] + xc[2]) * a.Xc[1] + xc[1]) * a.Xc[0] + xc[0];
-  const long A = cpar * a.Vhc + clex / 2;
-  int b = ((yb[3] * a.bs[2] + yb[2]) * a.bs[1] + yb[1]) * a.bs[0] + yb[0];
-  if (a.pm) b = ((yb[0] + yb[1] + yb[2] + yb[3]) & 1) * (a.blockVol / 2) + b / 2;   // block extents even: site parity = block-local parity
-  b2f[A * a.blockVol + b] = (int)f;
-  f2b[f] = (int)(A * a.blockVol + b);
-}
-void Transfer::createGeoMap() {
-  // on the device (round 3): the host loop over 10.6 M sites and its two 42 MB copies cost ~0.1 s of every build at 48^3 x 96
-  GeoMapArg a;
-  for (int d = 0; d < 4; d++) { a.Xf[d] = Xf[d]; a.Xc[d] = Xc[d]; a.bs[d] = geo_bs[d]; }
-  a.blockVol = blockVol; a.pm = parityMajor ? 1 : 0; a.Vh = fineVol / 2; a.Vhc = nAgg / 2;
-  block_to_fine = (int *)poolDeviceMalloc(fineVol * sizeof(int));
-  fine_to_block = (int *)poolDeviceMalloc(fineVol * sizeof(int));
-  hipLaunchKernelGGL(geo_map_kernel, dim3((unsigned)((fineVol + 255) / 256)), dim3(256), 0, computeStream(), block_to_fine, fine_to_block, a);
-  HIP_CHECK(hipGetLastError());
-}
-
-void Transfer::fillAndOrthonormalise(const std::vector<ColorSpinorField *> &B) {
-  VecList vl;
-  memset(&vl, 0, sizeof(vl));
-  for (int v = 0; v < Nvec; v++) { const FineVec f = fineVec(*B[v]); vl.ev[v] = f.v[0]; vl.od[v] = f.v[1]; }
-  const FineVec f0 = fineVec(*B[0]);
-  const long total = fineVol;
-  const int K = fineSpin * fineColor;
-  if (fineSpin == 4) hipLaunchKernelGGL((fillv_kernel<4>), dim3((total + 255) / 256), dim3(256), 0, computeStream(), V, vl, f0.stride, f0.Vh, block_to_fine, blockVol, K, Nvec, total);
-  else hipLaunchKernelGGL((fillv_kernel<2>), dim3((total + 255) / 256), dim3(256), 0, computeStream(), V, vl, f0.stride, f0.Vh, block_to_fine, blockVol, K, Nvec, total);
-  HIP_CHECK(hipGetLastError());
-  static int useQr = -1;
-  if (useQr < 0) { const char *e = getenv("QUDA_AMD_BLOCK_ORTHO"); useQr = (e && !strcmp(e, "gs")) ? 0 : 1; }
-  int nfail = useQr ? 0 : 1;
-  lastGsFallbackBlocks = 0;
-  if (useQr) {
-    int *d_fail = nullptr;   // [0] number of flagged blocks, [1 + b] flag of (aggregate, chirality) block b
-    const size_t failBytes = (1 + 2 * (size_t)nAgg) * sizeof(int);
-    d_fail = (int *)poolDeviceMalloc(failBytes);
-    HIP_CHECK(hipMemsetAsync(d_fail, 0, failBytes, computeStream()));
-    const size_t tileFloats2 = (size_t)kQrChunk * (Nvec + 1) + 1;
-    const size_t lds = tileFloats2 * sizeof(float2) + (size_t)Nvec * Nvec * (sizeof(double2) + sizeof(float2)) + 64;
-#define QA_QR(NV)                                                                                                                  \
-  {                                                                                                                                \
-    HIP_CHECK(hipFuncSetAttribute((const void *)block_cholqr_kernel<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   \
-    hipLaunchKernelGGL((block_cholqr_kernel<NV>), dim3(2 * nAgg), dim3(256), lds, computeStream(), V, blockVol, K, fineColor, spin_bs, d_fail, d_fail + 1); \
-  }
-    switch (Nvec) {
-      case 4: QA_QR(4) break;
-      case 8: QA_QR(8) break;
-      case 24: QA_QR(24) break;
-      case 32: QA_QR(32) break;
-      default: nfail = 1;   // not instantiated: Gram-Schmidt
-    }
-#undef QA_QR
-    HIP_CHECK(hipGetLastError());
-    if (!nfail) HIP_CHECK(hipMemcpyAsync(&nfail, d_fail, sizeof(int), hipMemcpyDeviceToHost, computeStream()));
-    HIP_CHECK(hipStreamSynchronize(computeStream()));
-    if (nfail && (Nvec == 4 || Nvec == 8 || Nvec == 24 || Nvec == 32)) {
-      // flagged blocks hold their original vectors or those times an upper-triangular matrix with a positive diagonal (first round done,
-      // second refused): the same Q either way, so the sequential kernel runs on exactly those blocks, in place
-      if (getVerbosity() >= QUDA_SUMMARIZE) printfQuda("block orthonormalisation: %d of %ld blocks too ill-conditioned for CholeskyQR2 in fp32, Gram-Schmidt on those\n", nfail, 2 * (long)nAgg);
-      hipLaunchKernelGGL(block_gs_kernel, dim3(2 * nAgg), dim3(256), 0, computeStream(), V, blockVol, K, fineColor, spin_bs, Nvec, (const int *)(d_fail + 1));
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipStreamSynchronize(computeStream()));
-      lastGsFallbackBlocks = nfail;
-      nfail = 0;
-    }
-    poolDeviceFree(d_fail, failBytes);
-  }
-  if (nfail) hipLaunchKernelGGL(block_gs_kernel, dim3(2 * nAgg), dim3(256), 0, computeStream(), V, blockVol, K, fineColor, spin_bs, Nvec, (const int *)nullptr);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(computeStream()));
-}
-
-ColorSpinorField *Transfer::createCoarseField() const {
-  ColorSpinorParam p;
-  p.location = QUDA_CUDA_FIELD_LOCATION;
-  p.nSpin = 2; p.nColor = Nvec;
-  for (int d = 0; d < 4; d++) p.x[d] = Xc[d];
-  p.siteSubset = QUDA_FULL_SITE_SUBSET;
-  p.precision = QUDA_SINGLE_PRECISION;
-  p.create = QUDA_ZERO_FIELD_CREATE;
-  return new ColorSpinorField(p);
-}
-ColorSpinorField *Transfer::createFineField() const {
-  ColorSpinorParam p;
-  p.location = QUDA_CUDA_FIELD_LOCATION;
-  p.nSpin = fineSpin; p.nColor = fineColor;
-  for (int d = 0; d < 4; d++) p.x[d] = Xf[d];
-  p.siteSubset = QUDA_FULL_SITE_SUBSET;
-  p.precision = QUDA_SINGLE_PRECISION;
-  p.create = QUDA_ZERO_FIELD_CREATE;
-  return new ColorSpinorField(p);
-}
-
-static CoarseVec coarseVec(const ColorSpinorField &c) {
-  FineVec f = fineVec(c);
-  CoarseVec r;
-  r.v[0] = f.v[0]; r.v[1] = f.v[1]; r.stride = f.stride; r.Vh = f.Vh;
-  return r;
-}
-
-#define QA_TRANSFER_DISPATCH(CALL)                                                             \
-  if (fineSpin == 4 && fineColor == 3) {                                                       \
-    switch (Nvec) {                                                                            \
-      case 4: { CALL(4, 3, 4, 4); } break;                                                     \
-      case 8: { CALL(4, 3, 8, 4); } break;                                                     \
-      case 24: { CALL(4, 3, 24, 4); } break;                                                   \
-      case 32: { CALL(4, 3, 32, 4); } break;                                                   \
-      default: errorQuda("Nvec = %d not instantiated for the fine level (4, 8, 24, 32)", Nvec); \
-    }                                                                                          \
-  } else if (fineSpin == 2 && fineColor == 4 && Nvec == 4) { CALL(2, 4, 4, 2);                 \
-  } else if (fineSpin == 2 && fineColor == 8 && Nvec == 8) { CALL(2, 8, 8, 2);                 \
-  } else if (fineSpin == 2 && fineColor == 8 && Nvec == 4) { CALL(2, 8, 4, 2);                 \
-  } else if (fineSpin == 2 && fineColor == 24 && Nvec == 24) { CALL(2, 24, 24, 2);             \
-  } else if (fineSpin == 2 && fineColor == 24 && Nvec == 32) { CALL(2, 24, 32, 2);             \
-  } else if (fineSpin == 2 && fineColor == 32 && Nvec == 32) { CALL(2, 32, 32, 2);             \
-  } else errorQuda("transfer %d x %d -> Nvec %d not instantiated", fineSpin, fineColor, Nvec);
-
+// ---- host side: every method assembles its arguments from the helpers below and launches through forShape / withV ----
 void Transfer::setSiteSubset(QudaSiteSubset subset, QudaParity parity) {
   if (subset == QUDA_PARITY_SITE_SUBSET && parity != QUDA_EVEN_PARITY && parity != QUDA_ODD_PARITY) errorQuda("Undefined parity %d", parity);
   site_subset = subset;
   subset_parity = parity;
+}
+
+// the instantiated (fine spin, fine colour, Nvec) shapes as compile-time constants: f(Shape<...>{}).  A kernel that exists for some of the
+// shapes only is launched under an `if constexpr` on them, so that no other instantiation appears.
+template <int NSF_, int NCF_, int NVEC_> struct Shape {
+  static constexpr int NSF = NSF_, NCF = NCF_, NVEC = NVEC_, NV = NSF_ == 4 ? 4 : 2;   // NV: reals per vector of the fine field order
+  // the barrier-free stream kernels (restrict_stream_kernel and the four-source pair): fine level, steps summed four at a time
+  static constexpr bool stream = NSF_ == 4 && NVEC_ % 8 == 0;
+};
+template <typename F> static void forShape(const Transfer &T, F &&f) {
+  const int fineSpin = T.fineSpin, fineColor = T.fineColor, Nvec = T.Nvec;
+  if (fineSpin == 4 && fineColor == 3) {
+    switch (Nvec) {
+      case 4: f(Shape<4, 3, 4>{}); break;
+      case 8: f(Shape<4, 3, 8>{}); break;
+      case 24: f(Shape<4, 3, 24>{}); break;
+      case 32: f(Shape<4, 3, 32>{}); break;
+      default: errorQuda("Nvec = %d not instantiated for the fine level (4, 8, 24, 32)", Nvec);
+    }
+  } else if (fineSpin == 2 && fineColor == 4 && Nvec == 4) f(Shape<2, 4, 4>{});
+  else if (fineSpin == 2 && fineColor == 8 && Nvec == 8) f(Shape<2, 8, 8>{});
+  else if (fineSpin == 2 && fineColor == 8 && Nvec == 4) f(Shape<2, 8, 4>{});
+  else if (fineSpin == 2 && fineColor == 24 && Nvec == 24) f(Shape<2, 24, 24>{});
+  else if (fineSpin == 2 && fineColor == 24 && Nvec == 32) f(Shape<2, 24, 32>{});
+  else if (fineSpin == 2 && fineColor == 32 && Nvec == 32) f(Shape<2, 32, 32>{});
+  else errorQuda("transfer %d x %d -> Nvec %d not instantiated", fineSpin, fineColor, Nvec);
+}
+
+// V as the kernels stream it: f(HALF as std::bool_constant, pointer) with the fp16 mirror or the fp32 master
+template <typename F> static void withV(const Transfer &T, bool half, F &&f) {
+  if (half) f(std::true_type{}, (const void *)T.V_h);
+  else f(std::false_type{}, (const void *)T.V);
+}
+
+template <typename... P, typename... A> static void launch(void (*kernel)(P...), int grid, int block, A... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, computeStream(), args...);
+  HIP_CHECK(hipGetLastError());
 }
 
 // the x-neighbour aggregate order (aggregate_of_block) where the blocking allows it; QUDA_AMD_PROLONG_XGROUP=0 switches it off
@@ -1479,231 +702,178 @@ static AggMap aggMapOf(const Transfer &T) {
   return amap;
 }
 
-void Transfer::R(ColorSpinorField &coarse, const ColorSpinorField &fine, int dir, int boundary) const {
-  const bool sub = fine.SiteSubset() == QUDA_PARITY_SITE_SUBSET;
-  if (sub && site_subset != QUDA_PARITY_SITE_SUBSET) errorQuda("single-parity fine field but the transfer is set to full fields");
-  if (fine.Nspin() != fineSpin || fine.Ncolor() != fineColor || (long)fine.VolumeCB() * 2 != fineVol) errorQuda("fine field does not match the transfer operator");
-  if (coarse.Nspin() != 2 || coarse.Ncolor() != Nvec || coarse.Volume() != nAgg) errorQuda("coarse field does not match the transfer operator");
-  const FineVec in = fineVec(fine, sub ? (int)subset_parity : -1);
-  const CoarseVec out = coarseVec(coarse);
+static MaskArg maskArg(const Transfer &T, int dir, int boundary) {
   MaskArg m;
-  m.dir = dir; m.boundary = boundary; m.pm = parityMajor ? 1 : 0;
-  for (int d = 0; d < 4; d++) { m.bs[d] = geo_bs[d]; m.single[d] = Xc[d] == 1; }
-  const int threads = (blockVol + 63) / 64 * 64;
-  int gs = 1; while (gs < blockVol) gs <<= 1;
-  const bool small = blockVol <= 32;
+  m.dir = dir; m.boundary = boundary; m.pm = T.parityMajor ? 1 : 0;
+  for (int d = 0; d < 4; d++) { m.bs[d] = T.geo_bs[d]; m.single[d] = T.Xc[d] == 1; }
+  return m;
+}
+
+// one work-group per aggregate: whole waves that cover its sites, or — small aggregates (the *_small kernels) — 512 threads in groups of gs lanes
+struct WorkGroup { int threads, gs; bool small; };
+static WorkGroup workGroup(const Transfer &T) {
+  WorkGroup w = {(T.blockVol + 63) / 64 * 64, 1, T.blockVol <= 32};
+  while (w.gs < T.blockVol) w.gs <<= 1;
+  return w;
+}
+
+// the shape of a fine operand; a single-parity one needs setSiteSubset (or is refused: fullOnly).  Returns the parity fineVec takes (-1: a full field)
+static int checkFine(const Transfer &T, const ColorSpinorField &fine, bool fullOnly = false) {
+  const bool sub = fine.SiteSubset() == QUDA_PARITY_SITE_SUBSET;
+  if (sub && !fullOnly && T.site_subset != QUDA_PARITY_SITE_SUBSET) errorQuda("single-parity fine field but the transfer is set to full fields");
+  if ((sub && fullOnly) || fine.Nspin() != T.fineSpin || fine.Ncolor() != T.fineColor || (long)fine.VolumeCB() * 2 != T.fineVol) errorQuda("fine field does not match the transfer operator");
+  return sub ? (int)T.subset_parity : -1;
+}
+static CoarseVec checkCoarse(const Transfer &T, const ColorSpinorField &coarse) {
+  if (coarse.Nspin() != 2 || coarse.Ncolor() != T.Nvec || coarse.Volume() != T.nAgg) errorQuda("coarse field does not match the transfer operator");
+  return coarseVec(coarse);
+}
+
+// algorithmic bytes of one pass over V for `sources` vectors: the fraction of V and of the fine vectors that the call touches (vFraction) at
+// vBytes per complex entry of V (fp32 or the fp16 mirror), the fine vectors (+ extraFine further passes over one) and the coarse vectors
+static double transferBytes(const Transfer &T, double frac, int sources, int vBytes, int extraFine = 0) {
+  const double K = (double)T.fineSpin * T.fineColor;
+  return frac * T.fineVol * (K * T.Nvec * vBytes + (sources + extraFine) * K * 8.0) + (double)sources * T.nAgg * 2 * T.Nvec * 8;
+}
+static double vFraction(const ColorSpinorField &fine) { return fine.SiteSubset() == QUDA_PARITY_SITE_SUBSET ? 0.5 : 1.0; }
+
+void Transfer::R(ColorSpinorField &coarse, const ColorSpinorField &fine, int dir, int boundary) const {
+  const FineVec in = fineVec(fine, checkFine(*this, fine));
+  const CoarseVec out = checkCoarse(*this, coarse);
+  const MaskArg m = maskArg(*this, dir, boundary);
+  const WorkGroup w = workGroup(*this);
+  const AggMap amap = aggMapOf(*this);
   const bool half = coarseHalfStorage() && V_h != nullptr && dir < 0;   // the Galerkin-split variants always use the fp32 master
   // the barrier-free restrictor (restrict_stream_kernel): fine level with two chiralities of K / 2 rows, at most four waves per aggregate
   static int streamOff = -1;
   if (streamOff < 0) { const char *e = getenv("QUDA_AMD_RESTRICT_STREAM"); streamOff = (e && !atoi(e)) ? 1 : 0; }
-  const bool stream = !streamOff && !small && threads <= 256 && spin_bs == 2;
-#define QA_R(NSF, NCF, NVEC, NV) \
-  if (small && half) hipLaunchKernelGGL((restrict_small_kernel<NSF, NCF, NVEC, NV, false, true>), dim3(nAgg), dim3(512), 0, computeStream(), out, out, in, (const void *)V_h, block_to_fine, blockVol, gs, spin_bs, m); \
-  else if (small) hipLaunchKernelGGL((restrict_small_kernel<NSF, NCF, NVEC, NV, false, false>), dim3(nAgg), dim3(512), 0, computeStream(), out, out, in, (const void *)V, block_to_fine, blockVol, gs, spin_bs, m); \
-  else if constexpr (NSF == 4 && NVEC % 8 == 0) { \
-    if (stream && half) hipLaunchKernelGGL((restrict_stream_kernel<NSF, NCF, NVEC, NV, true>), dim3(nAgg), dim3(threads), 0, computeStream(), out, in, (const void *)V_h, block_to_fine, blockVol, m, aggMapOf(*this)); \
-    else if (stream) hipLaunchKernelGGL((restrict_stream_kernel<NSF, NCF, NVEC, NV, false>), dim3(nAgg), dim3(threads), 0, computeStream(), out, in, (const void *)V, block_to_fine, blockVol, m, aggMapOf(*this)); \
-    else if (half) hipLaunchKernelGGL((restrict_kernel<NSF, NCF, NVEC, NV, false, true>), dim3(nAgg), dim3(threads), 0, computeStream(), out, out, in, (const void *)V_h, block_to_fine, blockVol, spin_bs, m, aggMapOf(*this)); \
-    else hipLaunchKernelGGL((restrict_kernel<NSF, NCF, NVEC, NV, false, false>), dim3(nAgg), dim3(threads), 0, computeStream(), out, out, in, (const void *)V, block_to_fine, blockVol, spin_bs, m, aggMapOf(*this)); \
-  } \
-  else if (half) hipLaunchKernelGGL((restrict_kernel<NSF, NCF, NVEC, NV, false, true>), dim3(nAgg), dim3(threads), 0, computeStream(), out, out, in, (const void *)V_h, block_to_fine, blockVol, spin_bs, m, aggMapOf(*this)); \
-  else hipLaunchKernelGGL((restrict_kernel<NSF, NCF, NVEC, NV, false, false>), dim3(nAgg), dim3(threads), 0, computeStream(), out, out, in, (const void *)V, block_to_fine, blockVol, spin_bs, m, aggMapOf(*this))
+  const bool stream = !streamOff && !w.small && w.threads <= 256 && spin_bs == 2 && fineSpin == 4 && Nvec % 8 == 0;   // the last two: Shape::stream
+  forShape(*this, [&](auto shape) {
+    using S = decltype(shape);
+    withV(*this, half, [&](auto h, const void *v) {
+      constexpr bool HALF = decltype(h)::value;
+      if (w.small) launch(restrict_small_kernel<S::NSF, S::NCF, S::NVEC, S::NV, false, HALF>, nAgg, 512, out, out, in, v, block_to_fine, blockVol, w.gs, spin_bs, m);
+      else if (!stream) launch(restrict_kernel<S::NSF, S::NCF, S::NVEC, S::NV, false, HALF>, nAgg, w.threads, out, out, in, v, block_to_fine, blockVol, spin_bs, m, amap);
+      else if constexpr (S::stream) launch(restrict_stream_kernel<S::NSF, S::NCF, S::NVEC, S::NV, HALF>, nAgg, w.threads, out, in, v, block_to_fine, blockVol, m, amap);
+    });
+  });
   if (g_acctOn) {   // V once (fp32 or its fp16 mirror; a single-parity source touches half of it) + fine vector + coarse vector
-    const double frac = sub ? 0.5 : 1.0;
     char tag[48]; snprintf(tag, sizeof(tag), "level %s -> coarse%s", fineSpin == 4 ? "0" : "c", half ? " fp16 V" : "");
-    const bool streamed = stream && fineSpin == 4 && Nvec % 8 == 0;
-    acct(small ? "restrict_small_kernel" : (streamed ? "restrict_stream_kernel" : "restrict_kernel"), frac * fineVol * ((double)fineSpin * fineColor * Nvec * (half ? 4 : 8) + fineSpin * fineColor * 8.0) + (double)nAgg * 2 * Nvec * 8, tag);
+    acct(w.small ? "restrict_small_kernel" : (stream ? "restrict_stream_kernel" : "restrict_kernel"), transferBytes(*this, vFraction(fine), 1, half ? 4 : 8), tag);
   }
-  QA_TRANSFER_DISPATCH(QA_R)
-#undef QA_R
-  HIP_CHECK(hipGetLastError());
   flops_ += 8ull * fineSpin * fineColor * Nvec * fineVol;  // reference lib/restrictor.cu:405
 }
 
 void Transfer::RSplit(ColorSpinorField &leaving, ColorSpinorField &staying, const ColorSpinorField &fine, int dir) const {
   if (fine.SiteSubset() != QUDA_FULL_SITE_SUBSET) errorQuda("the split restriction works on full fields");
-  if (fine.Nspin() != fineSpin || fine.Ncolor() != fineColor || fine.Volume() != fineVol) errorQuda("fine field does not match the transfer operator");
-  if (leaving.Nspin() != 2 || leaving.Ncolor() != Nvec || leaving.Volume() != nAgg || staying.Volume() != nAgg || staying.Ncolor() != Nvec) errorQuda("coarse field does not match the transfer operator");
   if (dir < 0 || dir > 7) errorQuda("direction %d", dir);
-  const FineVec in = fineVec(fine);
-  const CoarseVec out = coarseVec(leaving), out2 = coarseVec(staying);
-  MaskArg m;
-  m.dir = dir; m.boundary = 1; m.pm = parityMajor ? 1 : 0;
-  for (int d = 0; d < 4; d++) { m.bs[d] = geo_bs[d]; m.single[d] = Xc[d] == 1; }
-  const int threads = (blockVol + 63) / 64 * 64;
-  int gs = 1; while (gs < blockVol) gs <<= 1;
-  const bool small = blockVol <= 32;
-#define QA_R2(NSF, NCF, NVEC, NV) \
-  if (small) hipLaunchKernelGGL((restrict_small_kernel<NSF, NCF, NVEC, NV, true, false>), dim3(nAgg), dim3(512), 0, computeStream(), out, out2, in, (const void *)V, block_to_fine, blockVol, gs, spin_bs, m); \
-  else hipLaunchKernelGGL((restrict_kernel<NSF, NCF, NVEC, NV, true, false>), dim3(nAgg), dim3(threads), 0, computeStream(), out, out2, in, (const void *)V, block_to_fine, blockVol, spin_bs, m, aggMapOf(*this))
-  QA_TRANSFER_DISPATCH(QA_R2)
-#undef QA_R2
-  HIP_CHECK(hipGetLastError());
+  const FineVec in = fineVec(fine, checkFine(*this, fine, true));
+  const CoarseVec out = checkCoarse(*this, leaving), out2 = checkCoarse(*this, staying);
+  const MaskArg m = maskArg(*this, dir, 1);
+  const WorkGroup w = workGroup(*this);
+  const AggMap amap = aggMapOf(*this);
+  forShape(*this, [&](auto shape) {
+    using S = decltype(shape);
+    if (w.small) launch(restrict_small_kernel<S::NSF, S::NCF, S::NVEC, S::NV, true, false>, nAgg, 512, out, out2, in, (const void *)V, block_to_fine, blockVol, w.gs, spin_bs, m);
+    else launch(restrict_kernel<S::NSF, S::NCF, S::NVEC, S::NV, true, false>, nAgg, w.threads, out, out2, in, (const void *)V, block_to_fine, blockVol, spin_bs, m, amap);
+  });
   flops_ += 8ull * fineSpin * fineColor * Nvec * fineVol;
 }
 
 void Transfer::P(ColorSpinorField &fine, const ColorSpinorField &coarse) const {
-  const bool sub = fine.SiteSubset() == QUDA_PARITY_SITE_SUBSET;
-  if (sub && site_subset != QUDA_PARITY_SITE_SUBSET) errorQuda("single-parity fine field but the transfer is set to full fields");
-  if (fine.Nspin() != fineSpin || fine.Ncolor() != fineColor || (long)fine.VolumeCB() * 2 != fineVol) errorQuda("fine field does not match the transfer operator");
-  if (coarse.Nspin() != 2 || coarse.Ncolor() != Nvec || coarse.Volume() != nAgg) errorQuda("coarse field does not match the transfer operator");
-  const FineVec out = fineVec(fine, sub ? (int)subset_parity : -1);
-  const CoarseVec in = coarseVec(coarse);
-  const int threads = (blockVol + 63) / 64 * 64;
-  if (threads > 512) errorQuda("aggregates of %d sites: the prolongator runs one work-group of at most 512 threads per aggregate", blockVol);
-  int gs = 1; while (gs < blockVol) gs <<= 1;
-  const bool small = blockVol <= 32;
-  const bool half = coarseHalfStorage() && V_h != nullptr;
-#define QA_P(NSF, NCF, NVEC, NV) \
-  if (small && half) hipLaunchKernelGGL((prolong_small_kernel<NSF, NCF, NVEC, NV, true>), dim3(nAgg), dim3(512), 0, computeStream(), out, in, (const void *)V_h, block_to_fine, blockVol, gs, spin_bs); \
-  else if (small) hipLaunchKernelGGL((prolong_small_kernel<NSF, NCF, NVEC, NV, false>), dim3(nAgg), dim3(512), 0, computeStream(), out, in, (const void *)V, block_to_fine, blockVol, gs, spin_bs); \
-  else if (half) hipLaunchKernelGGL((prolong_kernel<NSF, NCF, NVEC, NV, true>), dim3(nAgg), dim3(threads), 0, computeStream(), out, in, (const void *)V_h, block_to_fine, blockVol, spin_bs, amap); \
-  else hipLaunchKernelGGL((prolong_kernel<NSF, NCF, NVEC, NV, false>), dim3(nAgg), dim3(threads), 0, computeStream(), out, in, (const void *)V, block_to_fine, blockVol, spin_bs, amap)
+  const FineVec out = fineVec(fine, checkFine(*this, fine));
+  const CoarseVec in = checkCoarse(*this, coarse);
+  const WorkGroup w = workGroup(*this);
+  if (w.threads > 512) errorQuda("aggregates of %d sites: the prolongator runs one work-group of at most 512 threads per aggregate", blockVol);
   const AggMap amap = aggMapOf(*this);
+  const bool half = coarseHalfStorage() && V_h != nullptr;
+  forShape(*this, [&](auto shape) {
+    using S = decltype(shape);
+    withV(*this, half, [&](auto h, const void *v) {
+      constexpr bool HALF = decltype(h)::value;
+      if (w.small) launch(prolong_small_kernel<S::NSF, S::NCF, S::NVEC, S::NV, HALF>, nAgg, 512, out, in, v, block_to_fine, blockVol, w.gs, spin_bs);
+      else launch(prolong_kernel<S::NSF, S::NCF, S::NVEC, S::NV, HALF>, nAgg, w.threads, out, in, v, block_to_fine, blockVol, spin_bs, amap);
+    });
+  });
   if (g_acctOn) {
-    const double frac = sub ? 0.5 : 1.0;
     char tag[48]; snprintf(tag, sizeof(tag), "coarse -> level %s%s", fineSpin == 4 ? "0" : "c", half ? " fp16 V" : "");
-    acct(small ? "prolong_small_kernel" : "prolong_kernel", frac * fineVol * ((double)fineSpin * fineColor * Nvec * (half ? 4 : 8) + fineSpin * fineColor * 8.0) + (double)nAgg * 2 * Nvec * 8, tag);
+    acct(w.small ? "prolong_small_kernel" : "prolong_kernel", transferBytes(*this, vFraction(fine), 1, half ? 4 : 8), tag);
   }
-  QA_TRANSFER_DISPATCH(QA_P)
-#undef QA_P
-  HIP_CHECK(hipGetLastError());
   flops_ += 8ull * fineSpin * fineColor * Nvec * fineVol;  // reference lib/prolongator.cu:228
 }
 
-// four sources per pass over V (fine level, fp32 V): see restrict_stream4_kernel / prolong4_kernel
+// ---- four sources per pass over V (fine level, fp32 V): see restrict_stream4_kernel / prolong4_kernel ----
 bool Transfer::canQuad() const { return fineSpin == 4 && fineColor == 3 && spin_bs == 2 && blockVol > 32 && blockVol <= 256 && (Nvec == 8 || Nvec == 24 || Nvec == 32); }
+
+// the operands of R4 / P4 (fine fields, all of one site subset) and of R4Block / P4Block (fine == nullptr: the fine side is a Blk4)
+static Src4 src4(const Transfer &T, const ColorSpinorField *const *fine, const ColorSpinorField *const *coarse) {
+  Src4 a;
+  memset(&a, 0, sizeof(a));
+  for (int s = 0; s < 4; s++) {
+    a.c[s] = checkCoarse(T, *coarse[s]);
+    if (!fine) continue;
+    if (fine[s]->SiteSubset() != fine[0]->SiteSubset()) errorQuda("fine field does not match the transfer operator");
+    a.f[s] = fineVec(*fine[s], checkFine(T, *fine[s]));
+  }
+  return a;
+}
+static Blk4 blk4(const Transfer &T, const float2 *panel, int nrhs, int col0, bool accumulate) {
+  return {reinterpret_cast<float4 *>(const_cast<float2 *>(panel)), nrhs, col0, T.subset_parity == QUDA_ODD_PARITY ? 1 : 0, (int)(T.fineVol / 2), accumulate ? 1 : 0};
+}
+template <bool BLK> static void launchQuad(const Transfer &T, bool restrictor, const Src4 &a, const Blk4 &blk) {
+  const int threads = workGroup(T).threads;
+  const AggMap amap = aggMapOf(T);
+  forShape(T, [&](auto shape) {
+    using S = decltype(shape);
+    if constexpr (S::stream) {   // canQuad
+      if (restrictor) launch(restrict_stream4_kernel<S::NCF, S::NVEC, S::NV, BLK>, T.nAgg, threads, a, (const void *)T.V, T.block_to_fine, T.blockVol, maskArg(T, -1, 0), amap, blk);
+      else launch(prolong4_kernel<S::NCF, S::NVEC, S::NV, BLK>, T.nAgg, threads, a, (const void *)T.V, T.block_to_fine, T.blockVol, amap, blk);
+    }
+  });
+}
+
 void Transfer::R4(ColorSpinorField *const coarse[4], const ColorSpinorField *const fine[4]) const {
   if (!canQuad()) errorQuda("four-source restrictor: fine level with 4^4-type aggregates only");
-  const bool sub = fine[0]->SiteSubset() == QUDA_PARITY_SITE_SUBSET;
-  if (sub && site_subset != QUDA_PARITY_SITE_SUBSET) errorQuda("single-parity fine field but the transfer is set to full fields");
-  Src4 a;
-  for (int s = 0; s < 4; s++) {
-    if (fine[s]->Nspin() != fineSpin || fine[s]->Ncolor() != fineColor || (long)fine[s]->VolumeCB() * 2 != fineVol || fine[s]->SiteSubset() != fine[0]->SiteSubset() || fine[s]->Precision() != QUDA_SINGLE_PRECISION)
-      errorQuda("fine field %d does not match the transfer operator", s);
-    a.f[s] = fineVec(*fine[s], sub ? (int)subset_parity : -1);
-    a.c[s] = coarseVec(*coarse[s]);
-  }
-  MaskArg m;
-  m.dir = -1; m.boundary = 0; m.pm = parityMajor ? 1 : 0;
-  for (int d = 0; d < 4; d++) { m.bs[d] = geo_bs[d]; m.single[d] = Xc[d] == 1; }
-  const int threads = (blockVol + 63) / 64 * 64;
-  if (g_acctOn) {
-    const double frac = sub ? 0.5 : 1.0;
-    acct("restrict_stream4_kernel", frac * fineVol * ((double)fineSpin * fineColor * Nvec * 8 + 4.0 * fineSpin * fineColor * 8.0) + 4.0 * nAgg * 2 * Nvec * 8, "level 0 -> coarse, 4 sources");
-  }
-  switch (Nvec) {
-    case 8: hipLaunchKernelGGL((restrict_stream4_kernel<3, 8, 4>), dim3(nAgg), dim3(threads), 0, computeStream(), a, (const void *)V, block_to_fine, blockVol, m, aggMapOf(*this), Blk4{}); break;
-    case 24: hipLaunchKernelGGL((restrict_stream4_kernel<3, 24, 4>), dim3(nAgg), dim3(threads), 0, computeStream(), a, (const void *)V, block_to_fine, blockVol, m, aggMapOf(*this), Blk4{}); break;
-    default: hipLaunchKernelGGL((restrict_stream4_kernel<3, 32, 4>), dim3(nAgg), dim3(threads), 0, computeStream(), a, (const void *)V, block_to_fine, blockVol, m, aggMapOf(*this), Blk4{}); break;
-  }
-  HIP_CHECK(hipGetLastError());
+  launchQuad<false>(*this, true, src4(*this, fine, coarse), Blk4{});
+  if (g_acctOn) acct("restrict_stream4_kernel", transferBytes(*this, vFraction(*fine[0]), 4, 8), "level 0 -> coarse, 4 sources");
   flops_ += 4 * 8ull * fineSpin * fineColor * Nvec * fineVol;
 }
 void Transfer::P4(ColorSpinorField *const fine[4], const ColorSpinorField *const coarse[4]) const {
   if (!canQuad()) errorQuda("four-source prolongator: fine level with 4^4-type aggregates only");
-  const bool sub = fine[0]->SiteSubset() == QUDA_PARITY_SITE_SUBSET;
-  if (sub && site_subset != QUDA_PARITY_SITE_SUBSET) errorQuda("single-parity fine field but the transfer is set to full fields");
-  Src4 a;
-  for (int s = 0; s < 4; s++) {
-    if (fine[s]->Nspin() != fineSpin || fine[s]->Ncolor() != fineColor || (long)fine[s]->VolumeCB() * 2 != fineVol || fine[s]->SiteSubset() != fine[0]->SiteSubset() || fine[s]->Precision() != QUDA_SINGLE_PRECISION)
-      errorQuda("fine field %d does not match the transfer operator", s);
-    a.f[s] = fineVec(*fine[s], sub ? (int)subset_parity : -1);
-    a.c[s] = coarseVec(*coarse[s]);
-  }
-  const int threads = (blockVol + 63) / 64 * 64;
-  const AggMap amap = aggMapOf(*this);
-  if (g_acctOn) {
-    const double frac = sub ? 0.5 : 1.0;
-    acct("prolong4_kernel", frac * fineVol * ((double)fineSpin * fineColor * Nvec * 8 + 4.0 * fineSpin * fineColor * 8.0) + 4.0 * nAgg * 2 * Nvec * 8, "coarse -> level 0, 4 sources");
-  }
-  switch (Nvec) {
-    case 8: hipLaunchKernelGGL((prolong4_kernel<3, 8, 4>), dim3(nAgg), dim3(threads), 0, computeStream(), a, (const void *)V, block_to_fine, blockVol, amap, Blk4{}); break;
-    case 24: hipLaunchKernelGGL((prolong4_kernel<3, 24, 4>), dim3(nAgg), dim3(threads), 0, computeStream(), a, (const void *)V, block_to_fine, blockVol, amap, Blk4{}); break;
-    default: hipLaunchKernelGGL((prolong4_kernel<3, 32, 4>), dim3(nAgg), dim3(threads), 0, computeStream(), a, (const void *)V, block_to_fine, blockVol, amap, Blk4{}); break;
-  }
-  HIP_CHECK(hipGetLastError());
+  launchQuad<false>(*this, false, src4(*this, fine, coarse), Blk4{});
+  if (g_acctOn) acct("prolong4_kernel", transferBytes(*this, vFraction(*fine[0]), 4, 8), "coarse -> level 0, 4 sources");
   flops_ += 4 * 8ull * fineSpin * fineColor * Nvec * fineVol;
 }
 
 // ... with the fine vectors in four columns of a pair-major block field of one parity (block.h): the multi-source smoother's residuals in, its solutions out
 void Transfer::R4Block(ColorSpinorField *const coarse[4], const float2 *panel, int nrhs, int col0) const {
   if (!canQuad() || site_subset != QUDA_PARITY_SITE_SUBSET) errorQuda("four-source restrictor on block fields: fine level, single-parity transfers");
-  Src4 a;
-  memset(&a, 0, sizeof(a));
-  for (int s = 0; s < 4; s++) a.c[s] = coarseVec(*coarse[s]);
-  const Blk4 blk = {reinterpret_cast<float4 *>(const_cast<float2 *>(panel)), nrhs, col0, subset_parity == QUDA_ODD_PARITY ? 1 : 0, (int)(fineVol / 2), 0};
-  MaskArg m;
-  m.dir = -1; m.boundary = 0; m.pm = parityMajor ? 1 : 0;
-  for (int d = 0; d < 4; d++) { m.bs[d] = geo_bs[d]; m.single[d] = Xc[d] == 1; }
-  const int threads = (blockVol + 63) / 64 * 64;
-  acct("restrict_stream4_kernel", 0.5 * fineVol * ((double)fineSpin * fineColor * Nvec * 8 + 4.0 * fineSpin * fineColor * 8.0) + 4.0 * nAgg * 2 * Nvec * 8, "level 0 (block columns) -> coarse, 4 sources");
-  switch (Nvec) {
-    case 8: hipLaunchKernelGGL((restrict_stream4_kernel<3, 8, 4, true>), dim3(nAgg), dim3(threads), 0, computeStream(), a, (const void *)V, block_to_fine, blockVol, m, aggMapOf(*this), blk); break;
-    case 24: hipLaunchKernelGGL((restrict_stream4_kernel<3, 24, 4, true>), dim3(nAgg), dim3(threads), 0, computeStream(), a, (const void *)V, block_to_fine, blockVol, m, aggMapOf(*this), blk); break;
-    default: hipLaunchKernelGGL((restrict_stream4_kernel<3, 32, 4, true>), dim3(nAgg), dim3(threads), 0, computeStream(), a, (const void *)V, block_to_fine, blockVol, m, aggMapOf(*this), blk); break;
-  }
-  HIP_CHECK(hipGetLastError());
+  launchQuad<true>(*this, true, src4(*this, nullptr, coarse), blk4(*this, panel, nrhs, col0, false));
+  if (g_acctOn) acct("restrict_stream4_kernel", transferBytes(*this, 0.5, 4, 8), "level 0 (block columns) -> coarse, 4 sources");
   flops_ += 4 * 8ull * fineSpin * fineColor * Nvec * fineVol / 2;
 }
 void Transfer::P4Block(float2 *panel, int nrhs, int col0, bool accumulate, const ColorSpinorField *const coarse[4]) const {
   if (!canQuad() || site_subset != QUDA_PARITY_SITE_SUBSET) errorQuda("four-source prolongator on block fields: fine level, single-parity transfers");
-  Src4 a;
-  memset(&a, 0, sizeof(a));
-  for (int s = 0; s < 4; s++) a.c[s] = coarseVec(*coarse[s]);
-  const Blk4 blk = {reinterpret_cast<float4 *>(panel), nrhs, col0, subset_parity == QUDA_ODD_PARITY ? 1 : 0, (int)(fineVol / 2), accumulate ? 1 : 0};
-  const int threads = (blockVol + 63) / 64 * 64;
-  const AggMap amap = aggMapOf(*this);
-  acct("prolong4_kernel", 0.5 * fineVol * ((double)fineSpin * fineColor * Nvec * 8 + (accumulate ? 8.0 : 4.0) * fineSpin * fineColor * 8.0) + 4.0 * nAgg * 2 * Nvec * 8, "coarse -> level 0 (block columns), 4 sources");
-  switch (Nvec) {
-    case 8: hipLaunchKernelGGL((prolong4_kernel<3, 8, 4, true>), dim3(nAgg), dim3(threads), 0, computeStream(), a, (const void *)V, block_to_fine, blockVol, amap, blk); break;
-    case 24: hipLaunchKernelGGL((prolong4_kernel<3, 24, 4, true>), dim3(nAgg), dim3(threads), 0, computeStream(), a, (const void *)V, block_to_fine, blockVol, amap, blk); break;
-    default: hipLaunchKernelGGL((prolong4_kernel<3, 32, 4, true>), dim3(nAgg), dim3(threads), 0, computeStream(), a, (const void *)V, block_to_fine, blockVol, amap, blk); break;
-  }
-  HIP_CHECK(hipGetLastError());
+  launchQuad<true>(*this, false, src4(*this, nullptr, coarse), blk4(*this, panel, nrhs, col0, accumulate));
+  if (g_acctOn) acct("prolong4_kernel", transferBytes(*this, 0.5, 4, 8, accumulate ? 4 : 0), "coarse -> level 0 (block columns), 4 sources");
   flops_ += 4 * 8ull * fineSpin * fineColor * Nvec * fineVol / 2;
 }
 
-void Transfer::column(ColorSpinorField &fine, int j) const {
-  if (fine.SiteSubset() != QUDA_FULL_SITE_SUBSET || fine.Nspin() != fineSpin || fine.Ncolor() != fineColor || fine.Volume() != fineVol) errorQuda("fine field does not match the transfer operator");
-  if (j < 0 || j >= 2 * Nvec) errorQuda("coarse component %d of %d", j, 2 * Nvec);
-  const FineVec out = fineVec(fine);
-  const int bs = 256;
-  const long total = fineVol;
-  if (fineSpin == 4) hipLaunchKernelGGL((column_kernel<4, 3, 4>), dim3((unsigned)((total + bs - 1) / bs)), dim3(bs), 0, computeStream(), out, (const float4 *)V, block_to_fine, blockVol, spin_bs, Nvec, j, total);
-  else {
-    switch (fineColor) {
-      case 4: hipLaunchKernelGGL((column_kernel<2, 4, 2>), dim3((unsigned)((total + bs - 1) / bs)), dim3(bs), 0, computeStream(), out, (const float4 *)V, block_to_fine, blockVol, spin_bs, Nvec, j, total); break;
-      case 8: hipLaunchKernelGGL((column_kernel<2, 8, 2>), dim3((unsigned)((total + bs - 1) / bs)), dim3(bs), 0, computeStream(), out, (const float4 *)V, block_to_fine, blockVol, spin_bs, Nvec, j, total); break;
-      case 24: hipLaunchKernelGGL((column_kernel<2, 24, 2>), dim3((unsigned)((total + bs - 1) / bs)), dim3(bs), 0, computeStream(), out, (const float4 *)V, block_to_fine, blockVol, spin_bs, Nvec, j, total); break;
-      case 32: hipLaunchKernelGGL((column_kernel<2, 32, 2>), dim3((unsigned)((total + bs - 1) / bs)), dim3(bs), 0, computeStream(), out, (const float4 *)V, block_to_fine, blockVol, spin_bs, Nvec, j, total); break;
-      default: errorQuda("column extraction for %d fine colours not instantiated", fineColor);
-    }
-  }
-  HIP_CHECK(hipGetLastError());
-}
-
+// ---- the Galerkin split of four fine vectors, each with its own direction, in one pass over V (restrict4_kernel) ----
 bool Transfer::canSplit4() const { return fineSpin == 4 && fineColor == 3 && blockVol > 32 && blockVol <= 256; }
 
 void Transfer::RSplit4(ColorSpinorField *const leaving[4], ColorSpinorField *const staying[4], ColorSpinorField *const fine[4], const int dir[4]) const {
   if (!canSplit4()) errorQuda("the four-way split restriction is built for the fine level");
   Multi4 a;
   for (int q = 0; q < 4; q++) {
-    if (fine[q]->SiteSubset() != QUDA_FULL_SITE_SUBSET || fine[q]->Volume() != fineVol) errorQuda("fine field does not match the transfer operator");
-    a.in[q] = fineVec(*fine[q]); a.out[q] = coarseVec(*leaving[q]); a.out2[q] = coarseVec(*staying[q]); a.dir[q] = dir[q];
+    a.in[q] = fineVec(*fine[q], checkFine(*this, *fine[q], true));
+    a.out[q] = checkCoarse(*this, *leaving[q]); a.out2[q] = checkCoarse(*this, *staying[q]); a.dir[q] = dir[q];
   }
-  MaskArg m;
-  m.dir = 0; m.boundary = 1; m.pm = parityMajor ? 1 : 0;
-  for (int d = 0; d < 4; d++) { m.bs[d] = geo_bs[d]; m.single[d] = Xc[d] == 1; }
-  const int threads = (blockVol + 63) / 64 * 64;
-  switch (Nvec) {
-    case 4: hipLaunchKernelGGL((restrict4_kernel<4, 3, 4, 4>), dim3(nAgg), dim3(threads), 0, computeStream(), a, (const float4 *)V, block_to_fine, blockVol, spin_bs, m, aggMapOf(*this)); break;
-    case 8: hipLaunchKernelGGL((restrict4_kernel<4, 3, 8, 4>), dim3(nAgg), dim3(threads), 0, computeStream(), a, (const float4 *)V, block_to_fine, blockVol, spin_bs, m, aggMapOf(*this)); break;
-    case 24: hipLaunchKernelGGL((restrict4_kernel<4, 3, 24, 4>), dim3(nAgg), dim3(threads), 0, computeStream(), a, (const float4 *)V, block_to_fine, blockVol, spin_bs, m, aggMapOf(*this)); break;
-    case 32: hipLaunchKernelGGL((restrict4_kernel<4, 3, 32, 4>), dim3(nAgg), dim3(threads), 0, computeStream(), a, (const float4 *)V, block_to_fine, blockVol, spin_bs, m, aggMapOf(*this)); break;
-    default: errorQuda("Nvec = %d not instantiated", Nvec);
-  }
-  HIP_CHECK(hipGetLastError());
+  forShape(*this, [&](auto shape) {
+    using S = decltype(shape);
+    if constexpr (S::NSF == 4)
+      launch(restrict4_kernel<S::NSF, S::NCF, S::NVEC, S::NV>, nAgg, workGroup(*this).threads, a, (const float4 *)V, block_to_fine, blockVol, spin_bs, maskArg(*this, 0, 1), aggMapOf(*this));
+  });
   flops_ += 4 * 8ull * fineSpin * fineColor * Nvec * fineVol;
 }
 

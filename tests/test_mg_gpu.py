@@ -175,7 +175,7 @@ def test_hierarchy_against_oracle_restatement(qa, oracle, mask):
 @pytest.mark.parametrize("X", [(16, 8, 8, 16), (32, 8, 8, 8), (16, 16, 8, 8)])
 def test_restrictor_and_prolongator_in_the_x_neighbour_order(qa, oracle, X):
     """Lattices with four or more aggregates along x, where the transfer kernels walk the x-neighbour aggregates on one XCD
-    (transfer.hip aggregate_of_block) — a re-numbering of the work-groups that must not change R or P: element-wise against the
+    (transfer_device.h aggregate_of_block) — a re-numbering of the work-groups that must not change R or P: element-wise against the
     oracle with the device's own V, with the order switched on (default) — the hierarchy test above runs on 2 aggregates along x,
     where it is off."""
     kappa, mu = 0.124, 0.005
@@ -573,7 +573,7 @@ def _write_null_vectors(path, X, B):
 
 @pytest.mark.parametrize("eps,expect_fallback", [(3e-2, False), (1e-3, True), ("mixed", True)], ids=["cond-1e2", "cond-1e3", "ill-conditioned-in-some-blocks"])
 def test_block_orthonormalisation_of_nearly_dependent_vectors(qa, oracle, tmp_path, eps, expect_fallback):
-    """ADVICE r2 (transfer.hip pivot test): locally coherent near-null vectors make the block Gram matrices ill-conditioned.  The fp32
+    """ADVICE r2 (transfer_setup.hip pivot test): locally coherent near-null vectors make the block Gram matrices ill-conditioned.  The fp32
     CholeskyQR2 kernel has to notice what is beyond it — pivots at the round-off level of an fp32 Gram matrix, a first round that is
     not close to orthonormal — and hand exactly those blocks to Gram-Schmidt.  Vectors v_k = v_0 + eps r_k go in through vec_infile;
     checked: P^dag P = 1 per block to fp32 level (|V^dag V - 1| element-wise), the span (identity (1) of MG::verify), agreement with

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Seconds per restriction / prolongation of level 0 of a 3-level hierarchy (24 null vectors, 4^4 aggregates), with the HBM rate
-on V + fine + coarse vector.  usage: transfer_timing.py [lattice]   (QUDA_AMD_PROLONG_VAR selects a prolongator variant)"""
+on V + fine + coarse vector.  usage: transfer_timing.py [lattice]"""
 import importlib
 import os
 import sys
@@ -25,7 +25,7 @@ V = int(np.prod(X))
 nbytes = V * 12 * 24 * 8 + V * 24 * 4 + V // 256 * 48 * 8
 for what in ("R", "P"):
     s = min(mg.time_transfer(0, what, 20) for _ in range(3))
-    print("%s lattice %s var %s: %.1f us  %.0f GB/s  %.3f of 8 TB/s" % (what, "x".join(map(str, X)), os.environ.get("QUDA_AMD_PROLONG_VAR", "0"), 1e6 * s, nbytes / s * 1e-9, nbytes / s / 8e12))
+    print("%s lattice %s: %.1f us  %.0f GB/s  %.3f of 8 TB/s" % (what, "x".join(map(str, X)), 1e6 * s, nbytes / s * 1e-9, nbytes / s / 8e12))
 print("setup %.3f s" % mp.secs)
 mg.free()
 qa.end()
