@@ -80,6 +80,14 @@ bool blockCoarseSupported(const CoarseGauge &G, int nrhs);
 // parity >= 0: only the output sites of that parity are computed (and written) — half the link traffic where the caller wants one parity anyway
 void applyCoarseBlock(BlockField &out, BlockField &in, const CoarseGauge &G, int parity = -1);
 
+// One piece of the even-odd preconditioned coarse system as the block-field cycle of block_solver.cpp computes it (BlockCoarseCycle::matpc /
+// prepare / reconstruct on a one-level cycle made for the call; Y: links, H: preconditioned links, p: parity of the system), on nrhs full coarse
+// fields.  op 0: out = Mhat in (in on parity p); op 1: out = the preconditioned source of b; op 2: out = x reconstructed from in (parity p) and b.
+// Every work field is preloaded with nonzero words on both parities; returns the nonzero words left in the half of matpc's temporary that its
+// second application multiplies with Xinv (matpc clears it).
+int blockCoarseSchurPiece(const CoarseGauge &Y, const CoarseGauge &H, int p, int op, int nrhs, const std::vector<ColorSpinorField *> &out,
+                          const std::vector<ColorSpinorField *> &in, const std::vector<ColorSpinorField *> &b);
+
 // [site][9] table of the panel indices of a site's 8 neighbours (order of the link matrices: 2 mu forward, 2 mu + 1 backward) and of
 // the site itself: parity * Vh + x_cb, or — across a partitioned face — the ghost panel nSites + offset + face index; device memory,
 // built once per coarse lattice and partition mask

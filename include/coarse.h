@@ -85,5 +85,8 @@ class DiracCoarsePC : public DiracCoarse {
 
 // mmask: bit m set = include matrix m (0..7 hops, 8 local); parity: -1 both, else only that output parity
 void applyCoarse(ColorSpinorField &out, const ColorSpinorField &in, const CoarseGauge &G, int mmask, int parity);
+// hat = the preconditioned links of `links` (slot 8 = X^-1 by a batched Gauss-Jordan elimination with partial pivoting, slots 0..7 = X^-1 H_d);
+// returns 1 if some X had an identically zero pivot column (DiracCoarse::HatLinks stops there), else 0
+int coarseInvertHat(CoarseGauge &hat, const CoarseGauge &links);
 
 }  // namespace quda

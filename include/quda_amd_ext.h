@@ -192,6 +192,31 @@ void qudaAmdMultigridApply(void *mg_instance, int level, int op, float *h_out, c
  *   op 5  P4Block  accumulate = 0, op 6: accumulate = 1.  h_in: 4 coarse vectors, then the 8 fine vectors the 8-column parity block
  *                  field is preloaded with; the prolongation goes to columns 4..7; h_out: all 8 columns as fine vectors (parity >= 0 only) */
 void qudaAmdMultigridApplyTransfer(void *mg_instance, int level, int op, int parity, float *h_out, const float *h_in);
+/* The even-odd preconditioned coarse operator piece by piece (tests/test_coarse_pc_gpu.py against tests/coarse_ref.py).  `level` names the finer
+ * level, as for qudaAmdMultigridGetCoarseLinks: the operator lives on level + 1.  Vectors in the layout of qudaAmdMultigridApply; a parity field
+ * is the half [parity * Vh, (parity + 1) * Vh) of one; several vectors lie back to back.
+ * GetCoarseSiteLinks: the nine matrices every coarse site multiplies with, in the device's own bidirectional meaning (include/coarse.h),
+ *   h_out[site][m][row][col] complex fp32, m = 2 mu forward hop, 2 mu + 1 backward hop, 8 local.  which 0: the links (8 = X), 1: the
+ *   preconditioned links Xinv H_d (8 = Xinv), 2 / 3: the same read back from the fp16 mirror and widened (an error if there is no mirror).
+ *   GetCoarseLinks folds the backward links into the reference's dagger convention, which the preconditioned links do not obey.
+ * CoarseApply: applyCoarse itself on the links (which 0) or the preconditioned links (1) with matrix mask mmask (bit m = matrix m).  parity -1:
+ *   full fields.  parity 0 / 1: parity fields, h_out the half of that parity, h_in the half the call reads — the other parity for hops, the
+ *   same parity for mmask == 1 << 8.  The fp16 mirror is read when half storage is on.  Returns the number of words of the device's input
+ *   field (both parities) that differ afterwards from what was loaded: 0 unless the operator wrote into its input.
+ * CoarsePC: the Schur pieces with matpc = parity on nrhs vectors.  op 0: Mhat, h_in nrhs parity fields; op 1: prepare for a MAT solution, h_in
+ *   nrhs full sources b, the preconditioned source comes back on `parity`; op 2: reconstruct, h_in nrhs solved parity fields x then nrhs full b.
+ *   h_out: nrhs FULL fields in every case (what the routine leaves on the other parity is part of the answer).  impl 0: DiracCoarsePC, nrhs = 1
+ *   (the level's smoother operator where its matpc fits, else one made for the call that shares the links).  impl 1: BlockCoarseCycle::matpc /
+ *   prepare / reconstruct of csrc/block_solver.cpp on the MFMA kernel, nrhs in {8, 16, 24}, every work field preloaded with nonzero words on both
+ *   parities.  Returns (impl 1) the nonzero words left in the half of matpc's temporary that its second application multiplies with Xinv,
+ *   else 0.
+ * qudaAmdCoarseInvertSites: coarse_invert_kernel and coarse_hat_kernel on matrices of the caller (no hierarchy): h_X[site][row][col], h_H[site]
+ *   [d = 0..7][row][col] (NULL: zeros) -> h_Xinv, h_hat (NULL: not returned); *fail = the kernel's flag (1: an identically zero pivot column
+ *   somewhere) where DiracCoarse::HatLinks stops with an error.  n even, at most 64. */
+void qudaAmdMultigridGetCoarseSiteLinks(void *mg_instance, int level, int which, float *h_out);
+int qudaAmdMultigridCoarseApply(void *mg_instance, int level, int which, int mmask, int parity, float *h_out, const float *h_in);
+int qudaAmdMultigridCoarsePC(void *mg_instance, int level, int impl, int op, int parity, int nrhs, float *h_out, const float *h_in);
+void qudaAmdCoarseInvertSites(int n, int nsites, const float *h_X, float *h_Xinv, float *h_hat, const float *h_H, int *fail);
 /* The operator of a COARSE level applied to nrhs (8, 16, 24 or 32) host vectors at once through the multi-right-hand-side kernel
  * on the matrix cores (v_mfma_f32_16x16x4_f32; the reference's multi-source coarse Dslash, lib/dslash_coarse.cu:294-333): the
  * vectors lie back to back in h_in / h_out, each in the layout of qudaAmdMultigridApply.  niter > 0 additionally times niter

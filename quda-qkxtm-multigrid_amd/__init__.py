@@ -134,6 +134,7 @@ EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLo
                  "qudaAmdBlockFieldCreate", "qudaAmdBlockFieldDestroy", "qudaAmdBlockFieldLoad", "qudaAmdBlockFieldSave", "qudaAmdBlockBlasApply",
                  "qudaAmdBlockMrUpdate", "qudaAmdBlockPack", "qudaAmdBlockUnpack", "qudaAmdBlockPackParity", "qudaAmdBlockUnpackParity",
                  "qudaAmdBlockGhostPanels", "qudaAmdBlockFineApply",
+                 "qudaAmdMultigridGetCoarseSiteLinks", "qudaAmdMultigridCoarseApply", "qudaAmdMultigridCoarsePC", "qudaAmdCoarseInvertSites",
                  "qudaAmdFermionOprodForce", "qudaAmdComputeTMForce", "qudaAmdFermForceLastKernelSecs"]
 
 _lib = None
@@ -306,6 +307,14 @@ def lib():
         L.qudaAmdMultigridGetCoarseLinks.argtypes = [_p, _i, _p, _p]
         L.qudaAmdMultigridApply.argtypes = [_p, _i, _i, _p, _p]
         L.qudaAmdMultigridApplyTransfer.argtypes = [_p, _i, _i, _i, _p, _p]
+        L.qudaAmdMultigridGetCoarseSiteLinks.argtypes = [_p, _i, _i, _p]
+        L.qudaAmdMultigridGetCoarseSiteLinks.restype = None
+        L.qudaAmdMultigridCoarseApply.argtypes = [_p, _i, _i, _i, _i, _p, _p]
+        L.qudaAmdMultigridCoarseApply.restype = _i
+        L.qudaAmdMultigridCoarsePC.argtypes = [_p, _i, _i, _i, _i, _i, _p, _p]
+        L.qudaAmdMultigridCoarsePC.restype = _i
+        L.qudaAmdCoarseInvertSites.argtypes = [_i, _i, _p, _p, _p, _p, C.POINTER(_i)]
+        L.qudaAmdCoarseInvertSites.restype = None
         L.qudaAmdMultigridSetFused.argtypes = [_i]
         L.qudaAmdMultigridSetFused.restype = None
         L.qudaAmdMultigridFusedStats.argtypes = [_p, _i, _p]
@@ -1341,6 +1350,19 @@ class Dirac:
             self.h = None
 
 
+def coarse_invert_sites(X, H=None):
+    """coarse_invert_kernel / coarse_hat_kernel on the caller's matrices (qudaAmdCoarseInvertSites): X (sites, n, n), H (sites, 8, n, n) or None;
+    returns (Xinv, Xinv H_d or None, the kernel's singularity flag)"""
+    X = np.ascontiguousarray(X, dtype=np.complex64)
+    ns, n = X.shape[0], X.shape[1]
+    H = None if H is None else np.ascontiguousarray(H, dtype=np.complex64).reshape(ns, 8, n, n)
+    Xinv = np.zeros_like(X)
+    hat = None if H is None else np.zeros_like(H)
+    fail = _i(-1)
+    lib().qudaAmdCoarseInvertSites(int(n), int(ns), _vp(X), _vp(Xinv), _vp(hat), _vp(H), C.byref(fail))
+    return Xinv, hat, int(fail.value)
+
+
 def multigrid_param(ip, n_level=2, geo_block=(4, 4, 4, 4), n_vec=24, nu_pre=2, nu_post=2, cycle=QUDA_MG_CYCLE_RECURSIVE, smoother_tol=0.25,
                     setup_maxiter=500, setup_tol=5e-6, generate_all_levels=True, omega=0.85, smoother_pc=False, coarse_matpc=False):
     """QudaMultigridParam filled the way the reference harness does (tests/multigrid_invert_test.cpp:195-290), with the
@@ -1481,6 +1503,53 @@ class Multigrid:
         out = np.zeros(((8 if code >= 5 else n),) + (coarse_shape if restrict else fine_shape), dtype=np.complex64)
         lib().qudaAmdMultigridApplyTransfer(self.h, int(level), code, int(parity), _vp(out), _vp(h_in))
         return out[0] if n == 1 else out
+
+    # ---- the even-odd preconditioned coarse operator piece by piece (quda_amd_ext.h) ----
+    SITE_LINKS = {"links": 0, "hat": 1, "links16": 2, "hat16": 3}
+    PC_OPS = {"M": 0, "prepare": 1, "reconstruct": 2}
+
+    def _coarse_shape(self, level):
+        i = self.level_info(level)
+        return int(np.prod(i["Xc"])), 2, i["Nvec"]
+
+    def coarse_site_links(self, level, which="links"):
+        """(sites, 9, n, n) complex64: the matrices every site of level + 1 multiplies with (m = 2 mu forward, 2 mu + 1 backward, 8 local);
+        'links', 'hat' (Xinv H_d, 8 = Xinv), 'links16' / 'hat16': the fp16 mirrors widened"""
+        Vc, _, nvec = self._coarse_shape(level)
+        out = np.zeros((Vc, 9, 2 * nvec, 2 * nvec), dtype=np.complex64)
+        lib().qudaAmdMultigridGetCoarseSiteLinks(self.h, int(level), self.SITE_LINKS[which], _vp(out))
+        return out
+
+    def coarse_apply(self, level, which, mmask, h_in, parity=-1):
+        """applyCoarse of level + 1 with 'links' or 'hat' and matrix mask mmask; parity 0 / 1: h_in and the result are parity fields (h_in the
+        half the call reads: the other parity for hops, the same for mmask == 1 << 8)"""
+        Vc, ns, nvec = self._coarse_shape(level)
+        shape = (Vc if parity < 0 else Vc // 2, ns, nvec)
+        h_in = np.ascontiguousarray(h_in, dtype=np.complex64).reshape(shape)
+        out = np.zeros(shape, dtype=np.complex64)
+        changed = lib().qudaAmdMultigridCoarseApply(self.h, int(level), self.SITE_LINKS[which], int(mmask), int(parity), _vp(out), _vp(h_in))
+        if changed:
+            raise RuntimeError("the coarse operator changed %d words of its input field" % changed)
+        return out
+
+    def coarse_pc(self, level, impl, op, matpc, x=None, b=None):
+        """one Schur piece of the even-odd preconditioned operator of level + 1 with matpc parity `matpc`: op 'M' (x: parity fields), 'prepare'
+        (b: full sources), 'reconstruct' (x: the solved parity, b: full sources).  impl 0: DiracCoarsePC on one vector; impl 1: the block-field
+        routines on 8 / 16 / 24 vectors (leading axis).  Returns (full fields, nonzero words found where the block cycle relies on zeros)"""
+        Vc, ns, nvec = self._coarse_shape(level)
+        code = self.PC_OPS[op]
+        lead = x if x is not None else b
+        single = np.ndim(lead) == 3
+        nrhs = 1 if single else int(np.shape(lead)[0])
+        parts = []
+        if code != 1:
+            parts.append(np.ascontiguousarray(x, dtype=np.complex64).reshape(nrhs, Vc // 2, ns, nvec).reshape(-1))
+        if code != 0:
+            parts.append(np.ascontiguousarray(b, dtype=np.complex64).reshape(nrhs, Vc, ns, nvec).reshape(-1))
+        h_in = np.ascontiguousarray(np.concatenate(parts))
+        out = np.zeros((nrhs, Vc, ns, nvec), dtype=np.complex64)
+        leaked = lib().qudaAmdMultigridCoarsePC(self.h, int(level), int(impl), code, int(matpc), nrhs, _vp(out), _vp(h_in))
+        return (out[0] if single else out), int(leaked)
 
     def fused_stats(self, level):
         """None if `level` does not run its cycle as one persistent kernel (coarse_cycle.h), else the last launch's counters"""

@@ -95,8 +95,10 @@ class BlockCoarseCycle {
   void xmy(const BlockField &x, BlockField &yv) { blockblas::xmy(x, yv); }
 
   // out_p = in_p - Yhat_pq Yhat_qp in_p   (in: other parity zero; out: other parity zero)   reference DiracCoarsePC::M, lib/dirac_coarse.cpp:332-350
-  // (the two hops are computed on the output parity only: l.t is written on parity q alone, its other half stays zero from its creation)
+  // (the two hops are computed on the output parity only: l.t is written on parity q alone; its other half, which the second application multiplies
+  // with Xinv, is cleared here and not trusted to have stayed zero since its creation)
   void matpc(BlockLevel &l, BlockField &out, BlockField &in) {
+    zeroParity(*l.t, l.p);
     apply(*l.t, in, *l.H, 1 - l.p);
     apply(out, *l.t, *l.H, l.p);
     zeroParity(out, 1 - l.p);
@@ -311,6 +313,47 @@ static BlockCoarseCycle *blockCoarseCreate(MG &top, int nb, const MGParam *paren
     }
   }
   return bc;
+}
+
+// One Schur piece of the cycle above on host-supplied fields (block.h; qudaAmdMultigridCoarsePC impl 1): a one-level BlockCoarseCycle on the links
+// Y / H with matpc parity p, every work field preloaded with nonzero words on both parities (the input of matpc keeps its contract: other parity
+// zero).  Returns the number of nonzero words found afterwards in the half of l.t that the second application of matpc multiplies with Xinv.
+int blockCoarseSchurPiece(const CoarseGauge &Y, const CoarseGauge &H, int p, int op, int nrhs, const std::vector<ColorSpinorField *> &out,
+                          const std::vector<ColorSpinorField *> &in, const std::vector<ColorSpinorField *> &b) {
+  if (p < 0 || p > 1 || op < 0 || op > 2) errorQuda("Schur piece: matpc parity %d, op %d", p, op);
+  if (!blockCoarseSupported(Y, nrhs)) errorQuda("block coarse operator not available for n = %d, nrhs = %d", Y.n, nrhs);
+  BlockCoarseCycle bc;
+  bc.nl = 1; bc.nb = bc.nReal = nrhs;
+  bc.L.resize(1);
+  BlockLevel &l = bc.L[0];
+  l.Y = &Y; l.H = &H; l.p = p;
+  const int nGhost = blockGhost(Y.Xc, false).nGhost;
+  for (BlockField **f : {&l.b, &l.x, &l.bt, &l.r, &l.Ar, &l.t, &l.w1, &l.w2}) { *f = new BlockField(Y.nSites, Y.n, nrhs, nGhost); blockblas::zero(**f); }
+  const size_t half = (size_t)l.t->Vh * l.t->ncomp * l.t->nrhs;
+  auto dirty = [&](BlockField &f, int par) { HIP_CHECK(hipMemsetAsync(f.v + (size_t)par * half, 0x3f, half * sizeof(float2), computeStream())); };   // 0x3f3f3f3f = 0.747
+  for (BlockField *f : {l.bt, l.Ar, l.t, l.w1, l.w2}) { dirty(*f, 0); dirty(*f, 1); }
+  if (op == 0) {          // Mhat: in (parity p, the other half zero) -> out, with MR's operands
+    blockPack(*l.r, in);
+    BlockCoarseCycle::zeroParity(*l.r, 1 - p);
+    bc.matpc(l, *l.Ar, *l.r);
+    blockUnpack(out, *l.Ar);
+  } else if (op == 1) {   // b -> bt
+    blockPack(*l.b, b);
+    bc.prepare(l);
+    blockUnpack(out, *l.bt);
+  } else {                // x_p, b -> x
+    blockPack(*l.b, b);
+    blockPack(*l.x, in);
+    dirty(*l.x, 1 - p);
+    bc.reconstruct(l);
+    blockUnpack(out, *l.x);
+  }
+  std::vector<float2> th(half);
+  HIP_CHECK(hipMemcpyAsync(th.data(), l.t->v + (size_t)p * half, half * sizeof(float2), hipMemcpyDeviceToHost, computeStream()));
+  HIP_CHECK(hipStreamSynchronize(computeStream()));   // also: the work fields return to the pool at the end of this scope
+  int nonzero = 0;
+  if (op == 0) for (const float2 &w : th) nonzero += (w.x != 0.f) + (w.y != 0.f);   // prepare and reconstruct do not use l.t
+  return nonzero;
 }
 
 // ================================================================================================

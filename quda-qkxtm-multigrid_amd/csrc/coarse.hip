@@ -758,23 +758,31 @@ __global__ void __launch_bounds__(256) coarse_hat_kernel(float *hat, const float
   }
 }
 
-const CoarseGauge &DiracCoarse::HatLinks() const {
-  if (hat) return *hat;
-  const int n = links->n;
-  hat = new CoarseGauge(links->Xc, n);
-  ownHat = true;
+// hat = the preconditioned links of `links`: slot 8 = X^-1 (coarse_invert_kernel), slots 0..7 = X^-1 H_d (coarse_hat_kernel).  Returns the
+// kernel's flag: 1 if a pivot column of some site was identically zero (hat is then meaningless there)
+int coarseInvertHat(CoarseGauge &hat, const CoarseGauge &links) {
+  const int n = links.n;
+  if (hat.n != n || hat.nSites != links.nSites) errorQuda("preconditioned links (%d sites, n = %d) do not match the links (%d sites, n = %d)", hat.nSites, hat.n, links.nSites, n);
+  if (n < 2 || n > 64 || (n & 1)) errorQuda("batched inverse: n = %d (even, at most 64: [X | 1] of a site is held in LDS)", n);
   int *d_fail = nullptr, h_fail = 0;
   HIP_CHECK(qaMalloc((void **)&d_fail, sizeof(int)));
   HIP_CHECK(hipMemsetAsync(d_fail, 0, sizeof(int), computeStream()));
   HIP_CHECK(hipFuncSetAttribute((const void *)coarse_invert_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
   HIP_CHECK(hipFuncSetAttribute((const void *)coarse_hat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-  hipLaunchKernelGGL(coarse_invert_kernel, dim3(links->nSites), dim3(256), (size_t)n * 2 * n * sizeof(float2), computeStream(), hat->data, links->data, n, d_fail);
-  hipLaunchKernelGGL(coarse_hat_kernel, dim3(links->nSites * 8), dim3(256), (size_t)2 * n * n * sizeof(float2), computeStream(), hat->data, links->data, n);
+  hipLaunchKernelGGL(coarse_invert_kernel, dim3(links.nSites), dim3(256), (size_t)n * 2 * n * sizeof(float2), computeStream(), hat.data, links.data, n, d_fail);
+  hipLaunchKernelGGL(coarse_hat_kernel, dim3(links.nSites * 8), dim3(256), (size_t)2 * n * n * sizeof(float2), computeStream(), hat.data, links.data, n);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipMemcpyAsync(&h_fail, d_fail, sizeof(int), hipMemcpyDeviceToHost, computeStream()));
   HIP_CHECK(hipStreamSynchronize(computeStream()));
   HIP_CHECK(hipFree(d_fail));
-  if (h_fail) errorQuda("singular coarse local matrix X: cannot build the preconditioned coarse operator");
+  return h_fail;
+}
+
+const CoarseGauge &DiracCoarse::HatLinks() const {
+  if (hat) return *hat;
+  hat = new CoarseGauge(links->Xc, links->n);
+  ownHat = true;
+  if (coarseInvertHat(*hat, *links)) errorQuda("singular coarse local matrix X: cannot build the preconditioned coarse operator");
   return *hat;
 }
 

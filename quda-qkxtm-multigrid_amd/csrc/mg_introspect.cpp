@@ -4,6 +4,8 @@
 // Host layouts are the reference's CPU orders: vectors site-major (parity*Vh + x_cb, spin, colour, re/im) fp32
 // (QUDA_SPACE_SPIN_COLOR_FIELD_ORDER, DeGrand-Rossi basis on level 0); V as (site, spin, colour, vector);
 // coarse links as QDP-ordered Y[dim 0-3 backward | 4-7 forward][site][row][col] with the operator's -kappa folded in.
+// At the end: the even-odd preconditioned coarse operator piece by piece (qudaAmdMultigridGetCoarseSiteLinks, qudaAmdMultigridCoarseApply,
+// qudaAmdMultigridCoarsePC, qudaAmdCoarseInvertSites), which the library itself reaches only from inside a solve.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -345,6 +347,165 @@ double qudaAmdMultigridTimeApply(void *mg_instance, int level, int niter) {
   HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
   HIP_CHECK(hipEventDestroy(e0)); HIP_CHECK(hipEventDestroy(e1));
   return 1e-3 * ms / niter;
+}
+
+}
+
+// ---- the even-odd preconditioned coarse operator piece by piece (quda_amd_ext.h; tests/test_coarse_pc_gpu.py) ----
+// device layout of a link set (coarse.h): [site][matrix][column pair][row] float4 <-> host [site][matrix][row][col] complex
+static size_t linkWord(int n, size_t A, int m, int r, int c) { return ((((size_t)A * 9 + m) * (n / 2) + c / 2) * n + r) * 4 + (c & 1) * 2; }
+
+static const DiracCoarse *coarseOperatorOf(void *mg_instance, int level) {
+  const DiracCoarse *D = levelOf(mg_instance, level)->getCoarseDirac();
+  if (!D) errorQuda("level %d has no coarse operator below it", level);
+  return D;
+}
+// host vectors travel as full fields; a parity half is the contiguous range [parity * half, (parity + 1) * half) of one
+static void loadFull(ColorSpinorField &d, const float *h) { d = hostView(d, const_cast<float *>(h)); }
+static void saveFull(float *h, const ColorSpinorField &d) { ColorSpinorField v = hostView(d, h); v = d; }
+static void loadHalf(ColorSpinorField &d, const float *h_half, int parity, size_t half) {
+  std::vector<float> full(2 * half, 0.f);
+  memcpy(full.data() + parity * half, h_half, half * sizeof(float));
+  loadFull(d, full.data());
+}
+static ColorSpinorField &parityOf(ColorSpinorField &f, int parity) { return parity ? f.Odd() : f.Even(); }
+
+extern "C" {
+
+void qudaAmdMultigridGetCoarseSiteLinks(void *mg_instance, int level, int which, float *h_out) {
+  const DiracCoarse *D = coarseOperatorOf(mg_instance, level);
+  if (which < 0 || which > 3) errorQuda("link set %d (0 links, 1 preconditioned links, 2 / 3 their fp16 mirrors)", which);
+  const CoarseGauge &G = (which & 1) ? D->HatLinks() : D->Links();
+  const int n = G.n;
+  const size_t words = G.bytes / sizeof(float);
+  std::vector<float> g(words);
+  HIP_CHECK(hipStreamSynchronize(computeStream()));
+  if (which < 2) {
+    HIP_CHECK(hipMemcpy(g.data(), G.data, G.bytes, hipMemcpyDeviceToHost));
+  } else {
+    if (!G.data_h) errorQuda("the %s have no fp16 mirror (qudaAmdMultigridSetHalfStorage makes it)", (which & 1) ? "preconditioned links" : "links");
+    std::vector<_Float16> h(words);
+    HIP_CHECK(hipMemcpy(h.data(), G.data_h, words * sizeof(_Float16), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < words; i++) g[i] = (float)h[i];
+  }
+  for (size_t A = 0; A < (size_t)G.nSites; A++)
+    for (int m = 0; m < 9; m++)
+      for (int r = 0; r < n; r++)
+        for (int c = 0; c < n; c++) {
+          const float *w = &g[linkWord(n, A, m, r, c)];
+          float *o = h_out + ((((size_t)A * 9 + m) * n + r) * n + c) * 2;
+          o[0] = w[0]; o[1] = w[1];
+        }
+}
+
+int qudaAmdMultigridCoarseApply(void *mg_instance, int level, int which, int mmask, int parity, float *h_out, const float *h_in) {
+  const DiracCoarse *D = coarseOperatorOf(mg_instance, level);
+  const Transfer *T = levelOf(mg_instance, level)->getTransfer();
+  if (which < 0 || which > 1) errorQuda("link set %d (0 links, 1 preconditioned links)", which);
+  if (parity < -1 || parity > 1) errorQuda("parity %d (-1: full fields, 0 / 1)", parity);
+  if (mmask <= 0 || mmask > 0x1ff) errorQuda("matrix mask 0x%x", mmask);
+  const CoarseGauge &G = which ? D->HatLinks() : D->Links();
+  ColorSpinorField *in = T->createCoarseField(), *out = T->createCoarseField();
+  const size_t half = (size_t)G.nSites / 2 * G.n * 2;
+  const int inPar = parity < 0 ? -1 : (mmask == (1 << 8) ? parity : 1 - parity);   // the local term reads its own parity, hops the other one
+  std::vector<float> full(2 * half);
+  if (parity < 0) {
+    loadFull(*in, h_in);
+    applyCoarse(*out, *in, G, mmask, -1);
+    saveFull(h_out, *out);
+  } else {
+    loadHalf(*in, h_in, inPar, half);
+    applyCoarse(parityOf(*out, parity), parityOf(*in, inPar), G, mmask, parity);
+    saveFull(full.data(), *out);
+    memcpy(h_out, full.data() + parity * half, half * sizeof(float));
+  }
+  // the input as the device holds it afterwards against what was loaded, word by word
+  saveFull(full.data(), *in);
+  int changed = 0;
+  for (size_t i = 0; i < 2 * half; i++) {
+    const bool loaded = inPar < 0 || (int)(i / half) == inPar;
+    const float was = loaded ? h_in[inPar < 0 ? i : i - inPar * half] : 0.f;
+    changed += memcmp(&was, &full[i], sizeof(float)) != 0;
+  }
+  delete in; delete out;
+  return changed;
+}
+
+int qudaAmdMultigridCoarsePC(void *mg_instance, int level, int impl, int op, int parity, int nrhs, float *h_out, const float *h_in) {
+  MG *fineLevel = levelOf(mg_instance, level);
+  const DiracCoarse *D = coarseOperatorOf(mg_instance, level);
+  const Transfer *T = fineLevel->getTransfer();
+  if (impl < 0 || impl > 1 || op < 0 || op > 2 || parity < 0 || parity > 1) errorQuda("impl %d (0, 1), op %d (0..2), matpc parity %d (0, 1)", impl, op, parity);
+  if (impl == 0 && nrhs != 1) errorQuda("DiracCoarsePC works on one vector, not %d", nrhs);
+  const size_t half = (size_t)D->Links().nSites / 2 * D->Links().n * 2, full = 2 * half;
+  std::vector<ColorSpinorField *> x(nrhs), b(nrhs), out(nrhs);
+  for (int i = 0; i < nrhs; i++) {
+    x[i] = T->createCoarseField(); b[i] = T->createCoarseField(); out[i] = T->createCoarseField();
+    if (op == 0) loadHalf(*x[i], h_in + i * half, parity, half);
+    if (op == 1) loadFull(*b[i], h_in + i * full);
+    if (op == 2) { loadHalf(*x[i], h_in + i * half, parity, half); loadFull(*b[i], h_in + nrhs * half + i * full); }
+  }
+  int leaked = 0;
+  if (impl == 1) {
+    leaked = blockCoarseSchurPiece(D->Links(), D->HatLinks(), parity, op, nrhs, out, x, b);
+  } else {
+    // the level's own smoother operator where it is preconditioned on this parity, else one made for the call that shares the links
+    const QudaMatPCType want = parity ? QUDA_MATPC_ODD_ODD : QUDA_MATPC_EVEN_EVEN;
+    const MG *coarseLevel = fineLevel->getCoarse();
+    const DiracCoarsePC *pc = coarseLevel ? dynamic_cast<const DiracCoarsePC *>(coarseLevel->params().matSmooth.Expose()) : nullptr;
+    DiracCoarsePC *mine = nullptr;
+    if (!pc || pc->getMatPCType() != want) {
+      DiracParam dp;
+      dp.type = QUDA_COARSEPC_DIRAC;
+      dp.kappa = 1.0;
+      dp.dagger = QUDA_DAG_NO;
+      dp.matpcType = want;
+      pc = mine = new DiracCoarsePC(*D, dp);
+    }
+    if (op == 0) {
+      pc->M(parityOf(*out[0], parity), parityOf(*x[0], parity));
+    } else if (op == 1) {
+      ColorSpinorField *src = nullptr, *sol = nullptr;
+      pc->prepare(src, sol, *x[0], *b[0], QUDA_MAT_SOLUTION);
+      if (sol != &parityOf(*x[0], parity)) errorQuda("prepare: the solution does not live on parity %d", parity);
+      blas::copy(parityOf(*out[0], parity), *src);
+    } else {
+      pc->reconstruct(*x[0], *b[0], QUDA_MAT_SOLUTION);
+      blas::copy(*out[0], *x[0]);
+    }
+    HIP_CHECK(hipStreamSynchronize(computeStream()));
+    delete mine;
+  }
+  for (int i = 0; i < nrhs; i++) {
+    saveFull(h_out + i * full, *out[i]);
+    delete x[i]; delete b[i]; delete out[i];
+  }
+  return leaked;
+}
+
+void qudaAmdCoarseInvertSites(int n, int nsites, const float *h_X, float *h_Xinv, float *h_hat, const float *h_H, int *fail) {
+  if (n < 2 || n > 64 || (n & 1) || nsites < 1) errorQuda("batched inverse of %d matrices of order %d (even, at most 64)", nsites, n);
+  const int xc[4] = {nsites, 1, 1, 1};
+  CoarseGauge G(xc, n), hat(xc, n);
+  std::vector<float> g(G.bytes / sizeof(float), 0.f);
+  for (size_t A = 0; A < (size_t)nsites; A++)
+    for (int m = 0; m < 9; m++) {
+      const float *src = m == 8 ? h_X + A * n * n * 2 : (h_H ? h_H + (A * 8 + m) * n * n * 2 : nullptr);
+      if (!src) continue;
+      for (int r = 0; r < n; r++)
+        for (int c = 0; c < n; c++) { float *w = &g[linkWord(n, A, m, r, c)]; w[0] = src[((size_t)r * n + c) * 2]; w[1] = src[((size_t)r * n + c) * 2 + 1]; }
+    }
+  HIP_CHECK(hipMemcpyAsync(G.data, g.data(), G.bytes, hipMemcpyHostToDevice, computeStream()));
+  const int f = coarseInvertHat(hat, G);
+  if (fail) *fail = f;
+  HIP_CHECK(hipMemcpy(g.data(), hat.data, hat.bytes, hipMemcpyDeviceToHost));
+  for (size_t A = 0; A < (size_t)nsites; A++)
+    for (int m = 0; m < 9; m++) {
+      float *dst = m == 8 ? h_Xinv + A * n * n * 2 : (h_hat ? h_hat + (A * 8 + m) * n * n * 2 : nullptr);
+      if (!dst) continue;
+      for (int r = 0; r < n; r++)
+        for (int c = 0; c < n; c++) { const float *w = &g[linkWord(n, A, m, r, c)]; dst[((size_t)r * n + c) * 2] = w[0]; dst[((size_t)r * n + c) * 2 + 1] = w[1]; }
+    }
 }
 
 }
