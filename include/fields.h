@@ -174,6 +174,7 @@ class CloverField {
   bool twisted;
   double mu2;
   double trlog[2];
+  double coeff;      // the c of computeFromGauge; NAN: unknown (loaded from a host field)
 
   CloverField(const LatticeGeom &g, QudaPrecision prec);
   ~CloverField();
@@ -182,8 +183,10 @@ class CloverField {
   // computeFmunu + computeClover with c = clover_coeff); fp64 arithmetic, stored in this field's precision
   void computeFromGauge(const GaugeField &U, double coeff);
   void savePacked(void *h_clover, QudaPrecision cpu_prec) const;
-  // compute cloverInv = (A^2 + mu2)^-1 (mu2 = 0: plain inverse) on device; reference lib/clover_invert.cu:56-85
-  void computeInverse(double mu2);
+  // compute cloverInv = (A^2 + mu2)^-1 on device (reference lib/clover_invert.cu:56-85); the plain inverse A^-1 if mu2 = 0 and the
+  // field does not belong to a twisted operator (twisted clover at mu = 0 keeps the squared form A^-2 that its site kernels multiply
+  // (A -+ i a g5) v with)
+  void computeInverse(double mu2, bool twisted = false);
   void savePackedInverse(void *h_inv, QudaPrecision cpu_prec) const;
   const void *A(int parity) const { return (const char *)clover + (size_t)parity * parity_bytes; }
   const void *Ainv(int parity) const { return (const char *)cloverInv + (size_t)parity * parity_bytes; }
@@ -251,5 +254,34 @@ void fermionOprodForce(MomField &mom, const GaugeField &U, const std::vector<Col
 void tmForce(MomField &mom, const GaugeField &U, double dt, const std::vector<ColorSpinorField *> &x, const std::vector<double> &coeff, QudaInvertParam *inv);
 // seconds the last fermionOprodForce spent in its kernel launches (device events), for tools/ferm_force_timing.py
 double fermForceLastKernelSecs();
+// the kernels of clover_force.hip count towards the same figure: reset starts a new call
+void fermForceAddKernelSecs(double secs, bool reset);
+
+// ---- twisted-clover force (clover_force.hip; DESIGN section 3 "Twisted-clover force") ----
+// Six 3x3 colour matrices per site, one per plane f = mu (mu - 1) / 2 + nu, nu < mu (F10, F20, F21, F30, F31, F32): six fp64 matrix
+// fields in one allocation.  Host order [site (even, odd)][f][3][3][re, im]
+class TensorField {
+ public:
+  LatticeGeom geom;
+  size_t bytes;
+  double *data;
+  explicit TensorField(const LatticeGeom &g);   // zeroed
+  ~TensorField();
+  TensorField(const TensorField &) = delete;
+  TensorField &operator=(const TensorField &) = delete;
+  void load(const double *h_tensor);
+  void save(double *h_tensor) const;
+};
+// One (X, Y) pair of the sigma outer product: fp64 parity fields (even, odd) of one flavour and the complex coefficient of each parity
+struct SigmaOprodPair { const ColorSpinorField *x[2], *y[2]; double cr[2], ci[2]; };
+// T_f(x) (+)= sum_i c_i[parity(x)] S_f[X_i, Y_i](x), S_f[X, Y]_ba = sum_ss' (sigma_f)_ss' X_s'b conj(Y_sa).  Site-local: any partition mask
+void cloverSigmaOprod(TensorField &T, const std::vector<SigmaOprodPair> &pairs, bool accumulate);
+// T_f(x) (+)= c[parity(x)] sum_ss' (sigma_f)_ss' B(x)_(s'b)(sa), B = A (A^2 + mu2)^-1 from the fp64 blocks of a clover field and its
+// resident (twisted) inverse; c = cr + i ci per parity.  Site-local: any partition mask
+void cloverSigmaTrace(TensorField &T, const CloverField &clover, const double cr[2], const double ci[2], bool accumulate);
+// mom <- mom + coeff G[T], G[T] the force of L_T(U) = sum_x sum_f Re tr(T_f(x) F_f(x; U)).  Unpartitioned lattices only
+void cloverDerivativeForce(MomField &mom, const GaugeField &U, const TensorField &T, double coeff);
+// stops with a message that names the partition if any direction is partitioned
+void checkCloverDerivativeUnpartitioned(const char *fn);
 
 }  // namespace quda

@@ -302,12 +302,13 @@ double qudaAmdQCharge(double *h_density, int lexicographic, int which);
  * device by the function the stout kernel calls (Cayley-Hamilton form). */
 void qudaAmdSu3ExpIQ(int n, const double *q, double *out);
 /* Fermion force of molecular dynamics for the actions this library solves (Wilson, degenerate twisted mass, the non-degenerate
- * doublet); the reference's only Wilson-type fermion force, computeCloverForceQuda, belongs to the Wilson-clover action.  Conventions
+ * doublet, twisted clover); the reference's only Wilson-type fermion force, computeCloverForceQuda, belongs to the Wilson-clover action
+ * with the MILC / Chroma gamma5 conventions and is not provided under that name.  Conventions
  * of the gauge force: U' = A U, momenta as ten reals per link [site (even, odd)][mu][10], TA(M) = (M - M^dag)/2 - tr(M - M^dag)/6.
  * Both calls work on the resident links (an error if there are none), take fp64 host momenta under gauge_param with
  * QUDA_QDP_GAUGE_ORDER, honour overwrite_mom, use_resident_mom, make_resident_mom and return_result_mom as computeGaugeForceQuda
- * does, and run under any partition.  Refused: twisted clover (the derivative of the clover term is not part of this), cuda_prec
- * other than fp64, solve_type other than QUDA_NORMOP_PC_SOLVE / QUDA_DIRECT_PC_SOLVE.
+ * does, and run under any partition (twisted clover in qudaAmdComputeTMForce: unpartitioned lattices only, see below).  Refused:
+ * cuda_prec other than fp64, solve_type other than QUDA_NORMOP_PC_SOLVE / QUDA_DIRECT_PC_SOLVE, the doublet with a clover term.
  *
  * qudaAmdFermionOprodForce: mom_mu(x) <- TA(mom_mu(x) - sum_i coeff[i] U_mu(x) O_mu[X_i, Y_i](x)) with
  *   O_mu[X, Y](x) = tr_spin[(1 - g_mu) X(x + mu) Y^dag(x) + (1 + g_mu) Y(x + mu) X^dag(x)]
@@ -317,11 +318,51 @@ void qudaAmdSu3ExpIQ(int n, const double *q, double *out);
  * qudaAmdComputeTMForce: mom <- mom + dt sum_i coeff[i] F[x_i], F the force of phi^dag (Mh^dag Mh)^-1 phi, for the single-parity
  * solutions h_x[i] = (Mh^dag Mh + shift_i)^-1 phi that a QUDA_NORMOP_PC_SOLVE returns under inv_param (the shifts drop out of the force).
  * Mh is the even-odd operator of inv_param: dslash_type Wilson or twisted mass, twist +-1 or the doublet with epsilon, the four
- * matpc_type (Wilson: the two symmetric ones), every mass_normalization.  X_i and Y_i are built on the device. */
+ * matpc_type (Wilson: the two symmetric ones), every mass_normalization.  X_i and Y_i are built on the device.
+ * With dslash_type QUDA_TWISTED_CLOVER_DSLASH (twist +-1, any mu including 0: Wilson clover) Mh is the twisted-clover operator on the
+ * resident clover term and the call adds the derivative of that term as well: one sigma outer product and one derivative launch (below)
+ * after the hop kernel.  The clover term must have been built from the resident links by loadCloverQuda(NULL, NULL, inv_param) in fp64
+ * (clover_cuda_prec) with the kappa, mu and clover_coeff of inv_param; the caller rebuilds it after every link update.  Refused
+ * before any device work: no resident clover term, one loaded from a host field (its coefficient is unknown), a clover_coeff, kappa or
+ * mu that differ from those it was built with, a clover term held in another precision than fp64, any partitioned direction. */
 void qudaAmdFermionOprodForce(void *mom, void **h_x, void **h_y, double *coeff, int nvector, QudaGaugeParam *gauge_param, QudaInvertParam *inv_param);
 void qudaAmdComputeTMForce(void *mom, double dt, void **h_x, double *coeff, int nvector, QudaGaugeParam *gauge_param, QudaInvertParam *inv_param);
-/* seconds the kernels of the last of these calls took on the device (tools/ferm_force_timing.py) */
+/* seconds the kernels of the last of these calls, or of the clover-force calls below, took on the device (tools/ferm_force_timing.py,
+ * tools/clover_force_timing.py) */
 double qudaAmdFermForceLastKernelSecs(void);
+/* The clover part of the twisted-clover force and the force of the clover determinant.  Conventions as above; in addition
+ * F_mu_nu = (Q_mu_nu - Q_mu_nu^dag)/8 of the four clover leaves, no trace removed, plane index f = mu (mu - 1)/2 + nu for nu < mu (F10,
+ * F20, F21, F30, F31, F32); the clover term is A = 1 + i c sum_f sigma_f (x) F_f with c = clover_coeff and sigma_mu_nu = (i/2)[g_mu, g_nu];
+ * a = 2 kappa mu twist_flavor and R = A + i a g5, so that R^dag R = A^2 + a^2, whose inverse is the resident clover inverse.  A tensor
+ * field holds six 3x3 complex colour matrices per site: h_tensor[site (even, odd)][f][3][3][re, im], 108 doubles per site.  "The force
+ * F[S] of S" is what a call adds to the momentum per unit dt: d/d eps S(exp(eps Theta) U) = sum_links Re tr(Theta_mu(x) F_mu(x)) for every
+ * traceless anti-Hermitian Theta.
+ *
+ * qudaAmdCloverSigmaOprod: h_tensor_f(x) = sum_i coeff[2 i + parity(x)] S_f[X_i, Y_i](x) with
+ *   S_f[X, Y](x)_ba = sum_ss' (sigma_f)_ss' X(x)_s'b conj(Y(x)_sa),        so that Y^dag(x) dA(x) X(x) = i c sum_f tr(dF_f(x) S_f(x)),
+ * for nvector pairs of full one-flavour host fields as MatQuda takes them under inv_param.  Overwrites h_tensor.  Site-local: any
+ * partition.  Refused: cuda_prec other than fp64, the doublet, no resident links (they fix the lattice).
+ *
+ * qudaAmdCloverSigmaTrace: h_tensor_f(x) = coeff[parity(x)] sum_ss' (sigma_f)_ss' B(x)_(s'b)(sa) with B = A (A^2 + a^2)^-1 from the
+ * resident fp64 clover term and its inverse, a from the kappa, mu and twist_flavor of inv_param (which must be those the inverse was
+ * computed with).  d log det(A^2 + a^2) = 2 i c sum_f tr(dF_f [this with coeff 1]).  Overwrites h_tensor.  Site-local: any partition.
+ * Refused: no resident clover term, one not held in fp64, kappa and mu that differ from those of the resident inverse.
+ *
+ * qudaAmdCloverDerivativeForce: mom <- mom + coeff G[T] for the tensor field T = h_tensor (general complex; only (T - T^dag)/2 counts),
+ * G[T] the force of L_T(U) = sum_x sum_f Re tr(T_f(x) F_f(x; U)) on the resident links, in every precision and reconstruction the gauge
+ * force takes, fp64 arithmetic.  Momentum flags as above.  Unpartitioned lattices only: refused before any device work, with a message
+ * that names the partitioned directions.
+ *
+ * qudaAmdCloverLogDetForce: mom <- mom + dt (coeff_even F[L_even] + coeff_odd F[L_odd]) with L_p = sum over the sites of parity p of
+ * log det(A(x)^2 + a^2), the quantity loadCloverQuda reports in trlogA[p].  Even-odd preconditioning leaves the determinant of the
+ * eliminated parity outside the pseudofermion action: a pair of flavours +-mu under asymmetric preconditioning has the weight
+ * det(A^2 + a^2) of that parity, S = -L_p, so the caller passes -1 for the parity that was eliminated (the odd one for the EVEN_EVEN
+ * types) and 0 for the other; symmetric preconditioning divides by R on both parities, -1 for both.  Requirements and refusals on the
+ * clover term and the partition as for twisted clover in qudaAmdComputeTMForce. */
+void qudaAmdCloverSigmaOprod(double *h_tensor, void **h_x, void **h_y, double *coeff /* [nvector][2]: even, odd */, int nvector, QudaInvertParam *inv_param);
+void qudaAmdCloverSigmaTrace(double *h_tensor, double coeff_even, double coeff_odd, QudaInvertParam *inv_param);
+void qudaAmdCloverDerivativeForce(void *mom, double *h_tensor, double coeff, QudaGaugeParam *gauge_param);
+void qudaAmdCloverLogDetForce(void *mom, double dt, double coeff_even, double coeff_odd, QudaGaugeParam *gauge_param, QudaInvertParam *inv_param);
 /* h_out = smear^nsmear(h_in) (QKXTM_Vector_Kepler::gaussianSmearing, lib/qudaQKXTM_Vector_Kepler.cpp:386-421); the lattice is
  * that of the resident gauge field */
 void qudaAmdGaussianSmear(void *h_out, const void *h_in, void **gauge_APE, int nsmear, double alpha);

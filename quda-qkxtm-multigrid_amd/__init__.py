@@ -135,7 +135,8 @@ EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLo
                  "qudaAmdBlockMrUpdate", "qudaAmdBlockPack", "qudaAmdBlockUnpack", "qudaAmdBlockPackParity", "qudaAmdBlockUnpackParity",
                  "qudaAmdBlockGhostPanels", "qudaAmdBlockFineApply",
                  "qudaAmdMultigridGetCoarseSiteLinks", "qudaAmdMultigridCoarseApply", "qudaAmdMultigridCoarsePC", "qudaAmdCoarseInvertSites",
-                 "qudaAmdFermionOprodForce", "qudaAmdComputeTMForce", "qudaAmdFermForceLastKernelSecs"]
+                 "qudaAmdFermionOprodForce", "qudaAmdComputeTMForce", "qudaAmdFermForceLastKernelSecs",
+                 "qudaAmdCloverSigmaOprod", "qudaAmdCloverSigmaTrace", "qudaAmdCloverDerivativeForce", "qudaAmdCloverLogDetForce"]
 
 _lib = None
 
@@ -361,6 +362,14 @@ def lib():
         L.qudaAmdComputeTMForce.restype = None
         L.qudaAmdFermForceLastKernelSecs.argtypes = []
         L.qudaAmdFermForceLastKernelSecs.restype = _d
+        L.qudaAmdCloverSigmaOprod.argtypes = [C.POINTER(_d), C.POINTER(_p), C.POINTER(_p), C.POINTER(_d), _i, C.POINTER(QudaInvertParam)]
+        L.qudaAmdCloverSigmaOprod.restype = None
+        L.qudaAmdCloverSigmaTrace.argtypes = [C.POINTER(_d), _d, _d, C.POINTER(QudaInvertParam)]
+        L.qudaAmdCloverSigmaTrace.restype = None
+        L.qudaAmdCloverDerivativeForce.argtypes = [_p, C.POINTER(_d), _d, C.POINTER(QudaGaugeParam)]
+        L.qudaAmdCloverDerivativeForce.restype = None
+        L.qudaAmdCloverLogDetForce.argtypes = [_p, _d, _d, _d, C.POINTER(QudaGaugeParam), C.POINTER(QudaInvertParam)]
+        L.qudaAmdCloverLogDetForce.restype = None
         L.qudaAmdGaussianSmear.argtypes = [_p, _p, C.POINTER(_p), _i, _d]
         L.qudaAmdCalcMGPropagators.argtypes = [_p, _p, C.POINTER(_p), C.POINTER(QudaInvertParam), C.POINTER(QudaAmdSourceParam)]
         L.qudaAmdTwopMomenta.argtypes = [_i, C.POINTER(_i), _i]
@@ -927,14 +936,61 @@ def ferm_oprod_force(gp, ip, xs, ys, coeff, mom=None, overwrite=False, make_resi
 
 def tm_force(gp, ip, xs, coeff, dt, mom=None, overwrite=False, make_resident_mom=False, return_mom=True):
     """qudaAmdComputeTMForce: mom <- mom + dt sum_i coeff[i] F[xs[i]] on the resident links, F the force of phi^dag (Mh^dag Mh)^-1 phi at
-    the single-parity solutions xs[i] of a QUDA_NORMOP_PC_SOLVE under ip (Wilson, twisted mass +-1 or the doublet; any matpc type and
-    mass normalisation).  Momentum arguments as in ferm_oprod_force"""
+    the single-parity solutions xs[i] of a QUDA_NORMOP_PC_SOLVE under ip (Wilson, twisted mass +-1, the doublet, or twisted clover +-1
+    on a clover term built from the resident links with ip.clover_coeff; any matpc type and mass normalisation).  Momentum arguments
+    as in ferm_oprod_force"""
     n = len(coeff)
     if len(xs) != n:
         raise ValueError("one coefficient per solution")
     out, q = _force_mom(gp, mom, overwrite, make_resident_mom, return_mom)
     xs, px = _field_ptrs(xs)
     lib().qudaAmdComputeTMForce(_vp(out), float(dt), px, (_d * max(n, 1))(*[float(c) for c in coeff]), n, C.byref(q), C.byref(ip))
+    return out if return_mom else None
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(_d))
+
+
+def clover_sigma_oprod(ip, xs, ys, coeff, V):
+    """qudaAmdCloverSigmaOprod: T_f(x) = sum_i coeff[i][parity(x)] S_f[xs[i], ys[i]](x), S_f[X, Y]_ba = sum_ss' (sigma_f)_ss' X_s'b conj(Y_sa),
+    for full host fields as MatQuda takes them under ip on the resident lattice of V sites.  coeff: (nvector, 2), even and odd.
+    Returns the tensor field (V, 6, 3, 3, 2), even sites then odd"""
+    n = len(xs)
+    c = np.ascontiguousarray(coeff, dtype=np.float64).reshape(n, 2)
+    if len(ys) != n:
+        raise ValueError("one Y per X")
+    out = np.zeros((int(V), 6, 3, 3, 2))
+    xs, px = _field_ptrs(xs)
+    ys, py = _field_ptrs(ys)
+    lib().qudaAmdCloverSigmaOprod(_dp(out), px, py, _dp(c), n, C.byref(ip))
+    return out
+
+
+def clover_sigma_trace(ip, coeff_even, coeff_odd, V):
+    """qudaAmdCloverSigmaTrace: T_f(x) = coeff[parity(x)] sum_ss' (sigma_f)_ss' B(x)_(s'b)(sa), B = A (A^2 + a^2)^-1 of the resident fp64 clover
+    term.  Returns the tensor field (V, 6, 3, 3, 2)"""
+    out = np.zeros((int(V), 6, 3, 3, 2))
+    lib().qudaAmdCloverSigmaTrace(_dp(out), float(coeff_even), float(coeff_odd), C.byref(ip))
+    return out
+
+
+def clover_derivative_force(gp, tensor, coeff, mom=None, overwrite=False, make_resident_mom=False, return_mom=True):
+    """qudaAmdCloverDerivativeForce: mom <- mom + coeff G[T], G[T] the force of L_T(U) = sum_x sum_f Re tr(T_f(x) F_f(x; U)) on the
+    resident links, T = tensor (V, 6, 3, 3, 2).  Momentum arguments as in ferm_oprod_force"""
+    out, q = _force_mom(gp, mom, overwrite, make_resident_mom, return_mom)
+    t = np.ascontiguousarray(tensor, dtype=np.float64)
+    if t.size != out.shape[0] * 108:
+        raise ValueError("the tensor field has 108 doubles per site")
+    lib().qudaAmdCloverDerivativeForce(_vp(out), _dp(t), float(coeff), C.byref(q))
+    return out if return_mom else None
+
+
+def clover_logdet_force(gp, ip, dt, coeff_even, coeff_odd, mom=None, overwrite=False, make_resident_mom=False, return_mom=True):
+    """qudaAmdCloverLogDetForce: mom <- mom + dt (coeff_even F[L_even] + coeff_odd F[L_odd]), L_p = sum over the sites of parity p of
+    log det(A^2 + a^2) (trlogA[p] of loadCloverQuda), on a clover term built from the resident links with ip.clover_coeff"""
+    out, q = _force_mom(gp, mom, overwrite, make_resident_mom, return_mom)
+    lib().qudaAmdCloverLogDetForce(_vp(out), float(dt), float(coeff_even), float(coeff_odd), C.byref(q), C.byref(ip))
     return out if return_mom else None
 
 

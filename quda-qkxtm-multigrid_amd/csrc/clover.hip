@@ -4,6 +4,8 @@
 #include "dispatch.h"
 #include "gauge_device.h"
 
+#include <cmath>
+
 namespace quda {
 
 CloverField::CloverField(const LatticeGeom &g, QudaPrecision prec)
@@ -19,6 +21,7 @@ CloverField::CloverField(const LatticeGeom &g, QudaPrecision prec)
     HIP_CHECK(qaMalloc((void **)&invNorm, 2 * parity_norm_bytes));
   }
   trlog[0] = trlog[1] = 0;
+  coeff = NAN;
 }
 CloverField::~CloverField() {
   if (clover) (void)hipFree(clover);
@@ -61,11 +64,11 @@ __global__ void clover_save_kernel(THost *host, const char *dev, const float *no
   }
 }
 
-// (A^2 + mu2)^-1 (mu2 == 0: A^-1) per chiral block, computed in fp64 registers by Gauss-Jordan on the
+// (A^2 + mu2)^-1 (squared == 0: A^-1) per chiral block, computed in fp64 registers by Gauss-Jordan on the
 // Hermitian 6x6 (small, setup-time only; reference lib/clover_invert.cu:56-85 uses Cholesky).
 template <typename TDev>
 __global__ void clover_invert_kernel(char *inv, float *invNorm, const char *A, const float *Anorm, size_t parity_bytes, int stride, int Vh,
-                                     double mu2, double *trlog) {
+                                     double mu2, int squared, double *trlog) {
   using real = typename Store<TDev>::real;
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= 2 * Vh) return;
@@ -85,7 +88,7 @@ __global__ void clover_invert_kernel(char *inv, float *invNorm, const char *A, c
     for (int r = 0; r < 6; r++)
       for (int c = 0; c < 6; c++) {
         double re, im;
-        if (mu2 != 0.0) {
+        if (squared) {
           re = 0; im = 0;
           for (int k = 0; k < 6; k++) {
             re += M[r][k][0] * M[k][c][0] - M[r][k][1] * M[k][c][1];
@@ -249,6 +252,7 @@ void CloverField::computeFromGauge(const GaugeField &U, double coeff) {
   else forLinkType(U, [&](auto t, auto r) { launchSites(clover_from_gauge_kernel<decltype(t), decltype(r)::value>, geom.Vh, 128, stage, viewOf(U), coeff, geom.Vh); });
   forPrecision(precision, [&](auto t) { launchSites(clover_load_kernel<decltype(t), double>, geom.Vh, 256, (char *)clover, norm, parity_bytes, stride, stage, geom.Vh); });
   HIP_CHECK(hipStreamSynchronize(computeStream()));
+  this->coeff = coeff;
 }
 
 template <typename TDev, typename THost> static void cloverLoad(CloverField &c, void *dev, float *nrm, const void *host) {
@@ -266,18 +270,18 @@ void CloverField::loadPacked(const void *h_clover, const void *h_inv, QudaPrecis
       else cloverLoad<decltype(t), float>(*this, dev, nrm, host);
     });
   };
-  if (h_clover) load(clover, norm, h_clover);
+  if (h_clover) { load(clover, norm, h_clover); coeff = NAN; }
   if (h_inv) load(cloverInv, invNorm, h_inv);
 }
 
-void CloverField::computeInverse(double mu2_) {
+void CloverField::computeInverse(double mu2_, bool twisted_) {
   mu2 = mu2_;
-  twisted = mu2_ != 0.0;
+  twisted = twisted_ || mu2_ != 0.0;
   double *d_trlog = nullptr;
   HIP_CHECK(qaMalloc((void **)&d_trlog, 2 * sizeof(double)));
   HIP_CHECK(hipMemsetAsync(d_trlog, 0, 2 * sizeof(double), computeStream()));
   forPrecision(precision, [&](auto t) {
-    launchSites(clover_invert_kernel<decltype(t)>, geom.Vh, 128, (char *)cloverInv, invNorm, (const char *)clover, norm, parity_bytes, stride, geom.Vh, mu2_, d_trlog);
+    launchSites(clover_invert_kernel<decltype(t)>, geom.Vh, 128, (char *)cloverInv, invNorm, (const char *)clover, norm, parity_bytes, stride, geom.Vh, mu2_, twisted ? 1 : 0, d_trlog);
   });
   HIP_CHECK(hipMemcpyAsync(trlog, d_trlog, 2 * sizeof(double), hipMemcpyDeviceToHost, computeStream()));
   HIP_CHECK(hipStreamSynchronize(computeStream()));

@@ -1,4 +1,4 @@
-// ferm_force.hip — the fermion force of molecular dynamics for Wilson, degenerate twisted-mass and doublet pseudofermions: the outer
+// ferm_force.hip — the fermion force of molecular dynamics for Wilson, degenerate twisted-mass, doublet and twisted-clover pseudofermions: the outer
 // product kernel and the driver that builds its fields from the solutions of an even-odd solve (DESIGN §3 "Fermion force").
 //
 // Outer product of two full spinor fields, forward neighbours only, projectors placed as in the stencil (forward hop (1 - g_mu) U psi(x+mu)):
@@ -102,6 +102,7 @@ template <typename T, int R> __global__ void __launch_bounds__(256) ferm_force_k
 
 static double g_kernelSecs = 0;
 double fermForceLastKernelSecs() { return g_kernelSecs; }
+void fermForceAddKernelSecs(double secs, bool reset) { g_kernelSecs = (reset ? 0 : g_kernelSecs) + secs; }
 
 static void checkForceField(const ColorSpinorField &f, const ColorSpinorField &like, const LatticeGeom &g) {
   if (f.Location() != QUDA_CUDA_FIELD_LOCATION || f.Precision() != QUDA_DOUBLE_PRECISION || f.SiteSubset() != QUDA_FULL_SITE_SUBSET || f.Nspin() != 4 || f.Ncolor() != 3)
@@ -160,31 +161,45 @@ void fermionOprodForce(MomField &mom, const GaugeField &U, const std::vector<Col
 }
 
 // The fields of the force of phi^dag (Mh^dag Mh)^-1 phi at x = (Mh^dag Mh)^-1 phi on parity p0 (p1 the other), R the site term of the
-// operator (1, 1 + i a g5, or the flavour twist) and every operator in the kappa normalisation of the Dirac classes:
+// operator (1, 1 + i a g5, the flavour twist, or A + i a g5 of twisted clover) and every operator in the kappa normalisation of the Dirac classes:
 //   asymmetric  Mh = R - k^2 D R^-1 D       X = (x, R^-1 D x),  y = Mh x,         Y = (y, R^-dag D^dag y)
 //   symmetric   Mh = 1 - k^2 R^-1 D R^-1 D   X = (x, R^-1 D x),  y = R^-dag Mh x,  Y = (y, R^-dag D^dag y)
 // dS = -d|Mh x|^2 = 2 k^2 sum Re tr(T U O[X, Y]), so F = 2 k^2 TA(U O[X, Y]) and the kernel's coefficient is -dt coeff 2 k^2 s^2 with
 // s the factor the mass normalisations put on Mh: 1 / (4 k^2) (mass) or 1 / (2 k) (asymmetric mass), as massRescale does for the solve.
+// Twisted clover moves R = A(U) + i a g5 with the links as well: with w = Mh x
+//   asymmetric  w^dag d_A Mh x = Y0^dag dA X0 + k^2 Y1^dag dA X1
+//   symmetric   w^dag d_A Mh x = Y0^dag dA (X0 - w) + k^2 Y1^dag dA X1            (R0^-1 D R1^-1 D x = (x - w) / k^2)
+// and Y^dag dA X = i c sum_f tr(dF_f S_f[X, Y]), so the clover part is the derivative G[T] (clover_force.hip) of the tensor field
+// T_f = -2 s^2 i c w_p sum_i dt coeff_i S_f[X'_i, Y_i], w_p = 1 on p0 and k^2 on p1, X' = X with x - w on p0 in the symmetric case:
+// one sigma outer product launch (per kFermForceMaxFields solutions) and one derivative launch after the hop kernel.
 void tmForce(MomField &mom, const GaugeField &U, double dt, const std::vector<ColorSpinorField *> &x, const std::vector<double> &coeff, QudaInvertParam *inv) {
   const size_t n = x.size();
   if (coeff.size() != n) errorQuda("fermion force: %zu solutions, %zu coefficients", n, coeff.size());
+  const bool clover = inv->dslash_type == QUDA_TWISTED_CLOVER_DSLASH;
   const bool twisted = inv->dslash_type == QUDA_TWISTED_MASS_DSLASH;
   const QudaMatPCType mpc = inv->matpc_type;
   const bool asym = mpc == QUDA_MATPC_EVEN_EVEN_ASYMMETRIC || mpc == QUDA_MATPC_ODD_ODD_ASYMMETRIC;
   const bool even = mpc == QUDA_MATPC_EVEN_EVEN || mpc == QUDA_MATPC_EVEN_EVEN_ASYMMETRIC;
   if (!even && mpc != QUDA_MATPC_ODD_ODD && mpc != QUDA_MATPC_ODD_ODD_ASYMMETRIC) errorQuda("fermion force: matpc_type %d undefined", mpc);
-  if (!twisted && asym) errorQuda("fermion force: the Wilson operator has the symmetric matpc types only (matpc_type %d)", mpc);
+  if (!twisted && !clover && asym) errorQuda("fermion force: the Wilson operator has the symmetric matpc types only (matpc_type %d)", mpc);
   DiracParam dp;
   setDiracParam(dp, inv, true);
   dp.dagger = QUDA_DAG_NO;
   Dirac *d = Dirac::create(dp);
   DiracWilson *hop = static_cast<DiracWilson *>(d);                                       // the plain hop D, D^dag
   DiracTwistedMassPC *tm = twisted ? static_cast<DiracTwistedMassPC *>(d) : nullptr;      // R^-1, R^-dag
-  const QudaParity p1 = even ? QUDA_ODD_PARITY : QUDA_EVEN_PARITY;
+  DiracTwistedCloverPC *tc = clover ? static_cast<DiracTwistedCloverPC *>(d) : nullptr;
+  const QudaParity p0 = even ? QUDA_EVEN_PARITY : QUDA_ODD_PARITY, p1 = even ? QUDA_ODD_PARITY : QUDA_EVEN_PARITY;
+  // out = R^-1 in (R^-dag under Dagger(QUDA_DAG_YES)) on parity p
+  const auto rinv = [&](ColorSpinorField &out, const ColorSpinorField &in, QudaParity p) {
+    if (tm) tm->TwistInv(out, in);
+    else if (tc) tc->TwistCloverInv(out, in, p);
+    else blas::copy(out, in);
+  };
 
   ColorSpinorParam fp = deviceSpinorParam(QUDA_DOUBLE_PRECISION, QUDA_FULL_SITE_SUBSET, fieldTwistFlavor(*inv));
   fp.create = QUDA_ZERO_FIELD_CREATE;
-  std::vector<ColorSpinorField *> X(n), Y(n);
+  std::vector<ColorSpinorField *> X(n), Y(n), XW(n, nullptr);
   std::vector<double> c(n);
   double s = 1.0;
   if (inv->mass_normalization == QUDA_MASS_NORMALIZATION) s = 0.25 / (inv->kappa * inv->kappa);
@@ -199,15 +214,34 @@ void tmForce(MomField &mom, const GaugeField &U, double dt, const std::vector<Co
     blas::copy(x0, *x[i]);
     d->Dagger(QUDA_DAG_NO);
     d->Dslash(x1, x0, p1);                      // R^-1 D x (Wilson: D x)
-    if (tm && !asym) { d->M(*t, x0); d->Dagger(QUDA_DAG_YES); tm->TwistInv(y0, *t); }   // y = R^-dag Mh x
-    else { d->M(y0, x0); d->Dagger(QUDA_DAG_YES); }                                     // y = Mh x
+    if ((tm || tc) && !asym) {                  // y = R^-dag Mh x
+      d->M(*t, x0);
+      if (tc) { XW[i] = new ColorSpinorField(pp); blas::xmyz(x0, *t, *XW[i]); }   // x - w
+      d->Dagger(QUDA_DAG_YES);
+      rinv(y0, *t, p0);
+    } else { d->M(y0, x0); d->Dagger(QUDA_DAG_YES); }                              // y = Mh x
     hop->DiracWilson::Dslash(*t, y0, p1);       // D^dag y
-    if (tm) tm->TwistInv(y1, *t); else blas::copy(y1, *t);
+    rinv(y1, *t, p1);
     d->Dagger(QUDA_DAG_NO);
     c[i] = -dt * coeff[i] * 2.0 * inv->kappa * inv->kappa * s * s;
   }
   fermionOprodForce(mom, U, X, Y, c);
-  for (size_t i = 0; i < n; i++) { delete X[i]; delete Y[i]; }
+  if (tc) {
+    const int q0 = even ? 0 : 1, q1 = 1 - q0;
+    std::vector<SigmaOprodPair> pairs(n);
+    for (size_t i = 0; i < n; i++) {
+      SigmaOprodPair &p = pairs[i];
+      p.x[0] = &X[i]->Even(); p.x[1] = &X[i]->Odd(); p.y[0] = &Y[i]->Even(); p.y[1] = &Y[i]->Odd();
+      if (XW[i]) p.x[q0] = XW[i];
+      p.cr[0] = p.cr[1] = 0;
+      p.ci[q0] = -2.0 * s * s * inv->clover_coeff * dt * coeff[i];
+      p.ci[q1] = p.ci[q0] * inv->kappa * inv->kappa;
+    }
+    TensorField T(U.geom);
+    cloverSigmaOprod(T, pairs, false);
+    cloverDerivativeForce(mom, U, T, 1.0);
+  }
+  for (size_t i = 0; i < n; i++) { delete X[i]; delete Y[i]; delete XW[i]; }
   delete t;
   delete d;
 }

@@ -551,8 +551,10 @@ double momActionQuda(void *momentum, QudaGaugeParam *param) {
 static void meetRanksBeforeOperator();
 static void checkFermForceParam(const char *fn, int nvector, const QudaGaugeParam *gp, const QudaInvertParam *inv) {
   checkMdParam(fn, gp);
-  if (inv->dslash_type == QUDA_TWISTED_CLOVER_DSLASH) errorQuda("%s: twisted clover: the derivative of the clover term is not part of this force", fn);
-  if (inv->dslash_type != QUDA_WILSON_DSLASH && inv->dslash_type != QUDA_TWISTED_MASS_DSLASH) errorQuda("%s: dslash_type %d: Wilson and twisted mass only", fn, inv->dslash_type);
+  if (inv->dslash_type != QUDA_WILSON_DSLASH && inv->dslash_type != QUDA_TWISTED_MASS_DSLASH && inv->dslash_type != QUDA_TWISTED_CLOVER_DSLASH)
+    errorQuda("%s: dslash_type %d: Wilson, twisted mass and twisted clover only", fn, inv->dslash_type);
+  if (inv->dslash_type == QUDA_TWISTED_CLOVER_DSLASH && inv->twist_flavor != QUDA_TWIST_PLUS && inv->twist_flavor != QUDA_TWIST_MINUS)
+    errorQuda("%s: twist_flavor %d: twisted clover has the flavours +1 and -1 only (no doublet)", fn, inv->twist_flavor);
   if (inv->cuda_prec != QUDA_DOUBLE_PRECISION) errorQuda("%s: cuda_prec = %d: fp64 spinor fields only", fn, inv->cuda_prec);
   if (inv->solve_type != QUDA_NORMOP_PC_SOLVE && inv->solve_type != QUDA_DIRECT_PC_SOLVE)
     errorQuda("%s: solve_type = %d: the force is that of the even-odd operator (QUDA_NORMOP_PC_SOLVE or QUDA_DIRECT_PC_SOLVE)", fn, inv->solve_type);
@@ -571,6 +573,27 @@ static std::vector<ColorSpinorField *> uploadForceFields(void **h, int n, QudaIn
     *out[i] = host;
   }
   return out;
+}
+// the resident clover term as the clover force needs it: fp64, with the inverse of this kappa and mu; needCoeff: built from the links
+// with the clover_coeff of inv, which the derivative of A = 1 + i c sum sigma F carries
+static void checkForceClover(const char *fn, const QudaInvertParam *inv, bool needCoeff) {
+  if (!g_initialized) errorQuda("QUDA not initialized");
+  if (inv->dslash_type != QUDA_TWISTED_CLOVER_DSLASH) errorQuda("%s: dslash_type %d: twisted clover only", fn, inv->dslash_type);
+  if (inv->twist_flavor != QUDA_TWIST_PLUS && inv->twist_flavor != QUDA_TWIST_MINUS) errorQuda("%s: twist_flavor %d: twisted clover has the flavours +1 and -1 only", fn, inv->twist_flavor);
+  if (!cloverPrecise) errorQuda("%s: no resident clover term (loadCloverQuda)", fn);
+  if (cloverPrecise->precision != QUDA_DOUBLE_PRECISION) errorQuda("%s: the resident clover term is held in precision %d: clover_cuda_prec must be fp64", fn, cloverPrecise->precision);
+  const double mu2 = 4.0 * inv->kappa * inv->kappa * inv->mu * inv->mu;
+  if (fabs(cloverPrecise->mu2 - mu2) > 1e-14 * (mu2 + cloverPrecise->mu2))
+    errorQuda("%s: the resident clover inverse was computed with 4 kappa^2 mu^2 = %.17g, inv_param gives %.17g", fn, cloverPrecise->mu2, mu2);
+  if (!needCoeff) return;
+  if (cloverPrecise->coeff != cloverPrecise->coeff)
+    errorQuda("%s: the resident clover term was loaded from a host field, so its coefficient is unknown: build it from the links (loadCloverQuda(NULL, NULL, inv_param))", fn);
+  if (inv->clover_coeff != cloverPrecise->coeff) errorQuda("%s: clover_coeff = %.17g, the resident clover term was built with %.17g", fn, inv->clover_coeff, cloverPrecise->coeff);
+}
+static void checkForceLattice(const char *fn, const QudaGaugeParam *gp) {
+  checkMdParam(fn, gp);
+  if (!gaugePrecise) errorQuda("%s: No resident gauge field to use", fn);
+  for (int d = 0; d < 4; d++) if (gp->X[d] != g_geom.X[d]) errorQuda("%s: X[%d] = %d differs from the resident links' %d", fn, d, gp->X[d], g_geom.X[d]);
 }
 static void fermForceCall(const char *fn, void *mom, QudaGaugeParam *param, const std::function<void(MomField &)> &force) {
   bool ownM;
@@ -593,6 +616,10 @@ void qudaAmdFermionOprodForce(void *mom, void **h_x, void **h_y, double *coeff, 
 
 void qudaAmdComputeTMForce(void *mom, double dt, void **h_x, double *coeff, int nvector, QudaGaugeParam *gauge_param, QudaInvertParam *inv_param) {
   checkFermForceParam("qudaAmdComputeTMForce", nvector, gauge_param, inv_param);
+  if (inv_param->dslash_type == QUDA_TWISTED_CLOVER_DSLASH) {
+    checkForceClover("qudaAmdComputeTMForce", inv_param, true);
+    checkCloverDerivativeUnpartitioned("qudaAmdComputeTMForce");
+  }
   fermForceCall("qudaAmdComputeTMForce", mom, gauge_param, [&](MomField &M) {
     std::vector<ColorSpinorField *> x = uploadForceFields(h_x, nvector, inv_param, true);
     tmForce(M, *gaugePrecise, dt, x, std::vector<double>(coeff, coeff + nvector), inv_param);
@@ -601,6 +628,61 @@ void qudaAmdComputeTMForce(void *mom, double dt, void **h_x, double *coeff, int 
 }
 
 double qudaAmdFermForceLastKernelSecs(void) { return fermForceLastKernelSecs(); }
+
+// ---- the clover part of the twisted-clover force and the determinant force (clover_force.hip) ----
+void qudaAmdCloverSigmaOprod(double *h_tensor, void **h_x, void **h_y, double *coeff, int nvector, QudaInvertParam *inv_param) {
+  const char *fn = "qudaAmdCloverSigmaOprod";
+  if (!g_initialized) errorQuda("QUDA not initialized");
+  if (!gaugePrecise) errorQuda("%s: No resident gauge field (it fixes the lattice)", fn);
+  if (inv_param->cuda_prec != QUDA_DOUBLE_PRECISION) errorQuda("%s: cuda_prec = %d: fp64 spinor fields only", fn, inv_param->cuda_prec);
+  if (nvector < 1) errorQuda("%s: nvector = %d", fn, nvector);
+  if (inv_param->twist_flavor == QUDA_TWIST_NONDEG_DOUBLET) errorQuda("%s: one-flavour fields only", fn);
+  fermForceAddKernelSecs(0, true);
+  std::vector<ColorSpinorField *> X = uploadForceFields(h_x, nvector, inv_param, false), Y = uploadForceFields(h_y, nvector, inv_param, false);
+  std::vector<SigmaOprodPair> pairs(nvector);
+  for (int i = 0; i < nvector; i++) {
+    pairs[i].x[0] = &X[i]->Even(); pairs[i].x[1] = &X[i]->Odd(); pairs[i].y[0] = &Y[i]->Even(); pairs[i].y[1] = &Y[i]->Odd();
+    for (int q = 0; q < 2; q++) { pairs[i].cr[q] = coeff[2 * i + q]; pairs[i].ci[q] = 0; }
+  }
+  TensorField T(g_geom);
+  cloverSigmaOprod(T, pairs, false);
+  T.save(h_tensor);
+  for (int i = 0; i < nvector; i++) { delete X[i]; delete Y[i]; }
+}
+
+void qudaAmdCloverSigmaTrace(double *h_tensor, double coeff_even, double coeff_odd, QudaInvertParam *inv_param) {
+  checkForceClover("qudaAmdCloverSigmaTrace", inv_param, false);
+  fermForceAddKernelSecs(0, true);
+  const double cr[2] = {coeff_even, coeff_odd}, ci[2] = {0, 0};
+  TensorField T(g_geom);
+  cloverSigmaTrace(T, *cloverPrecise, cr, ci, false);
+  T.save(h_tensor);
+}
+
+void qudaAmdCloverDerivativeForce(void *mom, double *h_tensor, double coeff, QudaGaugeParam *gauge_param) {
+  checkForceLattice("qudaAmdCloverDerivativeForce", gauge_param);
+  checkCloverDerivativeUnpartitioned("qudaAmdCloverDerivativeForce");
+  fermForceCall("qudaAmdCloverDerivativeForce", mom, gauge_param, [&](MomField &M) {
+    fermForceAddKernelSecs(0, true);
+    TensorField T(g_geom);
+    T.load(h_tensor);
+    cloverDerivativeForce(M, *gaugePrecise, T, coeff);
+  });
+}
+
+void qudaAmdCloverLogDetForce(void *mom, double dt, double coeff_even, double coeff_odd, QudaGaugeParam *gauge_param, QudaInvertParam *inv_param) {
+  checkForceLattice("qudaAmdCloverLogDetForce", gauge_param);
+  checkForceClover("qudaAmdCloverLogDetForce", inv_param, true);
+  checkCloverDerivativeUnpartitioned("qudaAmdCloverLogDetForce");
+  fermForceCall("qudaAmdCloverLogDetForce", mom, gauge_param, [&](MomField &M) {
+    fermForceAddKernelSecs(0, true);
+    // d log det(A^2 + a^2) = 2 i c sum_f tr(dF_f tr_sigma(B)_f)
+    const double cr[2] = {0, 0}, ci[2] = {2.0 * inv_param->clover_coeff * coeff_even, 2.0 * inv_param->clover_coeff * coeff_odd};
+    TensorField T(g_geom);
+    cloverSigmaTrace(T, *cloverPrecise, cr, ci, false);
+    cloverDerivativeForce(M, *gaugePrecise, T, dt);
+  });
+}
 
 // reference :730-930.  Host order: QUDA_PACKED_CLOVER_ORDER.  If the inverse is not supplied (or
 // compute_clover_inverse is set) it is computed on the device; for twisted clover it is (A^2 + 4 kappa^2 mu^2)^-1
@@ -623,7 +705,7 @@ void loadCloverQuda(void *h_clover, void *h_clovinv, QudaInvertParam *inv) {
     CloverField *c = new CloverField(g_geom, prec);
     if (device_calc) c->computeFromGauge(*gaugePrecise, inv->clover_coeff);
     else c->loadPacked(h_clover, compute_inv ? nullptr : h_clovinv, inv->clover_cpu_prec);
-    if (compute_inv) c->computeInverse(mu2);
+    if (compute_inv) c->computeInverse(mu2, twisted);
     else { c->twisted = twisted; c->mu2 = mu2; }
     return c;
   };

@@ -933,7 +933,7 @@ void multigridSetHalfStorage(multigrid_solver &mgs, bool on) {
         dps.clover->savePacked(host.data(), QUDA_DOUBLE_PRECISION);
         mgs.cloverHalf = new CloverField(g->geom, QUDA_HALF_PRECISION);
         mgs.cloverHalf->loadPacked(host.data(), nullptr, QUDA_DOUBLE_PRECISION);
-        mgs.cloverHalf->computeInverse(4.0 * param->kappa * param->kappa * param->mu * param->mu);
+        mgs.cloverHalf->computeInverse(4.0 * param->kappa * param->kappa * param->mu * param->mu, true);
         dps.clover = mgs.cloverHalf;
       }
       mgs.dSmoothHalf = Dirac::create(dps);
