@@ -243,6 +243,21 @@ long projectSU3Links(void *const h_out[4], const GaugeField &U, double tol);
 // sum over links of tr(A^dag A)/2 - 4, global, in a fixed order
 double momAction(const MomField &mom);
 
+// ---- gauge fixing (gauge_fix.hip; DESIGN section 3 "Gauge fixing") ----
+struct GaugeFixResult { int iterations; double F, theta, delta; };   // delta: the last |F - F_prev|
+// Overrelaxation towards the maximum of F = sum_x sum_{mu<D} Re tr U_mu(x) / (3 D V), D = 3 if gauge_dir == 3 (Coulomb) else 4 (Landau):
+// at most nsteps iterations (even sites, then odd) with parameter omega, the links projected onto SU(3) when iteration % reunit_interval
+// == reunit_interval - 1 and at the end; stops when theta (stop_theta) or |F - F_prev| falls below tolerance.  fp64 on matrix fields
+// whatever the precision of U; the anti-periodic sign of the time links is taken off for the run and put back.  The direct sweep on
+// an unpartitioned lattice, the transport formulation on a partitioned one or under QUDA_AMD_GAUGE_FIX_TRANSPORT=1.  h_out: the fixed
+// links in host QDP order; h_transform (may be NULL): G(x), V x 18 reals, even sites then odd, with U^fixed_mu(x) = G(x) U_mu(x) G(x + mu)^dag;
+// secs: {extracting the links, iterating, writing the result}
+GaugeFixResult gaugeFixOVR(void *const h_out[4], double *h_transform, const GaugeField &U, int gauge_dir, int nsteps, int verbose_interval, double omega,
+                           double tolerance, int reunit_interval, int stop_theta, double secs[3]);
+bool gaugeFixUsesTransport();
+// out = {F, theta} of the links of U (sign of the time boundary taken off), global, in a fixed summation order
+void gaugeFixQuality(const GaugeField &U, int gauge_dir, double out[2]);
+
 // ---- fermion force (ferm_force.hip) ----
 constexpr int kFermForceMaxFields = 16;   // (X, Y) pairs of one launch, a doublet counting two: more are chunked on the host
 // mom <- TA(mom - sum_i coeff[i] U O[X_i, Y_i]), O_mu[X, Y](x) = tr_spin[(1 - g_mu) X(x + mu) Y^dag(x) + (1 + g_mu) Y(x + mu) X^dag(x)]

@@ -185,6 +185,20 @@ int computeGaugeForceQuda(void *mom, void *sitelink, int ***input_path_buf, int 
 void updateGaugeFieldQuda(void *gauge, void *momentum, double dt, int conj_mom, int exact, QudaGaugeParam *param);  /* ref quda.h:793; lib/interface_quda.cpp:5081: U <- exp(dt A) U, exact or to eighth order */
 void projectSU3Quda(void *gauge_h, double tol, QudaGaugeParam *param);  /* ref quda.h:815; lib/interface_quda.cpp:5187: every link onto SU(3); a link off by more than tol is an error */
 double momActionQuda(void *momentum, QudaGaugeParam *param);  /* ref quda.h:825; lib/interface_quda.cpp:5310: sum over links of tr(A^dag A)/2 - 4 */
+/* ref quda.h:998; lib/interface_quda.cpp:5716 (lib/gauge_fix_ovr.cu): Landau (gauge_dir != 3) or Coulomb (gauge_dir == 3) gauge fixing by
+   overrelaxation.  Field handling as the molecular-dynamics calls above (use_resident_gauge, return_result_gauge, make_resident_gauge); fp64
+   arithmetic whatever cuda_prec; the anti-periodic sign of the time links is taken off for the run and put back.  timeinfo (may be NULL):
+   {load, compute, save} seconds.  Returns 0.  qudaAmdGaugeFixOVR (quda_amd_ext.h) also returns the transformation and the final figures. */
+int computeGaugeFixingOVRQuda(void* gauge,
+                      const unsigned int gauge_dir,
+                      const unsigned int Nsteps,
+                      const unsigned int verbose_interval,
+                      const double relax_boost,
+                      const double tolerance,
+                      const unsigned int reunit_interval,
+                      const unsigned int stopWtheta,
+                      QudaGaugeParam* param,
+                      double* timeinfo);
 void loadCloverQuda(void *h_clover, void *h_clovinv, QudaInvertParam *inv_param); /* ref quda.h:607; interface_quda.cpp:730 */
 void freeCloverQuda(void);                                 /* ref quda.h:613 */
 

@@ -301,6 +301,16 @@ double qudaAmdQCharge(double *h_density, int lexicographic, int which);
 /* Test hook: out[k] = exp(i q[k]) for n traceless Hermitian 3x3 matrices, 18 doubles each (row-major, re/im), evaluated on the
  * device by the function the stout kernel calls (Cayley-Hamilton form). */
 void qudaAmdSu3ExpIQ(int n, const double *q, double *out);
+/* Gauge fixing by overrelaxation: computeGaugeFixingOVRQuda (quda.h) with two more results.  h_transform (may be NULL): the accumulated
+ * transformation G of the calling rank's local lattice, V x 18 doubles (row-major, re/im), even sites then odd, with
+ * U^fixed_mu(x) = G(x) U_mu(x) G(x + mu)^dag for the input links without their anti-periodic sign.  info (may be NULL): {iterations done,
+ * F, theta, the last |F - F_prev|}; F = sum_x sum_{mu<D} Re tr U_mu(x) / (3 D V) and theta = sum_x tr(Delta Delta^dag) / (3 V) as evaluated
+ * after the last iteration, D = 3 for gauge_dir == 3 (Coulomb) and 4 otherwise (Landau), V the global volume.
+ * qudaAmdGaugeFixQuality: out = {F, theta} of the resident precise links, summed in a fixed order (the same field gives the same bits). */
+int qudaAmdGaugeFixOVR(void *gauge, const unsigned int gauge_dir, const unsigned int Nsteps, const unsigned int verbose_interval, const double relax_boost,
+                       const double tolerance, const unsigned int reunit_interval, const unsigned int stopWtheta, QudaGaugeParam *param, double *timeinfo,
+                       void *h_transform, double info[4]);
+void qudaAmdGaugeFixQuality(unsigned gauge_dir, double out[2]);
 /* Fermion force of molecular dynamics for the actions this library solves (Wilson, degenerate twisted mass, the non-degenerate
  * doublet, twisted clover); the reference's only Wilson-type fermion force, computeCloverForceQuda, belongs to the Wilson-clover action
  * with the MILC / Chroma gamma5 conventions and is not provided under that name.  Conventions

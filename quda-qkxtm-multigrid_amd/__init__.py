@@ -110,6 +110,7 @@ class QudaMultigridParam(C.Structure):
 QUDA_H_SYMBOLS = ["setVerbosityQuda", "initCommsGridQuda", "initQudaDevice", "initQudaMemory", "initQuda", "endQuda",
                   "newQudaGaugeParam", "newQudaInvertParam", "newQudaMultigridParam", "printQudaGaugeParam", "printQudaInvertParam",
                   "printQudaMultigridParam", "loadGaugeQuda", "freeGaugeQuda", "performSTOUTnStep", "qChargeCuda", "computeGaugeForceQuda", "updateGaugeFieldQuda", "projectSU3Quda", "momActionQuda",
+                  "computeGaugeFixingOVRQuda",
                   "loadCloverQuda", "freeCloverQuda", "invertQuda", "invertMultiSrcQuda", "invertMultiShiftQuda",
                   "newMultigridQuda", "destroyMultigridQuda", "dslashQuda", "cloverQuda", "MatQuda", "MatDagMatQuda", "openMagma",
                   "closeMagma"]
@@ -136,7 +137,8 @@ EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLo
                  "qudaAmdBlockGhostPanels", "qudaAmdBlockFineApply",
                  "qudaAmdMultigridGetCoarseSiteLinks", "qudaAmdMultigridCoarseApply", "qudaAmdMultigridCoarsePC", "qudaAmdCoarseInvertSites",
                  "qudaAmdFermionOprodForce", "qudaAmdComputeTMForce", "qudaAmdFermForceLastKernelSecs",
-                 "qudaAmdCloverSigmaOprod", "qudaAmdCloverSigmaTrace", "qudaAmdCloverDerivativeForce", "qudaAmdCloverLogDetForce"]
+                 "qudaAmdCloverSigmaOprod", "qudaAmdCloverSigmaTrace", "qudaAmdCloverDerivativeForce", "qudaAmdCloverLogDetForce",
+                 "qudaAmdGaugeFixOVR", "qudaAmdGaugeFixQuality"]
 
 _lib = None
 
@@ -356,6 +358,13 @@ def lib():
         L.projectSU3Quda.restype = None
         L.momActionQuda.argtypes = [_p, C.POINTER(QudaGaugeParam)]
         L.momActionQuda.restype = _d
+        _u = C.c_uint
+        L.computeGaugeFixingOVRQuda.argtypes = [_p, _u, _u, _u, _d, _d, _u, _u, C.POINTER(QudaGaugeParam), C.POINTER(_d)]
+        L.computeGaugeFixingOVRQuda.restype = _i
+        L.qudaAmdGaugeFixOVR.argtypes = [_p, _u, _u, _u, _d, _d, _u, _u, C.POINTER(QudaGaugeParam), C.POINTER(_d), _p, C.POINTER(_d)]
+        L.qudaAmdGaugeFixOVR.restype = _i
+        L.qudaAmdGaugeFixQuality.argtypes = [_u, C.POINTER(_d)]
+        L.qudaAmdGaugeFixQuality.restype = None
         L.qudaAmdFermionOprodForce.argtypes = [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_d), _i, C.POINTER(QudaGaugeParam), C.POINTER(QudaInvertParam)]
         L.qudaAmdFermionOprodForce.restype = None
         L.qudaAmdComputeTMForce.argtypes = [_p, _d, C.POINTER(_p), C.POINTER(_d), _i, C.POINTER(QudaGaugeParam), C.POINTER(QudaInvertParam)]
@@ -1007,6 +1016,30 @@ def project_su3(gp, tol, gauge=None, make_resident_gauge=False, return_gauge=Tru
     q = _md_param(gp, use_resident_gauge=gauge is None, make_resident_gauge=make_resident_gauge, return_result_gauge=return_gauge)
     lib().projectSU3Quda(_qdp_ptrs(out), float(tol), C.byref(q))
     return out if return_gauge else None
+
+
+def gauge_fix_ovr(gp, gauge_dir, n_steps, relax_boost, tolerance, reunit_interval, stop_theta, gauge=None, make_resident_gauge=False,
+                  return_gauge=True, transform=False, verbose_interval=0):
+    """computeGaugeFixingOVRQuda / qudaAmdGaugeFixOVR: Landau (gauge_dir != 3) or Coulomb (3) gauge fixing by overrelaxation.  gauge
+    None: the resident links.  Returns (links, G, info): the fixed links, (4, V*18) host QDP order (None unless return_gauge); with
+    transform the accumulated transformation G, (V, 18), even sites then odd, else None; info = {"iterations", "F", "theta", "delta",
+    "secs": (load, compute, save)}"""
+    V = int(np.prod([gp.X[d] for d in range(4)]))
+    out = np.zeros((4, V * 18)) if gauge is None else np.array([np.asarray(gauge[d], dtype=np.float64) for d in range(4)]).reshape(4, V * 18)
+    q = _md_param(gp, use_resident_gauge=gauge is None, make_resident_gauge=make_resident_gauge, return_result_gauge=return_gauge)
+    G = np.zeros((V, 18)) if transform else None
+    info, secs = (_d * 4)(), (_d * 3)()
+    lib().qudaAmdGaugeFixOVR(_qdp_ptrs(out), int(gauge_dir), int(n_steps), int(verbose_interval), float(relax_boost), float(tolerance),
+                             int(reunit_interval), int(bool(stop_theta)), C.byref(q), secs, _vp(G), info)
+    return (out if return_gauge else None, G,
+            {"iterations": int(info[0]), "F": float(info[1]), "theta": float(info[2]), "delta": float(info[3]), "secs": tuple(secs)})
+
+
+def gauge_fix_quality(gauge_dir):
+    """qudaAmdGaugeFixQuality: (F, theta) of the resident precise links for gauge_dir 3 (Coulomb) or any other value (Landau)"""
+    out = (_d * 2)()
+    lib().qudaAmdGaugeFixQuality(int(gauge_dir), out)
+    return float(out[0]), float(out[1])
 
 
 def save_smeared_gauge(local_volume, lexicographic=False):

@@ -1,5 +1,5 @@
 // gauge_device.h — the 3x3 colour-matrix device code that clover.hip (clover construction), gauge_obs.hip (smearing, plaquette,
-// topological charge) and gauge_md.hip (gauge force, link update, SU(3) projection) share, and ferm_force.hip with them: the matrix
+// topological charge), gauge_md.hip (gauge force, link update, SU(3) projection) and gauge_fix.hip (gauge fixing) share, and ferm_force.hip with them: the matrix
 // type and its products, the resident-link loader, the epilogue of both force kernels, matrix fields with their load/store, the
 // polar SU(3) projection, exp(iQ), the clover-leaf sum with its scatter into the clover blocks and the block sum of the reductions;
 // and the host helpers of the transport formulation: pools of matrix fields, links to the host, ordered sums.
@@ -181,6 +181,18 @@ __device__ __forceinline__ void polar_su3(M3 &m, double tol) {
   for (int k = 0; k < 9; k++) { m.re[k] = out.re[k] * cr - out.im[k] * ci; m.im[k] = out.re[k] * ci + out.im[k] * cr; }
 }
 
+// max |U^dag U - 1| over the entries: how far a projected link still is from unitary
+__device__ __forceinline__ double unitarity_deviation(const M3 &u) {
+  M3 d, p;
+  m3_dag(d, u);
+  m3_mul(p, d, u);
+  p.re[0] -= 1.0; p.re[4] -= 1.0; p.re[8] -= 1.0;
+  double dev = 0;
+#pragma unroll
+  for (int k = 0; k < 9; k++) dev = fmax(dev, fmax(fabs(p.re[k]), fabs(p.im[k])));
+  return dev;
+}
+
 // ---- exp(iQ) of a traceless Hermitian Q ----
 // exp(iQ) = f0 + f1 Q + f2 Q^2 of a traceless Hermitian Q by the Cayley-Hamilton form (eqs. 14-34 of the paper):
 //   c0 = tr Q^3 / 3 = det Q,  c1 = tr Q^2 / 2,  c0max = 2 (c1/3)^(3/2),  theta = acos(c0 / c0max),
@@ -313,6 +325,8 @@ GaugeView viewOf(const GaugeField &U);
 void extractForwardLinks(MatField F, const GaugeField &U, int mu);
 void shiftField(MatField out, MatField in, const LatticeGeom &geom, int dir);
 void mfMul(MatField out, MatField A, MatField B, int dagA, int dagB, int accumulate);
+// F in host QDP order (even sites then odd, 18 reals per site) at stage, a device pointer: the launch of matFieldsToHost
+void matFieldToQdp(double *stage, MatField F, int mu);
 // the four clover leaves of the mu-nu plane by transport: on return W[4] = P, W[1] = T_mu P, W[2] = T_nu P, W[3] = T_nu T_mu P
 // (W[0] is scratch)
 void cloverLeaves(MatField W[5], const GaugeField &U, int mu, int nu);

@@ -250,19 +250,13 @@ __global__ void __launch_bounds__(128) project_su3_kernel(double *qdp, int *fail
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= 2 * Vh) return;
   const int par = gid >= Vh, idx = gid - par * Vh;
-  M3 u, d, p;
+  M3 u;
   mf_load(u, F, par, idx);
   const double sg = (sign_t >= 0 && idx >= sign_t) ? -1.0 : 1.0;   // sign_t: first checkerboard index of the last time slice (t runs slowest), or -1
 #pragma unroll
   for (int k = 0; k < 9; k++) { u.re[k] *= sg; u.im[k] *= sg; }
   polar_su3(u, 1e-15);
-  m3_dag(d, u);
-  m3_mul(p, d, u);
-  p.re[0] -= 1.0; p.re[4] -= 1.0; p.re[8] -= 1.0;
-  double dev = 0;
-#pragma unroll
-  for (int k = 0; k < 9; k++) dev = fmax(dev, fmax(fabs(p.re[k]), fabs(p.im[k])));
-  if (!(dev <= tol)) atomicAdd(failures, 1);
+  if (!(unitarity_deviation(u) <= tol)) atomicAdd(failures, 1);
   double *o = qdp + (size_t)gid * 18;
 #pragma unroll
   for (int k = 0; k < 9; k++) { o[2 * k] = sg * u.re[k]; o[2 * k + 1] = sg * u.im[k]; }

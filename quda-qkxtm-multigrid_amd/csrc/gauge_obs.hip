@@ -200,7 +200,7 @@ __global__ void mf_to_qdp_kernel(double *qdp, MatField F, int Vh) {
 #pragma unroll
   for (int k = 0; k < 9; k++) { o[2 * k] = u.re[k]; o[2 * k + 1] = u.im[k]; }
 }
-static void mfToQdp(double *stage, MatField F, int) { launchSites(mf_to_qdp_kernel, F.Vh, 128, stage, F, F.Vh); }
+void matFieldToQdp(double *stage, MatField F, int) { launchSites(mf_to_qdp_kernel, F.Vh, 128, stage, F, F.Vh); }
 
 // S = sum over the smeared directions mu != nu (mu < ndir) of the upper and the lower staple of (x, nu); F: the forward links of
 // the previous step, W1, W2, T1, T2: scratch.  Shared by the APE and the stout step.
@@ -237,7 +237,7 @@ template <typename Update> static GaugeField *smearLinks(const GaugeField &U, un
       // every direction of a step is smeared from the links of the previous step (the reference reads a copy, :5621-5627)
       for (int nu = 0; nu < ndir; nu++) std::swap(F[nu], G[nu]);
     }
-    matFieldsToHost(host.ptr, geom, [&](int mu) { return F[mu]; }, mfToQdp);
+    matFieldsToHost(host.ptr, geom, [&](int mu) { return F[mu]; }, matFieldToQdp);
   }
   // back through the loader: it builds the bidirectional layout and fetches the backward links that live on the neighbour ranks
   GaugeField *out = new GaugeField(geom, QUDA_DOUBLE_PRECISION, QUDA_RECONSTRUCT_NO, U.t_boundary, U.anisotropy);
@@ -316,7 +316,7 @@ GaugeField *stoutSmear(const GaugeField &U, unsigned nSteps, double rho, int ndi
 }
 void saveGaugeQDP(const GaugeField &U, void *const h_gauge[4], QudaPrecision cpu_prec) {
   if (cpu_prec != QUDA_DOUBLE_PRECISION) errorQuda("saving links: fp64 host fields only");
-  linksToHost(h_gauge, U, mfToQdp);
+  linksToHost(h_gauge, U, matFieldToQdp);
 }
 
 // plq[0] = mean of the spatial and temporal averages, plq[1] = spatial, plq[2] = temporal (lib/gauge_plaq.cu:129-153)

@@ -536,6 +536,39 @@ void projectSU3Quda(void *gauge_h, double tol, QudaGaugeParam *param) {
   if (param->make_resident_gauge) makeLinksResident(links, param, !ownU);
 }
 
+// reference lib/interface_quda.cpp:5716-5826 (lib/gauge_fix_ovr.cu).  Unlike the reference, which always reloads the host links and
+// leaves them resident, the fields follow the flags of the molecular-dynamics calls above
+int qudaAmdGaugeFixOVR(void *gauge, const unsigned int gauge_dir, const unsigned int Nsteps, const unsigned int verbose_interval, const double relax_boost,
+                       const double tolerance, const unsigned int reunit_interval, const unsigned int stopWtheta, QudaGaugeParam *param, double *timeinfo,
+                       void *h_transform, double info[4]) {
+  const char *fn = "computeGaugeFixingOVRQuda";
+  checkMdParam(fn, param);
+  if (reunit_interval == 0) errorQuda("%s: reunit_interval = 0: the links are projected when iteration %% reunit_interval == reunit_interval - 1", fn);
+  if (Nsteps > 0x7fffffffu || reunit_interval > 0x7fffffffu || verbose_interval > 0x7fffffffu) errorQuda("%s: Nsteps, reunit_interval and verbose_interval have to fit an int", fn);
+  bool ownU;
+  GaugeField *U = mdLinks(fn, gauge, param, ownU);
+  const size_t n = (size_t)U->geom.V * 18;
+  HostLinks links(U->geom.V);
+  double secs[3] = {0, 0, 0};
+  const GaugeFixResult res = gaugeFixOVR(links.ptr, (double *)h_transform, *U, gauge_dir == 3 ? 3 : 4, (int)Nsteps, (int)verbose_interval, relax_boost, tolerance,
+                                         (int)reunit_interval, stopWtheta != 0, secs);
+  if (ownU) delete U;
+  if (param->return_result_gauge) for (int d = 0; d < 4; d++) memcpy(((void **)gauge)[d], links.ptr[d], n * sizeof(double));
+  if (param->make_resident_gauge) makeLinksResident(links, param, !ownU);
+  if (timeinfo) for (int k = 0; k < 3; k++) timeinfo[k] = secs[k];
+  if (info) { info[0] = res.iterations; info[1] = res.F; info[2] = res.theta; info[3] = res.delta; }
+  return 0;
+}
+int computeGaugeFixingOVRQuda(void *gauge, const unsigned int gauge_dir, const unsigned int Nsteps, const unsigned int verbose_interval, const double relax_boost,
+                              const double tolerance, const unsigned int reunit_interval, const unsigned int stopWtheta, QudaGaugeParam *param, double *timeinfo) {
+  return qudaAmdGaugeFixOVR(gauge, gauge_dir, Nsteps, verbose_interval, relax_boost, tolerance, reunit_interval, stopWtheta, param, timeinfo, nullptr, nullptr);
+}
+void qudaAmdGaugeFixQuality(unsigned gauge_dir, double out[2]) {
+  if (!g_initialized) errorQuda("QUDA not initialized");
+  if (!gaugePrecise) errorQuda("qudaAmdGaugeFixQuality: No resident gauge field to use");
+  gaugeFixQuality(*gaugePrecise, gauge_dir == 3 ? 3 : 4, out);
+}
+
 // reference lib/interface_quda.cpp:5310-5370 (lib/momentum.cu)
 double momActionQuda(void *momentum, QudaGaugeParam *param) {
   checkMdParam("momActionQuda", param);
