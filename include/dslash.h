@@ -65,6 +65,8 @@ void applyFineBlockM(float2 *out, float2 *in, int nrhs, const GaugeField &U, dou
 struct FineBlockDots { const float2 *a; int mode; };
 void applyFineBlockParity(float2 *out, const float2 *in_same, const float2 *in_other, int nrhs, const GaugeField &U, int parity, double s0, double a0, double k1,
                           double a1, const float *tmat = nullptr, int tmode = 0, float2 *ghost = nullptr, const FineBlockDots *dots = nullptr);
+// whether a launch on this lattice with nrhs right-hand sides walks its work-groups in the XCD plane-tiled order (else: linear)
+bool fineBlockOrderTiled(const LatticeGeom &g, int nrhs);
 bool fineBlockDotsSupported(int nrhs);
 void fineBlockDotsFinish(double *sums, int nrhs, int mode);
 // mode 3 (4 or 8 right-hand sides): (out, in_same), |out|^2 only — the sums of a minimal-residual step, no further field read (a unused).

@@ -137,6 +137,14 @@ int qudaAmdBlockGhostPanels(int parityField);
  * mode 1, 2, 3 (dslash.h FineBlockDots, a = dotA; NULL for mode 3): the epilogue sums, finished by fineBlockDotsFinish (deviceSums = 0) or
  * by fineBlockDotsFinishDev into device memory and copied back (deviceSums != 0), in sums[k * nrhs + i] */
 void qudaAmdBlockFineApply(void *out, void *in_same, void *in_other, void *dotA, int parity, double s0, double a0, double k1, double a1, int mode, int deviceSums, double *sums);
+/* cloverTwistDense on the resident precise clover field (fp32: clover_cuda_prec = 4): the dense site matrices A + i a s (s = +1 upper, -1
+ * lower chirality) of one parity, or their inverses (inverse != 0), copied to h_out[site][chirality][6][6] complex fp32 */
+void qudaAmdCloverTwistDense(int parity, double a, int inverse, float *h_out);
+/* the same parity launch as qudaAmdBlockFineApply (no inner products) with the dense site matrices of the OUTPUT parity, built here by
+ * cloverTwistDense(a, inverse) and freed after a stream synchronise: tmode 1 puts them on the hop sum in place of (1 + i a1 g5), tmode 2 on
+ * in_same in place of (1 + i a0 g5), tmode 0 launches without them (a, inverse unused).  Ghost panels as for qudaAmdBlockFineApply.
+ * Returns a flag word: bit 0 is set if the launch walked its work-groups in the XCD plane-tiled order (fineBlockOrderTiled), clear: linear */
+int qudaAmdBlockFineApplySite(void *out, void *in_same, void *in_other, int parity, double s0, double a0, double k1, double a1, int tmode, double a, int inverse);
 /* out = (M^dag M + shift) in through the DiracMdagM functor the solvers use; shift = 0 launches exactly what qudaAmdDiracMdagM does */
 void qudaAmdDiracMdagMShift(void *dirac, void *out, const void *in, double shift);
 /* device-event timed loops for tools/cg_timing.py, seconds per pass:

@@ -134,7 +134,7 @@ EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLo
                  "qudaAmdBlasMultiCaxpy", "qudaAmdBlasHeavyQuarkResidualNorm",
                  "qudaAmdBlockFieldCreate", "qudaAmdBlockFieldDestroy", "qudaAmdBlockFieldLoad", "qudaAmdBlockFieldSave", "qudaAmdBlockBlasApply",
                  "qudaAmdBlockMrUpdate", "qudaAmdBlockPack", "qudaAmdBlockUnpack", "qudaAmdBlockPackParity", "qudaAmdBlockUnpackParity",
-                 "qudaAmdBlockGhostPanels", "qudaAmdBlockFineApply",
+                 "qudaAmdBlockGhostPanels", "qudaAmdBlockFineApply", "qudaAmdCloverTwistDense", "qudaAmdBlockFineApplySite",
                  "qudaAmdMultigridGetCoarseSiteLinks", "qudaAmdMultigridCoarseApply", "qudaAmdMultigridCoarsePC", "qudaAmdCoarseInvertSites",
                  "qudaAmdFermionOprodForce", "qudaAmdComputeTMForce", "qudaAmdFermForceLastKernelSecs",
                  "qudaAmdCloverSigmaOprod", "qudaAmdCloverSigmaTrace", "qudaAmdCloverDerivativeForce", "qudaAmdCloverLogDetForce",
@@ -271,6 +271,11 @@ def lib():
             L.qudaAmdBlockGhostPanels.restype = _i
             L.qudaAmdBlockFineApply.argtypes = [_p, _p, _p, _p, _i, _d, _d, _d, _d, _i, _i, _p]
             L.qudaAmdBlockFineApply.restype = None
+        if hasattr(L, "qudaAmdBlockFineApplySite"):
+            L.qudaAmdCloverTwistDense.argtypes = [_i, _d, _i, _p]
+            L.qudaAmdCloverTwistDense.restype = None
+            L.qudaAmdBlockFineApplySite.argtypes = [_p, _p, _p, _i, _d, _d, _d, _d, _i, _d, _i]
+            L.qudaAmdBlockFineApplySite.restype = _i
         L.qudaAmdDiracMdagMShift.argtypes = [_p, _p, _p, _d]
         L.qudaAmdDiracMdagMShift.restype = None
         L.qudaAmdTimeMdagM.argtypes = [_p, _p, _p, _i]
@@ -762,6 +767,21 @@ def block_fine_apply(out, in_same, in_other, parity, s0, a0, k1, a1, mode=0, dot
     lib().qudaAmdBlockFineApply(out.h, in_same.h if in_same is not None else None, in_other.h, dot_a.h if dot_a is not None else None, int(parity),
                                 float(s0), float(a0), float(k1), float(a1), int(mode), int(bool(device_sums)), _vp(sums))
     return sums.reshape(-1, out.nrhs) if ns else None
+
+
+def clover_twist_dense(parity, a, inverse, vh):
+    """qudaAmdCloverTwistDense: the dense site matrices A + i a s (s = +1 / -1 for the upper / lower chirality) of one parity of the resident
+    fp32 clover field, or their inverses, as complex64 [vh][2][6][6]"""
+    out = np.empty(int(vh) * 2 * 72, dtype=np.float32)
+    lib().qudaAmdCloverTwistDense(int(parity), float(a), int(bool(inverse)), _vp(out))
+    return out.view(np.complex64).reshape(int(vh), 2, 6, 6)
+
+
+def block_fine_apply_site(out, in_same, in_other, parity, s0, a0, k1, a1, tmode=0, a=0.0, inverse=False):
+    """qudaAmdBlockFineApplySite: one parity launch of the multi-right-hand-side fine stencil with the dense site matrices of the output parity
+    on the hop sum (tmode 1) or on in_same (tmode 2), none with tmode 0.  Returns the flag word: bit 0 = XCD plane-tiled work-group order"""
+    return int(lib().qudaAmdBlockFineApplySite(out.h, in_same.h if in_same is not None else None, in_other.h, int(parity), float(s0), float(a0),
+                                               float(k1), float(a1), int(tmode), float(a), int(bool(inverse))))
 
 
 def multi_src_stats():

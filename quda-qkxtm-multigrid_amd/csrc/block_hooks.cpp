@@ -1,7 +1,8 @@
 // block_hooks.cpp — test hooks (quda_amd_ext.h qudaAmdBlock*) onto the multi-right-hand-side path: block fields free of any lattice,
 // namespace blockblas by name, the minimal-residual updates with their sums as inputs, the four pack functions and one parity launch of the
 // multi-right-hand-side fine stencil with its epilogue sums (include/block.h, include/dslash.h).  tests/test_block_kernels_gpu.py compares
-// them with the longdouble references of tests/block_ref.py.
+// them with the longdouble references of tests/block_ref.py.  The same launch with dense clover-twist site matrices, and those matrices
+// themselves: tests/test_fine_stencil_gpu.py against the fp64 reference of tests/fine_stencil_ref.py.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -132,6 +133,49 @@ void qudaAmdBlockFineApply(void *out_, void *in_same_, void *in_other_, void *do
   HIP_CHECK(hipMemcpyAsync(sums, d, (size_t)nval * sizeof(double), hipMemcpyDeviceToHost, computeStream()));
   HIP_CHECK(hipStreamSynchronize(computeStream()));
   HIP_CHECK(hipFree(d));
+}
+
+static const CloverField &denseSource(const char *hook) {
+  if (!cloverPrecise) errorQuda("%s: load a clover field first", hook);
+  if (cloverPrecise->precision != QUDA_SINGLE_PRECISION) errorQuda("%s: the resident clover field must be fp32 (clover_cuda_prec = 4)", hook);
+  return *cloverPrecise;
+}
+static size_t denseFloats(const CloverField &C) { return (size_t)C.geom.Vh * 2 * 72; }
+
+void qudaAmdCloverTwistDense(int parity, double a, int inverse, float *h_out) {
+  const CloverField &C = denseSource(__func__);
+  if (parity != 0 && parity != 1) errorQuda("qudaAmdCloverTwistDense: parity %d", parity);
+  float *d = nullptr;
+  HIP_CHECK(qaMalloc(&d, denseFloats(C) * sizeof(float)));
+  cloverTwistDense(d, C, parity, a, inverse != 0);
+  HIP_CHECK(hipMemcpyAsync(h_out, d, denseFloats(C) * sizeof(float), hipMemcpyDeviceToHost, computeStream()));
+  HIP_CHECK(hipStreamSynchronize(computeStream()));
+  HIP_CHECK(hipFree(d));
+}
+
+int qudaAmdBlockFineApplySite(void *out_, void *in_same_, void *in_other_, int parity, double s0, double a0, double k1, double a1, int tmode, double a, int inverse) {
+  if (!gaugePrecise) errorQuda("load a gauge field first");
+  const GaugeField &U = *gaugePrecise;
+  BlockField &out = blk(out_, __func__, "out"), &other = blk(in_other_, __func__, "in_other");
+  BlockField *same = (BlockField *)in_same_;
+  const int n = out.nrhs, Vh = U.geom.Vh;
+  for (const BlockField *f : {(const BlockField *)&out, (const BlockField *)&other, (const BlockField *)same})
+    if (f && (f->nSites != Vh || f->ncomp != 12 || f->nrhs != n)) errorQuda("qudaAmdBlockFineApplySite: single-parity fields of %d sites x 12 components x %d right-hand sides", Vh, n);
+  if (out.v == other.v || (same && out.v == same->v)) errorQuda("qudaAmdBlockFineApplySite: out must not alias an input");
+  if (tmode < 0 || tmode > 2) errorQuda("qudaAmdBlockFineApplySite: site-matrix mode %d (0 none, 1 on the hop sum, 2 on in_same)", tmode);
+  const BlockGhost gh = blockGhost(U.geom.X, true);
+  if (gh.mask && other.nGhost < gh.nGhost) errorQuda("qudaAmdBlockFineApplySite: in_other has %d ghost panels, %d needed", other.nGhost, gh.nGhost);
+  float *tmat = nullptr;
+  if (tmode) {
+    const CloverField &C = denseSource(__func__);
+    if (C.geom.Vh != Vh) errorQuda("qudaAmdBlockFineApplySite: clover field of %d sites per parity, links of %d", C.geom.Vh, Vh);
+    HIP_CHECK(qaMalloc(&tmat, denseFloats(C) * sizeof(float)));
+    cloverTwistDense(tmat, C, parity, a, inverse != 0);
+  }
+  applyFineBlockParity(out.v, same ? same->v : nullptr, other.v, n, U, parity, s0, a0, k1, a1, tmat, tmode, gh.mask ? other.v + other.elems() : nullptr);
+  HIP_CHECK(hipStreamSynchronize(computeStream()));
+  if (tmat) HIP_CHECK(hipFree(tmat));
+  return fineBlockOrderTiled(U.geom, n) ? 1 : 0;
 }
 
 }  // extern "C"

@@ -53,6 +53,8 @@ static BlockOrder makeBlockOrder(const LatticeGeom &g, int bs) {
   o.dPTt = FastDiv((uint32_t)(o.P * o.tt)); o.dTt = FastDiv((uint32_t)o.tt);
   return o;
 }
+static int fineBlockSitesPerGroup(int nrhs) { return nrhs == 24 ? 8 : 256 / nrhs; }   // SPB of fine_block_kernel
+bool fineBlockOrderTiled(const LatticeGeom &g, int nrhs) { return makeBlockOrder(g, fineBlockSitesPerGroup(nrhs)).tiled != 0; }
 
 struct FineBlockArg {
   float2 *out;             // panels of the output parity
@@ -569,7 +571,7 @@ void applyFineBlockParity(float2 *out, const float2 *in_same, const float2 *in_o
   if (tmat && (tmode != 1 && tmode != 2)) errorQuda("site-matrix mode %d (1: on the hop sum, 2: on the same-parity input)", tmode);
   if (tmat && tmode == 2 && s0 == 0.0) errorQuda("site matrix on the same-parity input, but that input is switched off");
   const LatticeGeom &g = U.geom;
-  const int spb = nrhs == 24 ? 8 : 256 / nrhs, threads = spb * nrhs;
+  const int spb = fineBlockSitesPerGroup(nrhs), threads = spb * nrhs;
   FineBlockArg arg;
   arg.link_bytes = U.link_bytes; arg.g_stride = U.stride;
   arg.Vh = g.Vh; arg.Xh = g.Xh; arg.Y = g.X[1]; arg.Z = g.X[2]; arg.T = g.X[3];

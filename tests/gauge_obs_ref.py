@@ -35,6 +35,16 @@ def flip_time_boundary(U):
     return out
 
 
+def fp32_recon12(U, antiperiodic):
+    """the links as a fp32 12-real device field holds them: rows 0 and 1 rounded to fp32, row 2 = conj(row 0 x row 1) in fp32, with
+    the anti-periodic sign put back on the time links of the last time slice.  U[mu][t, ..., 3, 3]: any site axes behind t"""
+    R = U.astype(np.complex64)
+    R[..., 2, :] = np.conj(np.cross(R[..., 0, :], R[..., 1, :]))
+    if antiperiodic:
+        R[3, -1, ..., 2, :] *= -1
+    return R.astype(np.complex128)
+
+
 def _fwd(A, mu):
     """A(x + mu)"""
     return np.roll(A, -1, axis=3 - mu)

@@ -1,6 +1,6 @@
-"""CPU-side check of the block-field test hooks: the library exports the qudaAmdBlock* entry points tests/test_block_kernels_gpu.py goes
-through, include/quda_amd_ext.h declares them, and the binding lists and wraps them (no GPU needed: dlopen + dlsym).  Every operation the
-reference of tests/block_ref.py knows is dispatched by name in csrc/block_hooks.cpp, named in the header's list of the dispatcher, declared
+"""CPU-side check of the block-field test hooks: the library exports the qudaAmdBlock* entry points tests/test_block_kernels_gpu.py and
+tests/test_fine_stencil_gpu.py go through (with qudaAmdCloverTwistDense), include/quda_amd_ext.h declares them, and the binding lists and
+wraps them (no GPU needed: dlopen + dlsym).  Every operation the reference of tests/block_ref.py knows is dispatched by name in csrc/block_hooks.cpp, named in the header's list of the dispatcher, declared
 in namespace blockblas of include/block.h, and has its operands mapped to slots by the binding."""
 import importlib
 import os
@@ -13,7 +13,7 @@ qa = importlib.import_module("quda-qkxtm-multigrid_amd")
 
 EXT_H = ["qudaAmdBlockFieldCreate", "qudaAmdBlockFieldDestroy", "qudaAmdBlockFieldLoad", "qudaAmdBlockFieldSave", "qudaAmdBlockBlasApply",
          "qudaAmdBlockMrUpdate", "qudaAmdBlockPack", "qudaAmdBlockUnpack", "qudaAmdBlockPackParity", "qudaAmdBlockUnpackParity",
-         "qudaAmdBlockGhostPanels", "qudaAmdBlockFineApply"]
+         "qudaAmdBlockGhostPanels", "qudaAmdBlockFineApply", "qudaAmdCloverTwistDense", "qudaAmdBlockFineApplySite"]
 
 
 def test_library_exports_the_block_hooks():
@@ -32,7 +32,7 @@ def test_header_declares_them_and_the_binding_lists_them():
 
 def test_binding_has_the_wrappers():
     for name in ("BlockField", "block_blas_apply", "block_mr_update", "block_pack", "block_unpack", "block_pack_parity", "block_unpack_parity",
-                 "block_ghost_panels", "block_fine_apply"):
+                 "block_ghost_panels", "block_fine_apply", "clover_twist_dense", "block_fine_apply_site"):
         assert callable(getattr(qa, name)), name
 
 

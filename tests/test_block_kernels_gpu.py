@@ -30,6 +30,9 @@ Function -> test:
   blockPackParity, blockUnpackParity (block_fine_pack_kernel modes 0, 1, 2)      test_parity_pack
   blockPack, blockUnpack (block_pack_kernel<*, 4>, pair-major branch)            test_full_field_pack
   FineBlockDots modes 1, 2, 3, fine_block_dots_reduce / _finish, fineBlockDotsFinish / FinishDev      test_epilogue_sums
+  applyFineBlockParity: `out` of fine_block_kernel<4..32, 0 / 1 / 2> element-wise (general form, site-matrix modes 1 and 2, 12-real links,
+        tail work-group, plane-tiled order, ghost faces), cloverTwistDense (clover_twist_dense_kernel)
+                                                                                 tests/test_fine_stencil_gpu.py (reference: tests/fine_stencil_ref.py)
   block_pack_kernel<*, 2> (coarse levels), blockExchangeGhost, applyCoarseBlock: pinned through the operator tests against the oracle
   (tests/test_mg_gpu.py); the recurrences of blockBiCGstabNull: through the solver tests.  Not covered here, by decision."""
 import importlib

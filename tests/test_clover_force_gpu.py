@@ -57,16 +57,6 @@ def qa():
     mod.end()
 
 
-def fp32_recon12(U, antiperiodic):
-    """the links as a fp32 12-real device field holds them: rows 0 and 1 rounded to fp32, row 2 = conj(row 0 x row 1) in fp32, with
-    the anti-periodic sign put back on the time links of the last time slice"""
-    R = U.astype(np.complex64)
-    R[..., 2, :] = np.conj(np.cross(R[..., 0, :], R[..., 1, :]))
-    if antiperiodic:
-        R[3, -1, ..., 2, :] *= -1
-    return R.astype(np.complex128)
-
-
 @pytest.fixture(scope="module")
 def cases(oracle):
     """per lattice: hot links with the anti-periodic sign, a momentum, a random complex tensor field, three pairs of random full fields,
@@ -84,7 +74,7 @@ def cases(oracle):
              "xs": rng.standard_normal((3, V * 24)), "ys": rng.standard_normal((3, V * 24)), "A": cf.clover_matrix(U, CSW)}
         c["acc"] = cf.deriv_force(U, A0, T, DERIV_COEFF)
         c["over"] = cf.deriv_force(U, np.zeros_like(A0), T, DERIV_COEFF)
-        c["fp32"] = np.max(np.abs(cf.deriv_force(fp32_recon12(U, True), A0, T, DERIV_COEFF) - c["acc"]))
+        c["fp32"] = np.max(np.abs(cf.deriv_force(ob.fp32_recon12(U, True), A0, T, DERIV_COEFF) - c["acc"]))
         c["S"] = [cf.sigma_oprod(ff.lex_spinor(oracle, x, X), ff.lex_spinor(oracle, y, X)) for x, y in zip(c["xs"], c["ys"])]
         c["par"] = cf.parity_mask((X[3], X[2], X[1], X[0]))
         out[X] = c

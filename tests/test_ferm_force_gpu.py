@@ -42,16 +42,6 @@ def qa():
     mod.end()
 
 
-def fp32_recon12(U, antiperiodic):
-    """the links as a fp32 12-real device field holds them: rows 0 and 1 rounded to fp32, row 2 = conj(row 0 x row 1) in fp32, with
-    the anti-periodic sign put back on the time links of the last time slice"""
-    R = U.astype(np.complex64)
-    R[..., 2, :] = np.conj(np.cross(R[..., 0, :], R[..., 1, :]))
-    if antiperiodic:
-        R[3, -1, ..., 2, :] *= -1
-    return R.astype(np.complex128)
-
-
 def _flavours(oracle, full, X, nf):
     """a full host field ([even][odd], a doublet [flavour 1][flavour 2] within each parity) -> per flavour psi[t, z, y, x, 4, 3]"""
     h = full.size // 2
@@ -72,7 +62,7 @@ def cases(oracle):
         A0 = md.random_momentum(rng, (4, X[3], X[2], X[1], X[0]))
         c = {"hot": hot, "U": U, "A0": A0, "mom0": md.mom_to_host(oracle, A0, X), "x1": rng.standard_normal((2, V * 12)), "x2": rng.standard_normal((2, V * 24))}
         zero = np.zeros_like(A0)
-        rounded = fp32_recon12(U, True)
+        rounded = ob.fp32_recon12(U, True)
         for nf in (1, 2):
             xs, ys = rng.standard_normal((3, nf * V * 24)), rng.standard_normal((3, nf * V * 24))
             c["xs", nf], c["ys", nf] = xs, ys

@@ -41,16 +41,6 @@ def _dag(a):
     return np.conj(np.swapaxes(a, -1, -2))
 
 
-def fp32_recon12(U, antiperiodic):
-    """the links as a fp32 12-real device field holds them (test_gauge_md_gpu.py, restated): rows 0 and 1 rounded to fp32, row 2 =
-    conj(row 0 x row 1) in fp32, with the anti-periodic sign put back on the time links of the last time slice"""
-    R = U.astype(np.complex64)
-    R[..., 2, :] = np.conj(np.cross(R[..., 0, :], R[..., 1, :]))
-    if antiperiodic:
-        R[3, -1, ..., 2, :] *= -1
-    return R.astype(np.complex128)
-
-
 def _g_lex(oracle, G, X):
     lex = oracle.eo_to_lex(np.ascontiguousarray(G, dtype=np.float64).reshape(-1), [int(v) for v in X], 18).reshape(X[3], X[2], X[1], X[0], 3, 3, 2)
     return lex[..., 0] + 1j * lex[..., 1]
@@ -222,7 +212,7 @@ def test_fp32_recon12_resident_links_as_input(qa, oracle, cases, X):
     gp = _gp(qa, X, "hot", cuda_prec=4, recon=12)
     qa.load_gauge(c["hot"], gp)
     held = ob.from_qdp(oracle, qa.save_gauge(_gp(qa, X, "hot")), X)
-    restated = fp32_recon12(c["hot_lex"], True)
+    restated = ob.fp32_recon12(c["hot_lex"], True)
     assert np.array_equal(held[..., :2, :], restated[..., :2, :])
     assert np.max(np.abs(held[..., 2, :] - restated[..., 2, :])) <= 8 * 2.0 ** -24   # a sum of four fp32 products of magnitude <= 1
     got = qa.gauge_fix_ovr(gp, 4, 10, OMEGA, 0.0, 4, 1, transform=True)

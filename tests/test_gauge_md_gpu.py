@@ -41,16 +41,6 @@ def _dag(a):
     return np.conj(np.swapaxes(a, -1, -2))
 
 
-def fp32_recon12(U, antiperiodic):
-    """the links as a fp32 12-real device field holds them: rows 0 and 1 rounded to fp32, row 2 = conj(row 0 x row 1) in fp32, with
-    the anti-periodic sign put back on the time links of the last time slice"""
-    R = U.astype(np.complex64)
-    R[..., 2, :] = np.conj(np.cross(R[..., 0, :], R[..., 1, :]))
-    if antiperiodic:
-        R[3, -1, ..., 2, :] *= -1
-    return R.astype(np.complex128)
-
-
 @pytest.fixture(scope="module")
 def cases(oracle):
     """per lattice: host arrays, momenta and references, computed once and never modified"""
@@ -70,7 +60,7 @@ def cases(oracle):
                 c[kind, name, "acc"] = md.force(U, A0, paths, coeff, EB3)
                 c[kind, name, "over"] = md.force(U, zero, paths, coeff, EB3)
         for name, (paths, coeff) in TABLES.items():
-            rounded = md.force(fp32_recon12(c["hot_lex"], True), A0, paths, coeff, EB3)
+            rounded = md.force(ob.fp32_recon12(c["hot_lex"], True), A0, paths, coeff, EB3)
             c["fp32", name] = np.max(np.abs(rounded - c["hot", name, "acc"]))
         out[X] = c
     return out
@@ -132,7 +122,7 @@ def test_force_host_links_boundaries_and_transport(qa, oracle, cases, X):
         # fp32 12-real links loaded from the host with the sign: the sign goes back on the rebuilt third row
         gp12 = qa.gauge_param(X, cuda_prec=4, recon=12, t_boundary=qa.QUDA_ANTI_PERIODIC_T)
         got = qa.gauge_force(gp12, paths, coeff, EB3, gauge=flipped, mom=c["mom0"])
-        assert np.max(np.abs(_mom(oracle, got, X) - want)) <= 4.0 * np.max(np.abs(md.force(fp32_recon12(ob.flip_time_boundary(c["warm_lex"]), True), c["A0"], paths, coeff, EB3) - want))
+        assert np.max(np.abs(_mom(oracle, got, X) - want)) <= 4.0 * np.max(np.abs(md.force(ob.fp32_recon12(ob.flip_time_boundary(c["warm_lex"]), True), c["A0"], paths, coeff, EB3) - want))
         # the transport formulation on one rank against the direct kernel
         os.environ["QUDA_AMD_GAUGE_FORCE_TRANSPORT"] = "1"
         try:
