@@ -127,18 +127,24 @@ def fold_antiperiodic(gauge, X):
 
 
 # ---- the hop sum ----
-def hop_terms(links, X, parity, psi, absolute=False):
-    """sum of the 8 hops onto `parity` of psi[rhs][Vh][4][3] (complex, other parity) in numpy; absolute: its term sum (container |Re| + i |Im|)"""
+def hop_terms(links, X, parity, psi, absolute=False, blocks=None, dagger=False):
+    """sum of the 8 hops onto `parity` of psi[rhs][Vh][4][3] (complex, other parity) in numpy; absolute: its term sum (container |Re| + i |Im|).
+    blocks: complex [2][8][Vh][3][3], the eight matrices of every site as the device stores them (block 2 mu + 1 already the daggered link of
+    x - mu, tests/stored_ref.py) instead of `links`; dagger: the hops of D^dagger = g5 D g5 (the projectors 1 -+ gamma_mu exchanged)"""
     vh = int(np.prod(X)) // 2
-    u = np.asarray(links, dtype=np.float64).reshape(4, 2, vh, 3, 3, 2)
-    u = u[..., 0] + 1j * u[..., 1]
+    if blocks is None:
+        u = np.asarray(links, dtype=np.float64).reshape(4, 2, vh, 3, 3, 2)
+        u = u[..., 0] + 1j * u[..., 1]
     nb = neighbours(X, parity)
     if absolute:
         psi = _abs(psi)
     out = np.zeros(psi.shape, dtype=np.complex128)
     for d in range(8):
-        m = u[d // 2, parity] if d % 2 == 0 else u[d // 2, 1 - parity][nb[d]].conj().transpose(0, 2, 1)
-        p = PROJECTORS[d]
+        if blocks is not None:
+            m = blocks[parity][d]
+        else:
+            m = u[d // 2, parity] if d % 2 == 0 else u[d // 2, 1 - parity][nb[d]].conj().transpose(0, 2, 1)
+        p = PROJECTORS[d ^ 1] if dagger else PROJECTORS[d]
         if absolute:
             m, p = _abs(m), _abs(p)
         out += _mul("xab,nxsb->nxsa", m, _mul("st,nxtb->nxsb", p, psi[:, nb[d]], absolute), absolute)
