@@ -585,7 +585,7 @@ void applyCoarseBlock(BlockField &out, BlockField &in, const CoarseGauge &G, int
   QA_CASE(48, 24) QA_CASE(48, 8) QA_CASE(48, 16) QA_CASE(48, 32)
   QA_CASE(16, 8) QA_CASE(16, 16) QA_CASE(16, 24) QA_CASE(16, 32)
   QA_CASE(32, 8) QA_CASE(32, 16) QA_CASE(32, 24) QA_CASE(32, 32)
-  QA_CASE(64, 8) QA_CASE(64, 16) QA_CASE(64, 24)
+  QA_CASE(64, 8) QA_CASE(64, 16) QA_CASE(64, 24) QA_CASE(64, 32)
 #undef QA_CASE
   errorQuda("block coarse operator: no kernel for n = %d, nrhs = %d", G.n, in.nrhs);
 }

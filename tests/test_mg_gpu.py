@@ -308,13 +308,14 @@ def test_transfer_kernels_on_other_aggregate_shapes(qa, oracle, X, bs, nvec):
 
 
 @pytest.mark.parametrize("mask", [0, 15, 9], ids=["unpartitioned", "self-neighbour-xyzt", "self-neighbour-xt"])
-@pytest.mark.parametrize("nvec,nrhs_list", [(8, (8, 16, 24, 32)), (24, (24, 8))], ids=["n16", "n48"])
+@pytest.mark.parametrize("nvec,nrhs_list", [(8, (8, 16, 24, 32)), (24, (24, 8)), (32, (32, 24, 16, 8))], ids=["n16", "n48", "n64"])
 def test_block_coarse_operator_on_mfma(qa, oracle, nvec, nrhs_list, mask):
     """The multi-right-hand-side coarse operator on the matrix cores (csrc/block.hip, v_mfma_f32_16x16x4_f32; reference: the
     multi-source 5th dimension of coarseDslashKernel, lib/dslash_coarse.cu:294-333) against the oracle's restatement of the
     reference's CPU coarse operator (lib/dslash_coarse.cu:50-290) applied to every right-hand side separately, with the device's
     own links, and against the single-vector device kernel.  fp32 MFMA is exact fp32 arithmetic: same 2e-5 bar as the
-    single-vector kernel.  n = 2 Nvec = 16 and the production 48 x 24 shape.
+    single-vector kernel.  n = 2 Nvec = 16, the production 48 x 24 shape, and n = 64 with every batch size (the lockstep set-up of a level
+    with 32 vectors below a level with 32 runs the 64 x 32 kernel).
     mask != 0: the dimensions in the mask are grid-decomposed with the process as its own neighbour — the panels
     of the face sites travel through the pack kernel and the exchange into the ghost zone behind the field and the MFMA kernel reaches
     them through the neighbour table (reference: ghost of the multi-source coarse field, lib/dslash_coarse.cu:68-137); the result must
