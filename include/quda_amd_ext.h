@@ -452,6 +452,15 @@ void qudaAmdSetLoopOutput(int enable);
 /* seconds of the last loop contraction on this rank (device events): phi, stencil (or the unfused chain), projection, all of it */
 void qudaAmdLoopLastTimings(double secs[4]);
 
+/* ---- the momentum projection that the two-point, loop and three-point contractions share (csrc/momproj.hip) ---- */
+/* test hook: h_acc[nblk][Lt][Nm][16][re,im] (host, in and out) += the projection of h_cs[nblk][nt * Vs][16][re,im] (host), Vs = X[0] X[1] X[2],
+   x fastest, for the local slices [t0, t0 + nt): uploads both, runs momentumProject once, downloads h_acc.  moms[Nm][3] (host), X the
+   local spatial extents, gx the global coordinate of the local origin (of any sign), L the global extents:
+     h_acc[k][t0 + tl][m][e] += sum_s exp(-2 pi i sum_d moms[m][d] (x_d(s) + gx[d]) / L[d]) h_cs[k][tl * Vs + s][e]
+   in the fixed summation order stated at momentumProject (csrc/qkxtm_internal.h).  Needs initQuda, no resident field. */
+void qudaAmdMomentumProject(double *h_acc, const double *h_cs, int nblk, int t0, int nt, int Lt, const int *moms, int Nm,
+                            const int X[3], const int gx[3], const int L[3]);
+
 /* ---- exact deflation of the quark loops (reference QKXTM_Deflation_Kepler, lib/qudaQKXTM_Deflation_Kepler.cpp; ARPACK is replaced by a
  * thick-restart Lanczos process on the device) ----
  * A = M^dag M of the FULL (not even-odd) twisted-mass or twisted-clover operator made from `param` (dslash_type, kappa, mu,

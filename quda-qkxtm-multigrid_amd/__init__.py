@@ -124,7 +124,7 @@ EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLo
                  "qudaAmdMultigridSetHalfStorage", "qudaAmdMultigridGetNullVector", "qudaAmdMultigridGetV", "qudaAmdMultigridGetCoarseLinks", "qudaAmdMultigridApply", "qudaAmdMultigridApplyTransfer", "qudaAmdMultigridApplyBlock",
                  "qudaAmdMultigridTimeApply", "qudaAmdMultigridTimeTransfer", "qudaAmdSetExitLine", "qudaAmdDiracPrepare", "qudaAmdDiracReconstruct", "qudaAmdSpinorRawInfo", "qudaAmdGaugeRawInfo", "qudaAmdCloverRawInfo", "qudaAmdRawDeviceCopy",
                  "qudaAmdSetSolutionSink", "qudaAmdCommStats", "qudaAmdDescribeHaloError", "qudaAmdMultigridOrthoFallbackBlocks", "qudaAmdProfileMarker", "qudaAmdAccountStart", "qudaAmdAccountDump", "qudaAmdWriteSpinorFields", "qudaAmdReadSpinorFields", "qudaAmdMultigridRefine", "qudaAmdMultigridSetFused", "qudaAmdMultigridFusedStats", "qudaAmdMultiSrcStats", "qudaAmdTwopMomenta", "qudaAmdTwopTimeExtent", "qudaAmdContractTwop", "qudaAmdSetTwopOutput",
-                 "qudaAmdLoopMomenta", "qudaAmdContractLoop", "qudaAmdSetLoopOutput", "qudaAmdLoopLastTimings",
+                 "qudaAmdLoopMomenta", "qudaAmdContractLoop", "qudaAmdSetLoopOutput", "qudaAmdLoopLastTimings", "qudaAmdMomentumProject",
                  "qudaAmdNewDeflation", "qudaAmdDestroyDeflation", "qudaAmdDeflationInfo", "qudaAmdDeflationTimings", "qudaAmdDeflationGetVector", "qudaAmdDeflationProject",
                  "qudaAmdDeflationExactLoop", "qudaAmdHostSymmetricEig", "qudaAmdRotateBasis", "qudaAmdBlockDot", "qudaAmdBlockAxpy", "qudaAmdLastEigenvalues",
                  "qudaAmdBlasAxpyCGNorm", "qudaAmdBlasAxpyZpbx", "qudaAmdBlasTripleCGReduction", "qudaAmdBlasAxpyReDot", "qudaAmdBlasMultiShiftUpdate",
@@ -402,6 +402,8 @@ def lib():
         L.qudaAmdSetLoopOutput.restype = None
         L.qudaAmdLoopLastTimings.argtypes = [C.POINTER(_d)]
         L.qudaAmdLoopLastTimings.restype = None
+        L.qudaAmdMomentumProject.argtypes = [_p, _p, _i, _i, _i, _i, C.POINTER(_i), _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]
+        L.qudaAmdMomentumProject.restype = None
         L.qudaAmdNewDeflation.argtypes = [C.POINTER(QudaInvertParam), C.POINTER(QudaAmdEigParam)]
         L.qudaAmdNewDeflation.restype = _p
         L.qudaAmdDestroyDeflation.argtypes = [_p]
@@ -1150,6 +1152,27 @@ def contract_loop(solution, ip, Q_sq, L):
     T = lib().qudaAmdTwopTimeExtent()
     out = np.zeros((18, T, nm, 16, 2))
     lib().qudaAmdContractLoop(_vp(out), _vp(sol), C.byref(ip), int(Q_sq))
+    return out[..., 0] + 1j * out[..., 1]
+
+
+def momentum_project(acc, cs, t0, moms, X, gx=(0, 0, 0), L=None):
+    """qudaAmdMomentumProject (test hook onto the projection that all contractions share): acc (nblk, Lt, Nm, 16) complex, cs
+    (nblk, nt * Vs, 16) complex with Vs = X[0] X[1] X[2] sites per slice, x fastest; returns acc + the projection of cs onto moms (Nm, 3)
+    written into the slices [t0, t0 + nt).  X the local extents, gx the global coordinate of the local origin, L the global extents
+    (None: X).  Needs init(), no resident field"""
+    acc, cs = np.asarray(acc, dtype=np.complex128), np.asarray(cs, dtype=np.complex128)
+    m = np.ascontiguousarray(moms, dtype=np.int32).reshape(-1, 3)
+    nblk, Lt, Nm = acc.shape[:3]
+    Vs = int(X[0]) * int(X[1]) * int(X[2])
+    if acc.shape != (nblk, Lt, len(m), 16) or cs.ndim != 3 or cs.shape[0] != nblk or cs.shape[2] != 16 or cs.shape[1] % Vs:
+        raise ValueError("acc must be (nblk, Lt, Nm, 16) and cs (nblk, nt * Vs, 16)")
+    nt = cs.shape[1] // Vs
+    if nt < 1 or t0 < 0 or t0 + nt > Lt:
+        raise ValueError("slices [%d, %d) of %d" % (t0, t0 + nt, Lt))
+    out = np.ascontiguousarray(np.stack([acc.real, acc.imag], axis=-1))
+    h_cs = np.ascontiguousarray(np.stack([cs.real, cs.imag], axis=-1))
+    ext = [(_i * 3)(*[int(v) for v in a]) for a in (X, gx, X if L is None else L)]
+    lib().qudaAmdMomentumProject(_vp(out), _vp(h_cs), nblk, int(t0), nt, Lt, m.ctypes.data_as(C.POINTER(_i)), Nm, *ext)
     return out[..., 0] + 1j * out[..., 1]
 
 

@@ -191,3 +191,29 @@ int copyMomenta(const std::vector<int> &m, int *moms, int max_moms, const char *
 }
 
 }  // namespace quda
+
+using namespace quda;
+
+extern "C" {
+
+void qudaAmdMomentumProject(double *h_acc, const double *h_cs, int nblk, int t0, int nt, int Lt, const int *moms, int Nm, const int X[3], const int gx[3], const int L[3]) {
+  if (!h_acc || !h_cs || !moms || !X || !gx || !L) errorQuda("qudaAmdMomentumProject: NULL argument");
+  if (nblk < 1 || nt < 1 || Lt < 1 || Nm < 1 || X[0] < 1 || X[1] < 1 || X[2] < 1 || L[0] < 1 || L[1] < 1 || L[2] < 1) errorQuda("qudaAmdMomentumProject: bad extents");
+  const size_t accBytes = (size_t)nblk * Lt * Nm * momproj::NGM * sizeof(double2);
+  const size_t csBytes = (size_t)nblk * nt * X[0] * X[1] * X[2] * momproj::NGM * sizeof(double2);
+  hipStream_t st = computeStream();
+  double2 *acc = nullptr, *cs = nullptr;
+  int *d_moms = nullptr;
+  HIP_CHECK(hipMalloc(&acc, accBytes));
+  HIP_CHECK(hipMalloc(&cs, csBytes));
+  HIP_CHECK(hipMalloc(&d_moms, (size_t)Nm * 3 * sizeof(int)));
+  HIP_CHECK(hipMemcpyAsync(acc, h_acc, accBytes, hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(cs, h_cs, csBytes, hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(d_moms, moms, (size_t)Nm * 3 * sizeof(int), hipMemcpyHostToDevice, st));
+  momentumProject(acc, cs, nblk, t0, nt, Lt, d_moms, Nm, X, gx, L);
+  HIP_CHECK(hipMemcpyAsync(h_acc, acc, accBytes, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  (void)hipFree(acc); (void)hipFree(cs); (void)hipFree(d_moms);
+}
+
+}  // extern "C"

@@ -222,3 +222,29 @@ def test_unfused_chain_matches(qa, oracle, X, tmp_path):
     want = numpy_loops(x, _wilson(oracle, gauge, None, x, X), _lex_links(oracle, gauge, X), X, qa.loop_momenta(X[:3], QSQ))
     assert _block_err(chain, want) < 1e-12
     assert _block_err(chain, fused) < 1e-12
+
+
+def test_chunked_driver_equals_unchunked_bit_for_bit(qa, oracle, tmp_path):
+    """QUDA_AMD_LOOP_TCHUNK=3 in a child process: 8 time slices staged and projected in chunks of 3, 3 and 2, so the shared projection
+    runs with t0 > 0 and nt > 1 together, as the production loops do once their staged blocks pass 2 GiB.  The summation order within
+    a slice does not depend on the chunking, so the result equals the parent's single chunk in every bit"""
+    X = LATTICES[1]
+    gauge, _, x = _fields(oracle, X, True)
+    _load(qa, gauge, X, True)
+    whole = qa.contract_loop(x, _ip(qa, False), QSQ, X[:3])
+    inp, out, script = tmp_path / "in.npz", tmp_path / "out.npy", tmp_path / "child.py"
+    np.savez(str(inp), X=np.array(X), gauge=gauge, x=x, kappa=KAPPA, qsq=QSQ)
+    script.write_text(_CHILD % (ROOT, os.path.join(ROOT, "tests")))
+    r = subprocess.run([sys.executable, str(script), str(inp), str(out)], capture_output=True, text=True, timeout=300, env=dict(os.environ, QUDA_AMD_LOOP_TCHUNK="3"))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    chunked = np.load(str(out))
+    assert chunked.shape == whole.shape and np.array_equal(chunked.view(np.float64).view(np.uint64), whole.view(np.float64).view(np.uint64))
+    want = numpy_loops(x, _wilson(oracle, gauge, None, x, X), _lex_links(oracle, gauge, X), X, qa.loop_momenta(X[:3], QSQ))
+    assert _block_err(chunked, want) < 1e-12
+
+
+def test_twisted_mass_matches_numpy_where_a_share_holds_many_sites(qa, oracle):
+    """12 x 10 x 14 x 4: a time slice has 1680 sites, so the 64 shares of the shared projection hold 26 or 27 and their 16 site lanes
+    make a second trip, fed by the fused staging kernel.  Same restatement, same bound; the projection itself is held to a per-element
+    bound in tests/test_momproj_gpu.py"""
+    test_twisted_mass_matches_numpy(qa, oracle, (12, 10, 14, 4), True)

@@ -86,23 +86,43 @@ def _baryons_site(U, D):
     return np.stack(out + deltas_iso1 + deltas_iso12, axis=1)   # (V, 10, 4, 4)
 
 
-def numpy_twop(prop_up, prop_dn, X, src, moms, smear=None):
+def _rotated(prop_up, prop_dn, X, smear):
     V = int(np.prod(X))
     if smear is not None:
         prop_up = np.stack([smear(c) for c in prop_up])
         prop_dn = np.stack([smear(c) for c in prop_dn])
-    U = _rotate(_to_tensor(prop_up, V), +1)
-    D = _rotate(_to_tensor(prop_dn, V), -1)
+    return _rotate(_to_tensor(prop_up, V), +1), _rotate(_to_tensor(prop_dn, V), -1)
+
+
+def _phases(X, src, moms):
+    z, y, x = np.meshgrid(np.arange(X[2]), np.arange(X[1]), np.arange(X[0]), indexing="ij")
+    return np.stack([np.exp(-2j * np.pi * (n[0] * (x - src[0]) / X[0] + n[1] * (y - src[1]) / X[1] + n[2] * (z - src[2]) / X[2])) for n in moms])   # (Nm, Z, Y, X)
+
+
+def numpy_mesons(prop_up, prop_dn, X, src, moms, smear=None):
+    """the meson half of numpy_twop: (T, Nm, 2, 10), time relative to the source"""
+    U, D = _rotated(prop_up, prop_dn, X, smear)
     mes = np.stack([_mesons_site(U), _mesons_site(D)], axis=1)                 # (V, 2, 10)
+    T, Z, Y, Xx = X[3], X[2], X[1], X[0]
+    mes = np.einsum("mzyx,tzyxfc->tmfc", _phases(X, src, moms), mes.reshape(T, Z, Y, Xx, 2, 10))
+    return mes[(np.arange(T) + src[3]) % T]
+
+
+def numpy_baryons(prop_up, prop_dn, X, src, moms, smear=None):
+    """the baryon half: (T, Nm, 2, 10, 4, 4), time relative to the source, with the wrap sign"""
+    U, D = _rotated(prop_up, prop_dn, X, smear)
     bar = np.stack([_baryons_site(U, D), _baryons_site(D, U)], axis=1)         # (V, 2, 10, 4, 4)
     T, Z, Y, Xx = X[3], X[2], X[1], X[0]
-    z, y, x = np.meshgrid(np.arange(Z), np.arange(Y), np.arange(Xx), indexing="ij")
-    ph = np.stack([np.exp(-2j * np.pi * (n[0] * (x - src[0]) / Xx + n[1] * (y - src[1]) / Y + n[2] * (z - src[2]) / Z)) for n in moms])   # (Nm, Z, Y, X)
-    mes = np.einsum("mzyx,tzyxfc->tmfc", ph, mes.reshape(T, Z, Y, Xx, 2, 10))
-    bar = np.einsum("mzyx,tzyxfcgh->tmfcgh", ph, bar.reshape(T, Z, Y, Xx, 2, 10, 4, 4))
+    bar = np.einsum("mzyx,tzyxfcgh->tmfcgh", _phases(X, src, moms), bar.reshape(T, Z, Y, Xx, 2, 10, 4, 4))
     ts = (np.arange(T) + src[3]) % T
     sign = np.where(np.arange(T) + src[3] >= T, -1.0, 1.0)
-    return mes[ts], bar[ts] * sign[:, None, None, None, None, None]
+    return bar[ts] * sign[:, None, None, None, None, None]
+
+
+def numpy_twop(prop_up, prop_dn, X, src, moms, smear=None):
+    if smear is not None:      # once for both halves
+        prop_up, prop_dn, smear = np.stack([smear(c) for c in prop_up]), np.stack([smear(c) for c in prop_dn]), None
+    return numpy_mesons(prop_up, prop_dn, X, src, moms, smear), numpy_baryons(prop_up, prop_dn, X, src, moms, smear)
 
 
 def _blockwise_err(got, want, axes):
@@ -155,6 +175,25 @@ def test_contractions_match_numpy_momentum_chunks(qa, oracle, Q, nmoms):
     n +- L), which the restatement handles by formula.  Same restatement, same bound."""
     assert len(_momenta(Q)) == nmoms
     test_contractions_match_numpy(qa, oracle, (6, 4, 2, 8), (5, 1, 1, 6), 0, 0, Q)
+
+
+def test_mesons_match_numpy_where_a_share_holds_many_sites(qa, oracle):
+    """12 x 10 x 14 x 2: a time slice has 1680 sites, so the 64 shares of the shared projection hold 26 or 27 and their 16 site lanes
+    make a second trip, staged by the meson kernel one slice at a time.  Mesons only: the numpy restatement of the baryons takes
+    minutes at this volume.  Same measure and bound as above; the projection itself is held to a per-element bound in
+    tests/test_momproj_gpu.py"""
+    X, src, Q = (12, 10, 14, 2), (7, 3, 9, 1), 3
+    gauge, _, _ = oracle.make_fields(list(X), seed=5, antiperiodic_t=False, clover=False)
+    qa.load_gauge(gauge, qa.gauge_param(X, t_boundary=qa.QUDA_PERIODIC_T))
+    V = int(np.prod(X))
+    rng = np.random.default_rng(23)
+    up, dn = rng.standard_normal((12, V * 24)), rng.standard_normal((12, V * 24))
+    mes, _ = qa.contract_twop(up, dn, None, src, Q, 0, 0.0)
+    moms = _momenta(Q)
+    want = numpy_mesons(up, dn, X, src, moms)
+    assert mes.shape == want.shape == (X[3], len(moms), 2, 10)
+    em = _blockwise_err(mes, want, (2, 3))
+    assert em < 1e-12, em
 
 
 def test_pseudoscalar_on_solved_propagators(qa, oracle):
