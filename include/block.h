@@ -80,7 +80,7 @@ bool blockCoarseSupported(const CoarseGauge &G, int nrhs);
 // parity >= 0: only the output sites of that parity are computed (and written) — half the link traffic where the caller wants one parity anyway
 void applyCoarseBlock(BlockField &out, BlockField &in, const CoarseGauge &G, int parity = -1);
 
-// One piece of the even-odd preconditioned coarse system as the block-field cycle of block_solver.cpp computes it (BlockCoarseCycle::matpc /
+// One piece of the even-odd preconditioned coarse system as the block-field cycle of block_coarse_cycle.cpp computes it (BlockCoarseCycle::matpc /
 // prepare / reconstruct on a one-level cycle made for the call; Y: links, H: preconditioned links, p: parity of the system), on nrhs full coarse
 // fields.  op 0: out = Mhat in (in on parity p); op 1: out = the preconditioned source of b; op 2: out = x reconstructed from in (parity p) and b.
 // Every work field is preloaded with nonzero words on both parities; returns the nonzero words left in the half of matpc's temporary that its

@@ -40,7 +40,7 @@ struct MGParam : SolverParam {
 };
 
 class CoarseCycle;   // coarse_cycle.h: the cycle below a coarse level as one persistent kernel
-struct MGBlockState;  // block_solver.cpp: per-source smoothers / work fields and the block-field cycle below the fine level (invertMultiSrcQuda)
+struct MGBlockState;  // block_cycle.h: per-source smoothers / work fields and the block-field cycle below the fine level (invertMultiSrcQuda)
 
 class MG : public Solver {
   MGParam &mgp;
@@ -97,10 +97,9 @@ class MG : public Solver {
   bool smootherIsPC() const { return pcSmooth; }
   const SolverParam *preSmootherParam() const { return param_presmooth; }
   const CoarseCycle *fusedCycle() const { return fused; }
-  void dropFusedCycle();
   // x_i = K b_i for several sources at once (level 0 only): smoothing / R / P per source, everything below the fine level on block fields through
-  // the multi-right-hand-side MFMA coarse operator (block_solver.cpp).  false: this hierarchy does not qualify, the caller applies K per source.
-  // active[i] = 0: source i is left alone.  blockRelease frees the per-source state.
+  // the multi-right-hand-side MFMA coarse operator (block_mg_cycle.cpp).  false: this hierarchy does not qualify, the caller applies K per source.
+  // active[i] = 0: source i is left alone.
   bool cycleBlock(std::vector<ColorSpinorField *> &x, std::vector<ColorSpinorField *> &b, const std::vector<char> &active);
   // out_i = Mhat x_i for the solutions x_i of the LAST cycleBlock on single-parity fields, while they are still on the block fields of the fine
   // smoother (two multi-right-hand-side stencil launches per group instead of two stencils per source): the outer solver's `A p_k`.  pc: the
@@ -110,7 +109,7 @@ class MG : public Solver {
   bool blockImageFull(std::vector<ColorSpinorField *> &out, std::vector<ColorSpinorField *> &b, const Dirac &full, const std::vector<char> &active);
   void blockWantImage(int nsrc, bool on);   // the next cycleBlock (of nsrc sources) keeps what blockApplyLast needs to answer from the post-smoother's residual
   bool blockApplyLast(std::vector<ColorSpinorField *> &out, const Dirac &pc, const std::vector<char> &active);
-  void blockRelease();   // hierarchy contents changed (half-precision mirrors switched on): rebuild or abandon at the next cycle
+  void blockRelease();   // frees the per-source state; called by ~MG and by blockPrepare when the number of sources changes
   DiracMatrix &residualMatrix() const { return mgp.matResidual; }
 };
 

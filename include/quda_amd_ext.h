@@ -215,7 +215,7 @@ void qudaAmdMultigridApplyTransfer(void *mg_instance, int level, int op, int par
  *   nrhs full sources b, the preconditioned source comes back on `parity`; op 2: reconstruct, h_in nrhs solved parity fields x then nrhs full b.
  *   h_out: nrhs FULL fields in every case (what the routine leaves on the other parity is part of the answer).  impl 0: DiracCoarsePC, nrhs = 1
  *   (the level's smoother operator where its matpc fits, else one made for the call that shares the links).  impl 1: BlockCoarseCycle::matpc /
- *   prepare / reconstruct of csrc/block_solver.cpp on the MFMA kernel, nrhs in {8, 16, 24}, every work field preloaded with nonzero words on both
+ *   prepare / reconstruct of csrc/block_coarse_cycle.cpp on the MFMA kernel, nrhs in {8, 16, 24}, every work field preloaded with nonzero words on both
  *   parities.  Returns (impl 1) the nonzero words left in the half of matpc's temporary that its second application multiplies with Xinv,
  *   else 0.
  * qudaAmdCoarseInvertSites: coarse_invert_kernel and coarse_hat_kernel on matrices of the caller (no hierarchy): h_X[site][row][col], h_H[site]
@@ -496,6 +496,10 @@ void qudaAmdDeflationExactLoop(void *defl, int n, double *out, int Q_sq);
 /* dense real symmetric eigenproblem on the host (cyclic Jacobi; what the eigensolver diagonalises its projected matrix with):
  * a[n][n] row-major (the upper triangle is read), w[n] ascending, q[n][n] row-major with COLUMN i the eigenvector of w[i] */
 void qudaAmdHostSymmetricEig(int n, const double *a, double *w, double *q);
+/* the back substitution of the restarted GCRs (csrc/gcr_core.h; host only): delta_a = (alpha_a - sum_{a < j < k} beta_aj delta_j) / gamma_a for
+ * a = k-1 .. 0, and delta_a = 0 where gamma_a == 0.  Complex values as interleaved doubles: alpha[nK], beta[nK][nK] row-major (leading
+ * dimension nK, the strict upper triangle is read), gamma[nK] real, delta[k]; k <= nK */
+void qudaAmdGcrBackSubstitute(int k, int nK, const double *alpha, const double *beta, const double *gamma, double *delta);
 /* test hooks onto the eigensolver's kernels; h_V: m <= 256 vectors of V * 24 doubles (V = X[0] X[1] X[2] X[3], even) seen as V * 12
  * complex numbers or V * 24 real rows; no resident field is needed.
  * qudaAmdRotateBasis: V[:, 0..k) <- V[:, 0..m) Q in place, Q real m x k row-major, the columns k .. m-1 are left alone (fp64 matrix cores);

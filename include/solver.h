@@ -5,12 +5,19 @@
 // definite operators (M^dag M): lib/inv_cg_quda.cpp:40-360, lib/inv_multi_cg_quda.cpp:115-527.
 #pragma once
 
+#include <memory>
 #include <vector>
 
 #include "blas.h"
 #include "dirac.h"
 
 namespace quda {
+
+struct GcrCoeffs;   // csrc/gcr_core.h: alpha, beta, gamma of one Krylov cycle and their back substitution
+
+double wallTime();   // seconds (gettimeofday)
+// a device field of the shape and twist flavour of x in precision prec, cleared or left as allocated
+ColorSpinorField *like(const ColorSpinorField &x, QudaPrecision prec, bool zero);
 
 struct SolverParam {
   QudaInverterType inv_type = QUDA_GCR_INVERTER;
@@ -94,8 +101,7 @@ class GCR : public Solver {
   bool ownK;
   SolverParam Kparam;
   int nKrylov;
-  Complex *alpha, **beta;
-  double *gamma;
+  std::unique_ptr<GcrCoeffs> coeffs;
   bool init;
   ColorSpinorField *rp, *yp, *x_sloppy, *r_sloppy, *p_pre, *r_pre, *rM;
   std::vector<ColorSpinorField *> p, Ap;
@@ -127,5 +133,16 @@ class MultiShiftCG {
 };
 
 void fillInnerSolveParam(SolverParam &inner, const SolverParam &outer);  // reference lib/inv_gcr_quda.cpp:17-50
+
+// One Krylov step of GCR on fields, shared by GCR::operator() and the lockstep multi-source GCR (block_solver.cpp): Ap[k] is orthogonalised
+// against Ap[0 .. k) and normalised, r -= alpha_k Ap[k]; column k of beta, gamma[k] and alpha[k] go into c; returns |r|^2.  The blocked two-sweep
+// form runs where blas::multiSupported allows it and the inferred norm keeps two digits, else the one-direction-at-a-time chain in the form
+// `chain` (the two forms reduce in different kernels, so a caller's results depend on its choice in the last bits).  blockedOk: the
+// measured-norm guard — read before the blocked form is tried, cleared (with Ap[k], gamma, alpha put right) when the measured |Ap_k|^2 is
+// off; the caller sets it again at its restart.  nullptr: no guard, the blocked form is always tried.
+enum class GcrChain { Pipelined, Sequential };   // caxpyDotzy pipeline (reference :103-121) / cDotProduct + caxpy (reference :86-101)
+double gcrKrylovStep(GcrCoeffs &c, std::vector<ColorSpinorField *> &Ap, int k, ColorSpinorField &r, GcrChain chain, bool *blockedOk);
+// x += sum_{a < k} delta_a p_a with delta from c.backSubstitute (reference :125-157)
+void gcrUpdateSolution(ColorSpinorField &x, const GcrCoeffs &c, int k, std::vector<ColorSpinorField *> &p);
 
 }  // namespace quda

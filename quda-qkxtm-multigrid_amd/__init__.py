@@ -126,7 +126,7 @@ EXT_H_SYMBOLS = ["qudaAmdSpinorCreate", "qudaAmdSpinorDestroy", "qudaAmdSpinorLo
                  "qudaAmdSetSolutionSink", "qudaAmdCommStats", "qudaAmdDescribeHaloError", "qudaAmdMultigridOrthoFallbackBlocks", "qudaAmdProfileMarker", "qudaAmdAccountStart", "qudaAmdAccountDump", "qudaAmdWriteSpinorFields", "qudaAmdReadSpinorFields", "qudaAmdMultigridRefine", "qudaAmdMultigridSetFused", "qudaAmdMultigridFusedStats", "qudaAmdMultiSrcStats", "qudaAmdTwopMomenta", "qudaAmdTwopTimeExtent", "qudaAmdContractTwop", "qudaAmdSetTwopOutput",
                  "qudaAmdLoopMomenta", "qudaAmdContractLoop", "qudaAmdSetLoopOutput", "qudaAmdLoopLastTimings", "qudaAmdMomentumProject",
                  "qudaAmdNewDeflation", "qudaAmdDestroyDeflation", "qudaAmdDeflationInfo", "qudaAmdDeflationTimings", "qudaAmdDeflationGetVector", "qudaAmdDeflationProject",
-                 "qudaAmdDeflationExactLoop", "qudaAmdHostSymmetricEig", "qudaAmdRotateBasis", "qudaAmdBlockDot", "qudaAmdBlockAxpy", "qudaAmdLastEigenvalues",
+                 "qudaAmdDeflationExactLoop", "qudaAmdHostSymmetricEig", "qudaAmdGcrBackSubstitute", "qudaAmdRotateBasis", "qudaAmdBlockDot", "qudaAmdBlockAxpy", "qudaAmdLastEigenvalues",
                  "qudaAmdBlasAxpyCGNorm", "qudaAmdBlasAxpyZpbx", "qudaAmdBlasTripleCGReduction", "qudaAmdBlasAxpyReDot", "qudaAmdBlasMultiShiftUpdate",
                  "qudaAmdBlasMultiShiftChunk", "qudaAmdDiracMdagMShift", "qudaAmdTimeMdagM", "qudaAmdTimeCGBlas", "qudaAmdTimeMultiShift",
                  "qudaAmdNdegTwist", "qudaAmdStoutSmear", "qudaAmdQCharge", "qudaAmdSu3ExpIQ",
@@ -420,6 +420,9 @@ def lib():
         L.qudaAmdDeflationExactLoop.restype = None
         L.qudaAmdHostSymmetricEig.argtypes = [_i, _p, _p, _p]
         L.qudaAmdHostSymmetricEig.restype = None
+        if hasattr(L, "qudaAmdGcrBackSubstitute"):   # absent from a build of an earlier commit loaded through QUDA_AMD_LIBRARY
+            L.qudaAmdGcrBackSubstitute.argtypes = [_i, _i, _p, _p, _p, _p]
+            L.qudaAmdGcrBackSubstitute.restype = None
         L.qudaAmdRotateBasis.argtypes = [_p, _i, _i, _p, C.POINTER(_i)]
         L.qudaAmdRotateBasis.restype = None
         L.qudaAmdBlockDot.argtypes = [_p, _p, _i, _p, C.POINTER(_i)]
@@ -1185,6 +1188,20 @@ def host_symmetric_eig(a):
     w, q = np.zeros(n), np.zeros((n, n))
     lib().qudaAmdHostSymmetricEig(n, _vp(a), _vp(w), _vp(q))
     return w, q
+
+
+def gcr_back_substitute(alpha, beta, gamma):
+    """qudaAmdGcrBackSubstitute (host only): delta[k] of the solution update of restarted GCR from alpha[k], gamma[k] and beta[nK][nK]
+    (row-major, the strict upper triangle of its leading k x k block is read), k = len(alpha) <= nK"""
+    alpha = np.ascontiguousarray(alpha, dtype=np.complex128)
+    beta = np.ascontiguousarray(beta, dtype=np.complex128)
+    gamma = np.ascontiguousarray(gamma, dtype=np.float64)
+    k, nK = alpha.shape[0], beta.shape[0]
+    assert beta.shape == (nK, nK) and gamma.shape == (k,) and 0 < k <= nK
+    a, g, delta = np.zeros(nK, dtype=np.complex128), np.ones(nK), np.zeros(k, dtype=np.complex128)
+    a[:k], g[:k] = alpha, gamma
+    lib().qudaAmdGcrBackSubstitute(k, nK, _vp(a), _vp(beta), _vp(g), _vp(delta))
+    return delta
 
 
 class Deflation:

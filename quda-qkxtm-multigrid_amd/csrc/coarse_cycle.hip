@@ -26,6 +26,7 @@
 
 #include "coarse.h"
 #include "device_io.h"
+#include "env.h"
 #include "p2p.h"
 
 namespace quda {
@@ -1115,8 +1116,6 @@ int coarseCycleEnabled() {
   return g_fusedEnabled;
 }
 void coarseCycleSetEnabled(int on) { g_fusedEnabled = on ? 1 : 0; }
-
-static int envInt(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 
 template <int N> static void launchCycle(const CoarseCycle &cc) {
   hipLaunchKernelGGL((coarse_cycle_kernel<N>), dim3(cc.grid), dim3(kThreads), cc.ldsBytes, computeStream(), (const CcArg *)cc.d_arg);

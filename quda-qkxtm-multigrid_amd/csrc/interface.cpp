@@ -36,12 +36,6 @@ static QudaGaugeParam g_gauge_param;
 // host copies kept so sloppy/precondition clover fields and MG setup can be (re)built
 const LatticeGeom &residentGeom() { return g_geom; }
 
-static double wallTime() {
-  timeval t;
-  gettimeofday(&t, nullptr);
-  return t.tv_sec + 1e-6 * t.tv_usec;
-}
-
 GaugeField *residentGauge(int which) {
   GaugeField *g = which == 0 ? gaugePrecise : (which == 1 ? gaugeSloppy : gaugePrecondition);
   if (!g) errorQuda("Gauge field not allocated");

@@ -14,27 +14,10 @@
 //     application to hide communication) and in one sweep for all active shifts, base system included; beta falls back to
 //     r2 / r2_old where (r_new, r_new - r_old) comes out negative, as the single-shift CG does.
 #include <cmath>
-#include <sys/time.h>
 
 #include "solver.h"
 
 namespace quda {
-
-static double now() {
-  timeval t;
-  gettimeofday(&t, nullptr);
-  return t.tv_sec + 1e-6 * t.tv_usec;
-}
-
-static ColorSpinorField *like(const ColorSpinorField &x, QudaPrecision prec, bool zero) {
-  ColorSpinorParam p = x.param();
-  p.location = QUDA_CUDA_FIELD_LOCATION;
-  p.precision = prec;
-  p.create = zero ? QUDA_ZERO_FIELD_CREATE : QUDA_NULL_FIELD_CREATE;
-  ColorSpinorField *f = new ColorSpinorField(p);
-  f->twistFlavor = x.twistFlavor;
-  return f;
-}
 
 static void needL2(const SolverParam &param, const char *name) {
   if (!(param.residual_type & (QUDA_L2_RELATIVE_RESIDUAL | QUDA_L2_ABSOLUTE_RESIDUAL)))
@@ -48,7 +31,7 @@ CG::CG(DiracMatrix &mat_, DiracMatrix &matSloppy_, SolverParam &p) : Solver(p), 
 
 void CG::operator()(ColorSpinorField &x, ColorSpinorField &b) {
   needL2(param, "CG");
-  const double t0 = now();
+  const double t0 = wallTime();
   const double b2 = blas::norm2(b);
   if (b2 == 0) {
     warningQuda("inverting on zero-field source");
@@ -141,7 +124,7 @@ void CG::operator()(ColorSpinorField &x, ColorSpinorField &b) {
   }
   if (mixed) { blas::copy(x, xSloppy); blas::xpy(*yp, x); }
 
-  param.secs += now() - t0;
+  param.secs += wallTime() - t0;
   param.gflops += (blas::flops + mat.flops() + matSloppy.flops()) * 1e-9;
   param.iter += k;
   if (k == param.maxiter) warningQuda("Exceeded maximum iterations %d", param.maxiter);
@@ -183,7 +166,7 @@ void MultiShiftCG::operator()(std::vector<ColorSpinorField *> &x, ColorSpinorFie
   const double *offset = param.offset;
   if (num_offset == 0) return;
   if (num_offset < 0 || num_offset > QUDA_MAX_MULTI_SHIFT || (int)x.size() < num_offset) errorQuda("MultiShiftCG: %d shifts, %zu solution fields", num_offset, x.size());
-  const double t0 = now();
+  const double t0 = wallTime();
   const double b2 = blas::norm2(b);
   if (b2 == 0) {
     warningQuda("inverting on zero-field source");
@@ -308,7 +291,7 @@ void MultiShiftCG::operator()(std::vector<ColorSpinorField *> &x, ColorSpinorFie
     if (mixed) blas::copy(*x[i], *xs[i]);
     if (reliable) blas::xpy(*y[i], *x[i]);
   }
-  param.secs += now() - t0;
+  param.secs += wallTime() - t0;
   param.gflops += (blas::flops + mat.flops() + matSloppy.flops()) * 1e-9;
   param.iter += k;
   if (k == param.maxiter) warningQuda("Exceeded maximum iterations %d", param.maxiter);

@@ -5,22 +5,16 @@
 #include "p2p.h"
 
 #include <cmath>
-#include <sys/time.h>
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 
+#include "env.h"
 #include "interface_internal.h"
 
 namespace quda {
-
-static double now() {
-  timeval t;
-  gettimeofday(&t, nullptr);
-  return t.tv_sec + 1e-6 * t.tv_usec;
-}
 
 MGParam::MGParam(QudaMultigridParam &g, std::vector<ColorSpinorField *> &B_, DiracMatrix &res, DiracMatrix &smooth, int level_, QudaTwistFlavorType flavor)
     : SolverParam(*g.invert_param), mg_global(g), level(level_), Nlevel(g.n_level), spinBlockSize(g.spin_block_size[level_]), Nvec(g.n_vec[level_]),
@@ -41,17 +35,10 @@ MGParam::MGParam(QudaMultigridParam &g, std::vector<ColorSpinorField *> &B_, Dir
 static double g_mgProf[QUDA_MAX_MG_LEVEL][6];
 static long g_mgCalls[QUDA_MAX_MG_LEVEL];
 static int mgProfiling() {
-  static int on = -1;
-  if (on < 0) { const char *e = getenv("QUDA_AMD_MG_PROFILE"); on = e ? atoi(e) : 0; }
+  static const int on = envInt("QUDA_AMD_MG_PROFILE", 0);
   return on;
 }
 void multigridSetHalfStorage(multigrid_solver &mgs, bool on);
-
-static ColorSpinorField *likeField(const ColorSpinorField &x) {
-  ColorSpinorParam p = x.param();
-  p.create = QUDA_ZERO_FIELD_CREATE;
-  return new ColorSpinorField(p);
-}
 
 MG::MG(MGParam &p)
     : Solver(p), mgp(p), transfer(nullptr), presmoother(nullptr), postsmoother(nullptr), coarse_solver(nullptr), param_presmooth(nullptr),
@@ -68,10 +55,10 @@ MG::MG(MGParam &p)
     if (p.vectorsPreset && p.level == 0) {
       // refinement pass: the caller has put the vectors into B
     } else if (p.mg_global.compute_null_vector == QUDA_COMPUTE_NULL_VECTOR_YES && (p.mg_global.generate_all_levels == QUDA_BOOLEAN_YES || p.level == 0)) {
-      const double t0 = now();
+      const double t0 = wallTime();
       generateNullVectors(p.B);
       HIP_CHECK(hipStreamSynchronize(computeStream()));
-      if (getVerbosity() >= QUDA_SUMMARIZE || mgProfiling()) printfQuda("MG level %d: %d null vectors generated in %.3f s\n", p.level + 1, p.Nvec, now() - t0);
+      if (getVerbosity() >= QUDA_SUMMARIZE || mgProfiling()) printfQuda("MG level %d: %d null vectors generated in %.3f s\n", p.level + 1, p.Nvec, wallTime() - t0);
       saveVectors(p.B);
     } else if (p.mg_global.compute_null_vector == QUDA_COMPUTE_NULL_VECTOR_NO && (p.mg_global.generate_all_levels == QUDA_BOOLEAN_YES || p.level == 0)) {
       loadVectors(p.B);   // reference :25-32: a previously saved null space instead of a fresh setup
@@ -108,7 +95,7 @@ MG::MG(MGParam &p)
     postsmoother = Solver::create(*param_postsmooth, p.matSmooth, p.matSmooth, p.matSmooth);
   }
 
-  r = likeField(*p.B[0]);
+  r = like(*p.B[0], p.B[0]->Precision(), true);
   r->twistFlavor = p.fineFlavor;
   if (pcSmooth) {
     ColorSpinorParam bp = r->Even().param();
@@ -117,9 +104,9 @@ MG::MG(MGParam &p)
     b_tilde->twistFlavor = p.fineFlavor;
   }
   if (!coarsest) {
-    const double tT = now();
+    const double tT = wallTime();
     transfer = new Transfer(p.B, p.Nvec, p.geoBlockSize, p.spinBlockSize);
-    if (getVerbosity() >= QUDA_SUMMARIZE || mgProfiling()) printfQuda("MG level %d: transfer (fill + block Gram-Schmidt) in %.3f s\n", p.level + 1, now() - tT);
+    if (getVerbosity() >= QUDA_SUMMARIZE || mgProfiling()) printfQuda("MG level %d: transfer (fill + block Gram-Schmidt) in %.3f s\n", p.level + 1, wallTime() - tT);
     for (int d = 0; d < 4; d++) p.mg_global.geo_block_size[p.level][d] = p.geoBlockSize[d];
     r_coarse = transfer->createCoarseField();
     x_coarse = transfer->createCoarseField();
@@ -133,10 +120,10 @@ MG::MG(MGParam &p)
     dp.dagger = QUDA_DAG_NO;
     dp.matpcType = p.mg_global.invert_param->matpc_type;
     dp.twistFlavor = p.fineFlavor;
-    const double t0 = now();
+    const double t0 = wallTime();
     diracCoarse = new DiracCoarse(dp);
     matCoarse = new DiracM(*diracCoarse);
-    if (getVerbosity() >= QUDA_SUMMARIZE || mgProfiling()) printfQuda("MG level %d: coarse operator %d^2 x 9 per site on %d x %d x %d x %d built in %.3f s\n", p.level + 1, 2 * p.Nvec, transfer->Xc[0], transfer->Xc[1], transfer->Xc[2], transfer->Xc[3], now() - t0);
+    if (getVerbosity() >= QUDA_SUMMARIZE || mgProfiling()) printfQuda("MG level %d: coarse operator %d^2 x 9 per site on %d x %d x %d x %d built in %.3f s\n", p.level + 1, 2 * p.Nvec, transfer->Xc[0], transfer->Xc[1], transfer->Xc[2], transfer->Xc[3], wallTime() - t0);
 
     // coarse null vectors: restricted fine ones unless every level generates its own (reference :196-208)
     const int nVecCoarse = std::max(p.Nvec, p.level + 1 < p.Nlevel ? p.mg_global.n_vec[p.level + 1] : p.Nvec);
@@ -182,12 +169,6 @@ MG::MG(MGParam &p)
     }
   }
   if (getVerbosity() >= QUDA_SUMMARIZE) printfQuda("MG level %d: setup completed\n", p.level + 1);
-}
-
-void MG::dropFusedCycle() {
-  coarseCycleDestroy(fused);
-  fused = nullptr; fusedTried = false; fusedVerified = false;
-  if (coarse) coarse->dropFusedCycle();
 }
 
 MG::~MG() {
@@ -262,7 +243,7 @@ void MG::generateNullVectors(std::vector<ColorSpinorField *> &B) {
   // interleaves with the solves only touches finished vectors, so it is done afterwards.
   const DiracCoarse *dc = dynamic_cast<const DiracCoarse *>(mgp.matResidual.Expose());
   if (dc && dc->getDiracType() == QUDA_COARSE_DIRAC && blockCoarseSupported(dc->Links(), mgp.Nvec) && !coarseHalfStorage()) {
-    const double t0 = now();
+    const double t0 = wallTime();
     for (int i = 0; i < mgp.Nvec; i++) { B[i]->twistFlavor = mgp.fineFlavor; spinorRandom(*B[i], 0x5eedULL + 7919ULL * (mgp.level * 131 + i)); }
     BlockField X(dc->Links().nSites, dc->Links().n, mgp.Nvec, blockGhost(dc->Links().Xc, false).nGhost);
     std::vector<ColorSpinorField *> Bv(B.begin(), B.begin() + mgp.Nvec);
@@ -277,7 +258,7 @@ void MG::generateNullVectors(std::vector<ColorSpinorField *> &B) {
       int imin = iters[0], imax = iters[0];
       for (int i = 1; i < mgp.Nvec; i++) { imin = iters[i] < imin ? iters[i] : imin; imax = iters[i] > imax ? iters[i] : imax; }
       printfQuda("MG level %d: %d null vectors by block BiCGstab on the MFMA coarse operator: %d lockstep iterations (per vector %d..%d), %ld block applications, %.3f s\n",
-                 mgp.level + 1, mgp.Nvec, kmax, imin, imax, ctx.applies, now() - t0);
+                 mgp.level + 1, mgp.Nvec, kmax, imin, imax, ctx.applies, wallTime() - t0);
     }
     return;
   }
@@ -292,7 +273,7 @@ void MG::generateNullVectors(std::vector<ColorSpinorField *> &B) {
     const bool tmc = ty == QUDA_TWISTED_CLOVER_DIRAC && df->Clover() && df->Clover()->precision == QUDA_SINGLE_PRECISION;
     if (df && (ty == QUDA_TWISTED_MASS_DIRAC || ty == QUDA_WILSON_DIRAC || tmc) && B[0]->Nspin() == 4 && B[0]->Precision() == QUDA_SINGLE_PRECISION &&
         mgp.Nvec % nb == 0 && df->Gauge() && fineBlockSupported(*df->Gauge(), nb)) {
-      const double t0 = now();
+      const double t0 = wallTime();
       const double a = ty == QUDA_WILSON_DIRAC ? 0.0 : 2.0 * df->Kappa() * (double)mgp.fineFlavor * df->Mu();
       // The solves run on the EVEN-ODD PRECONDITIONED system: M x = 0 with x = (x_e, x_o) is  Mhat x_e = 0,  x_o = kappa A^-1 D_oe x_e
       // (Mhat = 1 - kappa^2 A^-1 D_eo A^-1 D_oe, A = 1 + i a g5: reference DiracTwistedMassPC::M / reconstruct with b = 0,
@@ -321,22 +302,22 @@ void MG::generateNullVectors(std::vector<ColorSpinorField *> &B) {
       double tPack = 0, tSolve = 0;
       for (int g0 = 0; g0 < mgp.Nvec; g0 += nb) {
         std::vector<ColorSpinorField *> Bv(B.begin() + g0, B.begin() + g0 + nb);
-        double tp = now();
+        double tp = wallTime();
         int iters[kMaxBlockRhs], kmax;
         if (fullOp) {
           BlockField X(B[0]->Volume(), 12, nb, 2 * nGhostPar);
           blockPack(X, Bv);
-          if (mgProfiling()) { HIP_CHECK(hipStreamSynchronize(computeStream())); tPack += now() - tp; tp = now(); }
+          if (mgProfiling()) { HIP_CHECK(hipStreamSynchronize(computeStream())); tPack += wallTime() - tp; tp = wallTime(); }
           kmax = blockBiCGstabNull(X, [](BlockField &out, BlockField &in, void *c) {
             Ctx *x = (Ctx *)c; applyFineBlockM(out.v, in.v, in.nrhs, *x->U, x->kappa, x->a, x->tmat[0] ? x->tmat : nullptr); x->applies++; },
                                    &ctx, sp.tol, sp.maxiter, iters);
-          if (mgProfiling()) { HIP_CHECK(hipStreamSynchronize(computeStream())); tSolve += now() - tp; tp = now(); }
+          if (mgProfiling()) { HIP_CHECK(hipStreamSynchronize(computeStream())); tSolve += wallTime() - tp; tp = wallTime(); }
           blockUnpack(Bv, X);
         } else {
           BlockField Xe(Vh, 12, nb, nGhostPar), Xo(Vh, 12, nb, nGhostPar);
           blockPack(Xe, Bv, 0);
           ctx.tmp = &Xo;
-          if (mgProfiling()) { HIP_CHECK(hipStreamSynchronize(computeStream())); tPack += now() - tp; tp = now(); }
+          if (mgProfiling()) { HIP_CHECK(hipStreamSynchronize(computeStream())); tPack += wallTime() - tp; tp = wallTime(); }
           auto ghostOf = [](BlockField &f) { return f.nGhost ? f.v + f.elems() : nullptr; };
           kmax = blockBiCGstabNull(Xe, [](BlockField &out, BlockField &in, void *c) {
             Ctx *x = (Ctx *)c;
@@ -369,11 +350,11 @@ void MG::generateNullVectors(std::vector<ColorSpinorField *> &B) {
           // x_o = kappa A^-1 D_oe x_e
           if (tmc) applyFineBlockParity(Xo.v, nullptr, Xe.v, nb, *df->Gauge(), 1, 0.0, 0.0, kappa, 0.0, tmat[1], 1, ghostOf(Xe));
           else applyFineBlockParity(Xo.v, nullptr, Xe.v, nb, *df->Gauge(), 1, 0.0, 0.0, kappa * binv, -a, nullptr, 0, ghostOf(Xe));
-          if (mgProfiling()) { HIP_CHECK(hipStreamSynchronize(computeStream())); tSolve += now() - tp; tp = now(); }
+          if (mgProfiling()) { HIP_CHECK(hipStreamSynchronize(computeStream())); tSolve += wallTime() - tp; tp = wallTime(); }
           blockUnpack(Bv, Xe, 0);
           blockUnpack(Bv, Xo, 1);
         }
-        if (mgProfiling()) { HIP_CHECK(hipStreamSynchronize(computeStream())); tPack += now() - tp; }
+        if (mgProfiling()) { HIP_CHECK(hipStreamSynchronize(computeStream())); tPack += wallTime() - tp; }
         kmaxAll = kmax > kmaxAll ? kmax : kmaxAll;
         for (int i = 0; i < nb; i++) { imin = iters[i] < imin ? iters[i] : imin; imax = iters[i] > imax ? iters[i] : imax; }
       }
@@ -383,14 +364,14 @@ void MG::generateNullVectors(std::vector<ColorSpinorField *> &B) {
       }
       orthonormaliseNullVectors(B, mgp.Nvec);
       nullVectorMethod = 1; nullVectorIterations = kmaxAll;
-      if (mgProfiling()) printfQuda("MG level %d: block null-vector stage: pack/unpack + field allocation %.3f s, lockstep solves %.3f s, orthonormalisation %.3f s\n", mgp.level + 1, tPack, tSolve, now() - t0 - tPack - tSolve);
+      if (mgProfiling()) printfQuda("MG level %d: block null-vector stage: pack/unpack + field allocation %.3f s, lockstep solves %.3f s, orthonormalisation %.3f s\n", mgp.level + 1, tPack, tSolve, wallTime() - t0 - tPack - tSolve);
       if (getVerbosity() >= QUDA_SUMMARIZE || mgProfiling())
         printfQuda("MG level %d: %d null vectors by block BiCGstab on the %d-right-hand-side %s stencil: up to %d lockstep iterations (per vector %d..%d), %ld block applications, %.3f s\n",
-                   mgp.level + 1, mgp.Nvec, nb, tmc ? "twisted-clover" : "twisted-mass / Wilson", kmaxAll, imin, imax, ctx.applies, now() - t0);
+                   mgp.level + 1, mgp.Nvec, nb, tmc ? "twisted-clover" : "twisted-mass / Wilson", kmaxAll, imin, imax, ctx.applies, wallTime() - t0);
       return;
     }
   }
-  ColorSpinorField *b = likeField(*B[0]);
+  ColorSpinorField *b = like(*B[0], B[0]->Precision(), true);
   b->twistFlavor = mgp.fineFlavor;
   const QudaVerbosity v0 = getVerbosity();
   for (int i = 0; i < mgp.Nvec; i++) {
@@ -499,13 +480,13 @@ void MG::loadVectors(std::vector<ColorSpinorField *> &B) {
 struct StageTimer {
   int level, stage; double t0; bool on;
   StageTimer(int l, int s) : level(l), stage(s), t0(0), on(mgProfiling() != 0) {
-    if (on) { HIP_CHECK(hipStreamSynchronize(computeStream())); t0 = now(); }
+    if (on) { HIP_CHECK(hipStreamSynchronize(computeStream())); t0 = wallTime(); }
   }
   ~StageTimer() {
     if (!on) return;
-    const double t1 = now();
+    const double t1 = wallTime();
     HIP_CHECK(hipStreamSynchronize(computeStream()));
-    const double t2 = now();
+    const double t2 = wallTime();
     g_mgProf[level][stage] += t2 - t0;
     if (mgProfiling() == 2 && t2 - t0 > 2e-3) printfQuda("MG stage: level %d stage %d took %.3f ms (host %.3f ms + drain %.3f ms)\n", level, stage, 1e3 * (t2 - t0), 1e3 * (t1 - t0), 1e3 * (t2 - t1));
   }
@@ -588,8 +569,7 @@ void MG::cycleParity(ColorSpinorField &x, ColorSpinorField &b, bool fullResidual
 // — the relation MG::cycleParity uses the other way round to restrict the full residual behind an even-odd smoother.  One or two sweeps instead of
 // an application of A: 2 of the 12 stencil launches of an outer GCR iteration.
 bool MG::imageOfLast(ColorSpinorField &Ax, const ColorSpinorField &b, const DiracMatrix &A) {
-  static int on = -1;
-  if (on < 0) { const char *e = getenv("QUDA_AMD_MG_IMAGE_FROM_RESIDUAL"); on = e ? atoi(e) : 1; }
+  static const int on = envInt("QUDA_AMD_MG_IMAGE_FROM_RESIDUAL", 1);
   if (!on || lastParityCycle < 0 || !A.isM() || !pcSmooth) return false;
   const Dirac *Ad = A.Expose(), *S = mgp.matSmooth.Expose();
   const ColorSpinorField *res = postsmoother->lastResidual();
@@ -776,7 +756,7 @@ void MG::makeHalfMirrors() {
 void MG::verify(double dev[3]) {
   dev[0] = dev[1] = dev[2] = 0.0;
   if (mgp.level >= mgp.Nlevel - 1) return;
-  ColorSpinorField *tmp1 = likeField(*mgp.B[0]), *tmp2 = likeField(*mgp.B[0]);
+  ColorSpinorField *tmp1 = like(*mgp.B[0], mgp.B[0]->Precision(), true), *tmp2 = like(*mgp.B[0], mgp.B[0]->Precision(), true);
   ColorSpinorField *c1 = transfer->createCoarseField(), *c2 = transfer->createCoarseField(), *c3 = transfer->createCoarseField();
   tmp1->twistFlavor = tmp2->twistFlavor = mgp.fineFlavor;
   // (1) v_k - P P^dag v_k = 0 for the vectors the transfer was built from
@@ -839,7 +819,7 @@ multigrid_solver::multigrid_solver(QudaMultigridParam &mg_param)
   if (!g) errorQuda("Gauge field not allocated");
   if (g->precision != QUDA_SINGLE_PRECISION) errorQuda("the multigrid hierarchy runs in fp32: load the gauge field with cuda_prec_precondition = QUDA_SINGLE_PRECISION (got %d)", g->precision);
   mg_param.secs = 0; mg_param.gflops = 0;
-  const double t0 = now();
+  const double t0 = wallTime();
 
   // QKXTM: kappa / mu rescaled for the P,R setup only (reference :2196-2211)
   const double orig_mu = param->mu, orig_kappa = param->kappa, orig_mass = param->mass;
@@ -870,7 +850,7 @@ multigrid_solver::multigrid_solver(QudaMultigridParam &mg_param)
   inv_param_copy = *param;
   { const char *e = getenv("QUDA_AMD_MG_REFINE"); if (e && atoi(e) > 0) refine(atoi(e), 1); }
   { const char *e = getenv("QUDA_AMD_MG_HALF"); if (e && atoi(e)) multigridSetHalfStorage(*this, true); }
-  mg_param.secs = now() - t0;
+  mg_param.secs = wallTime() - t0;
   // the block work fields of the lockstep solves (7 x 4 GB at 48^3 x 96) stay parked in the pool for the next hierarchy (the down-flavour
   // one of the QKXTM drivers is built right after this one); QUDA_AMD_POOL_KEEP=0 hands everything of 256 MB and more back now
   { const char *e = getenv("QUDA_AMD_POOL_KEEP"); if (e && !atoi(e)) { HIP_CHECK(hipStreamSynchronize(computeStream())); poolDeviceFlush((size_t)256 << 20); } }
@@ -878,12 +858,12 @@ multigrid_solver::multigrid_solver(QudaMultigridParam &mg_param)
 
 void multigrid_solver::refine(int passes, int cycles) {
   if (passes <= 0) return;
-  const double t0 = now();
+  const double t0 = wallTime();
   // half-precision storage is a property of the hierarchy objects that are rebuilt below: remember it and put it back (a refined
   // hierarchy silently lost its fp16 mirrors and 16-bit smoother while the process-wide switch stayed on)
   const bool hadHalf = coarseHalfStorage() && mSmoothHalf != nullptr;
   if (hadHalf) multigridSetHalfStorage(*this, false);
-  ColorSpinorField *y = likeField(*B[0]);
+  ColorSpinorField *y = like(*B[0], B[0]->Precision(), true);
   const QudaTwistFlavorType flavor = B[0]->TwistFlavor();
   y->twistFlavor = flavor;
   mg_param_copy.invert_param = &inv_param_copy;
@@ -903,11 +883,11 @@ void multigrid_solver::refine(int passes, int cycles) {
     mgParam = new MGParam(mg_param_copy, B, *m, mSmooth ? *mSmooth : *m, 0, flavor);
     mgParam->vectorsPreset = true;
     mg = new MG(*mgParam);
-    if (getVerbosity() >= QUDA_SUMMARIZE || mgProfiling()) printfQuda("MG set-up refinement pass %d of %d done (%.3f s so far)\n", pass + 1, passes, now() - t0);
+    if (getVerbosity() >= QUDA_SUMMARIZE || mgProfiling()) printfQuda("MG set-up refinement pass %d of %d done (%.3f s so far)\n", pass + 1, passes, wallTime() - t0);
   }
   delete y;
   if (hadHalf) multigridSetHalfStorage(*this, true);
-  mg_param_copy.secs += now() - t0;
+  mg_param_copy.secs += wallTime() - t0;
 }
 
 void multigridSetHalfStorage(multigrid_solver &mgs, bool on) {

@@ -5,11 +5,13 @@
 #include <cmath>
 #include <sys/time.h>
 
+#include "gcr_core.h"
 #include "multigrid.h"
+#include "quda_amd_ext.h"
 
 namespace quda {
 
-static double now() {
+double wallTime() {
   timeval t;
   gettimeofday(&t, nullptr);
   return t.tv_sec + 1e-6 * t.tv_usec;
@@ -94,7 +96,7 @@ Solver *Solver::create(SolverParam &param, DiracMatrix &mat, DiracMatrix &matSlo
   return nullptr;
 }
 
-static ColorSpinorField *like(const ColorSpinorField &x, QudaPrecision prec, bool zero) {
+ColorSpinorField *like(const ColorSpinorField &x, QudaPrecision prec, bool zero) {
   ColorSpinorParam p = x.param();
   p.location = QUDA_CUDA_FIELD_LOCATION;
   p.precision = prec;
@@ -133,7 +135,7 @@ void MR::operator()(ColorSpinorField &x, ColorSpinorField &b) {
   for (ColorSpinorField *f : {rp, Arp, yp}) if (f) f->twistFlavor = b.twistFlavor;
   ColorSpinorField &r = *rp, &Ar = *Arp;
   ColorSpinorField &y = same ? x : *yp;   // where the iteration accumulates
-  const double t0 = now();
+  const double t0 = wallTime();
   const bool guess = param.use_init_guess == QUDA_USE_INIT_GUESS_YES;
   const double omega = param.omega;
   residualValid = false;
@@ -180,7 +182,7 @@ void MR::operator()(ColorSpinorField &x, ColorSpinorField &b) {
   }
   residualValid = true;
   if (!param.is_preconditioner) {
-    param.secs += now() - t0;
+    param.secs += wallTime() - t0;
     param.gflops += (blas::flops + mat.flops() + matSloppy.flops()) * 1e-9;
     param.iter += k;
     if (param.preserve_source == QUDA_PRESERVE_SOURCE_YES && param.compute_true_res) {
@@ -223,7 +225,7 @@ void BiCGstab::operator()(ColorSpinorField &x, ColorSpinorField &b) {
   xsp = mixed ? like(x, param.precision_sloppy, true) : nullptr;
   for (ColorSpinorField *f : {yp, rp, pp, vp, tp, r0p, rsp, xsp}) if (f) f->twistFlavor = x.twistFlavor;
   ColorSpinorField &y = *yp, &r = *rp, &p = *pp, &v = *vp, &t = *tp, &r0 = *r0p;
-  const double t0 = now();
+  const double t0 = wallTime();
 
   double b2 = blas::norm2(b), r2;
   if (param.use_init_guess == QUDA_USE_INIT_GUESS_YES) {
@@ -294,7 +296,7 @@ void BiCGstab::operator()(ColorSpinorField &x, ColorSpinorField &b) {
   }
   if (mixed) blas::copy(x, xSloppy);
   blas::xpy(y, x);
-  param.secs += now() - t0;
+  param.secs += wallTime() - t0;
   param.gflops += (blas::flops + mat.flops() + matSloppy.flops() + matPrecon.flops()) * 1e-9;
   param.iter += k;
   if (k == param.maxiter && param.compute_null_vector == QUDA_COMPUTE_NULL_VECTOR_NO) warningQuda("Exceeded maximum iterations %d", param.maxiter);
@@ -310,16 +312,9 @@ void BiCGstab::operator()(ColorSpinorField &x, ColorSpinorField &b) {
 // ================================================================================================
 // GCR — flexible, restarted, with reliable updates (outer solver; K = multigrid V/K-cycle)
 // ================================================================================================
-static void allocCoeffs(int n, Complex *&alpha, Complex **&beta, double *&gamma) {
-  alpha = new Complex[n];
-  beta = new Complex *[n];
-  for (int i = 0; i < n; i++) beta[i] = new Complex[n];
-  gamma = new double[n];
-}
-
 GCR::GCR(DiracMatrix &mat_, DiracMatrix &matSloppy_, DiracMatrix &matPrecon_, SolverParam &p)
-    : Solver(p), mat(mat_), matSloppy(matSloppy_), matPrecon(matPrecon_), K(nullptr), ownK(true), Kparam(p), nKrylov(p.Nkrylov), init(false), rp(nullptr),
-      yp(nullptr), x_sloppy(nullptr), r_sloppy(nullptr), p_pre(nullptr), r_pre(nullptr), rM(nullptr) {
+    : Solver(p), mat(mat_), matSloppy(matSloppy_), matPrecon(matPrecon_), K(nullptr), ownK(true), Kparam(p), nKrylov(p.Nkrylov), coeffs(new GcrCoeffs(p.Nkrylov)), init(false),
+      rp(nullptr), yp(nullptr), x_sloppy(nullptr), r_sloppy(nullptr), p_pre(nullptr), r_pre(nullptr), rM(nullptr) {
   fillInnerSolveParam(Kparam, p);
   if (p.inv_type_precondition == QUDA_MR_INVERTER) K = new MR(matPrecon_, matPrecon_, Kparam);
   else if (p.inv_type_precondition == QUDA_BICGSTAB_INVERTER) K = new BiCGstab(matPrecon_, matPrecon_, matPrecon_, Kparam);
@@ -327,22 +322,16 @@ GCR::GCR(DiracMatrix &mat_, DiracMatrix &matSloppy_, DiracMatrix &matPrecon_, So
   else errorQuda("Unsupported preconditioner %d", p.inv_type_precondition);
   this->p.resize(nKrylov, nullptr);
   Ap.resize(nKrylov, nullptr);
-  allocCoeffs(nKrylov, alpha, beta, gamma);
 }
 
 GCR::GCR(DiracMatrix &mat_, Solver &K_, DiracMatrix &matSloppy_, DiracMatrix &matPrecon_, SolverParam &p)
-    : Solver(p), mat(mat_), matSloppy(matSloppy_), matPrecon(matPrecon_), K(&K_), ownK(false), Kparam(p), nKrylov(p.Nkrylov), init(false), rp(nullptr),
-      yp(nullptr), x_sloppy(nullptr), r_sloppy(nullptr), p_pre(nullptr), r_pre(nullptr), rM(nullptr) {
+    : Solver(p), mat(mat_), matSloppy(matSloppy_), matPrecon(matPrecon_), K(&K_), ownK(false), Kparam(p), nKrylov(p.Nkrylov), coeffs(new GcrCoeffs(p.Nkrylov)), init(false),
+      rp(nullptr), yp(nullptr), x_sloppy(nullptr), r_sloppy(nullptr), p_pre(nullptr), r_pre(nullptr), rM(nullptr) {
   this->p.resize(nKrylov, nullptr);
   Ap.resize(nKrylov, nullptr);
-  allocCoeffs(nKrylov, alpha, beta, gamma);
 }
 
 GCR::~GCR() {
-  delete[] alpha;
-  for (int i = 0; i < nKrylov; i++) delete[] beta[i];
-  delete[] beta;
-  delete[] gamma;
   if (K && ownK) delete K;
   delete rM;
   if (x_sloppy && param.precision_sloppy != param.precision) { delete x_sloppy; delete r_sloppy; }
@@ -352,29 +341,67 @@ GCR::~GCR() {
   delete yp;
 }
 
-// reference :86-123 (pipeline 0/1 forms)
-static void orthoDir(Complex **beta, std::vector<ColorSpinorField *> &Ap, int k, int pipeline) {
-  if (pipeline == 0) {
+// reference :86-123: Ap[k] -= sum_{i < k} beta(i, k) Ap[i], one direction at a time
+static void orthoDir(GcrCoeffs &c, std::vector<ColorSpinorField *> &Ap, int k, GcrChain chain) {
+  if (chain == GcrChain::Sequential) {
     for (int i = 0; i < k; i++) {
-      beta[i][k] = blas::cDotProduct(*Ap[i], *Ap[k]);
-      blas::caxpy(-beta[i][k], *Ap[i], *Ap[k]);
+      c.b(i, k) = blas::cDotProduct(*Ap[i], *Ap[k]);
+      blas::caxpy(-c.b(i, k), *Ap[i], *Ap[k]);
     }
   } else {
     if (k == 0) return;
-    beta[0][k] = blas::cDotProduct(*Ap[0], *Ap[k]);
-    for (int i = 0; i < k - 1; i++) beta[i + 1][k] = blas::caxpyDotzy(-beta[i][k], *Ap[i], *Ap[k], *Ap[i + 1]);
-    blas::caxpy(-beta[k - 1][k], *Ap[k - 1], *Ap[k]);
+    c.b(0, k) = blas::cDotProduct(*Ap[0], *Ap[k]);
+    for (int i = 0; i < k - 1; i++) c.b(i + 1, k) = blas::caxpyDotzy(-c.b(i, k), *Ap[i], *Ap[k], *Ap[i + 1]);
+    blas::caxpy(-c.b(k - 1, k), *Ap[k - 1], *Ap[k]);
   }
 }
 
-// reference :125-157
-static void updateSolution(ColorSpinorField &x, const Complex *alpha, Complex **const beta, double *gamma, int k, std::vector<ColorSpinorField *> &p) {
-  std::vector<Complex> delta(k);
-  for (int i = k - 1; i >= 0; i--) {
-    delta[i] = alpha[i];
-    for (int j = i + 1; j < k; j++) delta[i] -= beta[i][j] * delta[j];
-    delta[i] /= gamma[i];
+double gcrKrylovStep(GcrCoeffs &c, std::vector<ColorSpinorField *> &Ap, int k, ColorSpinorField &r, GcrChain chain, bool *blockedOk) {
+  // Blocked orthogonalisation (reference :53-84, :103-121 pipelined forms): all k inner products (Ap_i, Ap_k), (Ap_k, r) and |Ap_k|^2
+  // in ONE sweep, then the k updates, the normalisation and the residual update in ONE sweep — 2 k + 6 field passes instead of the
+  // 4 (k - 1) + 9 of the one-direction-at-a-time chain below.  Classical Gram-Schmidt: the norm of the orthogonalised vector is
+  // |Ap_k|^2 - sum |beta_i|^2 (the Ap_i are orthonormal) and (Ap_i, r) = 0 for i < k, so (Ap_k', r) = (Ap_k, r).  Where that
+  // difference loses more than two digits (the new direction lies almost in the span of the old ones) the iteration falls back to
+  // the sequential chain, which measures the norm instead of inferring it.
+  double r2 = 0.0;
+  if ((!blockedOk || *blockedOk) && blas::multiSupported(*Ap[k], k)) {
+    std::vector<Complex> bk(k > 0 ? k : 1);
+    Complex apr; double apn;
+    blas::multiDot(bk.data(), apr, apn, Ap, k, *Ap[k], r);
+    double g2 = apn;
+    for (int i = 0; i < k; i++) g2 -= std::norm(bk[i]);
+    if (apn == 0.0) errorQuda("GCR breakdown");
+    if (g2 > 1e-2 * apn) {
+      for (int i = 0; i < k; i++) { c.b(i, k) = bk[i]; bk[i] = -bk[i]; }
+      c.gamma[k] = sqrt(g2);
+      c.alpha[k] = apr / c.gamma[k];
+      double y2;
+      blas::multiCaxpyResidual(r2, y2, bk.data(), Ap, k, 1.0 / c.gamma[k], *Ap[k], c.alpha[k], r);   // Ap_k = (Ap_k - sum beta_i Ap_i) / gamma ; r -= alpha Ap_k
+      // y2 is the MEASURED |Ap_k|^2 after the normalisation with the inferred gamma: 1 up to round-off while the old directions are
+      // orthonormal.  Where it is not (single-pass classical Gram-Schmidt in fp32 over up to 20 directions), the direction is put right
+      // with the measured norm — Ap_k, gamma and alpha rescaled consistently, r untouched: alpha Ap_k is invariant under that rescaling
+      // — and the rest of this Krylov cycle goes through the sequential chain, which measures instead of inferring.
+      if (blockedOk && k > 0 && std::fabs(y2 - 1.0) > 1e-3 && y2 > 0.0) {
+        const double s = sqrt(y2);
+        blas::ax(1.0 / s, *Ap[k]);
+        c.gamma[k] *= s;
+        c.alpha[k] *= s;
+        *blockedOk = false;
+      }
+      return r2;
+    }
   }
+  orthoDir(c, Ap, k, chain);
+  const double3_t Apr = blas::cDotProductNormA(*Ap[k], r);
+  c.gamma[k] = sqrt(Apr.z);
+  if (c.gamma[k] == 0.0) errorQuda("GCR breakdown");
+  c.alpha[k] = Complex(Apr.x, Apr.y) / c.gamma[k];
+  return blas::cabxpyAxNorm(1.0 / c.gamma[k], -c.alpha[k], *Ap[k], r);  // Ap /= |Ap| ; r -= alpha Ap
+}
+
+void gcrUpdateSolution(ColorSpinorField &x, const GcrCoeffs &c, int k, std::vector<ColorSpinorField *> &p) {
+  std::vector<Complex> delta(k);
+  c.backSubstitute(k, delta.data());
   // one pass over the k directions (blas::multiCaxpy) instead of k read-modify-write passes over x
   if (blas::multiSupported(x, k)) blas::multiCaxpy(delta.data(), p, k, x);
   else for (int i = 0; i < k; i++) blas::caxpy(delta[i], *p[i], x);
@@ -411,7 +438,7 @@ void GCR::operator()(ColorSpinorField &x, ColorSpinorField &b) {
   for (ColorSpinorField *f : {rp, yp, x_sloppy, r_sloppy, p_pre, r_pre, rM}) if (f) f->twistFlavor = b.twistFlavor;
   for (int i = 0; i < nKrylov; i++) { p[i]->twistFlavor = b.twistFlavor; Ap[i]->twistFlavor = b.twistFlavor; }
   blas::setGlobalReduction(param.global_reduction);
-  const double t0 = now();
+  const double t0 = wallTime();
   blas::zero(y);
 
   const double b2 = blas::norm2(b);
@@ -442,7 +469,6 @@ void GCR::operator()(ColorSpinorField &x, ColorSpinorField &b) {
   int total_iter = 0, restart = 0;
   double r2_old = r2;
   bool l2_converge = false;
-  const int pipeline = param.pipeline > 1 ? 1 : (param.pipeline == 0 ? 1 : param.pipeline);
   int k = 0;
   bool blockedOrthoOk = true;   // cleared for the rest of a Krylov cycle once the blocked orthogonalisation has shown a loss of orthogonality
   PrintStats("GCR", total_iter + k, r2, b2, 0.0);
@@ -462,53 +488,13 @@ void GCR::operator()(ColorSpinorField &x, ColorSpinorField &b) {
       // a multigrid cycle that ends in an MR smoother on this operator's even-odd system knows A p_k already (MG::imageOfLast)
       if (!(K && param.precondition_cycle == 1 && precMatch && K->imageOfLast(*Ap[k], rSloppy, matSloppy))) matSloppy(*Ap[k], *p[k]);
     }
-    // Blocked orthogonalisation (reference :53-84, :103-121 pipelined forms): all k inner products (Ap_i, Ap_k), (Ap_k, r) and |Ap_k|^2
-    // in ONE sweep, then the k updates, the normalisation and the residual update in ONE sweep — 2 k + 6 field passes instead of the
-    // 4 (k - 1) + 9 of the one-direction-at-a-time chain below.  Classical Gram-Schmidt: the norm of the orthogonalised vector is
-    // |Ap_k|^2 - sum |beta_i|^2 (the Ap_i are orthonormal) and (Ap_i, r) = 0 for i < k, so (Ap_k', r) = (Ap_k, r).  Where that
-    // difference loses more than two digits (the new direction lies almost in the span of the old ones) the iteration falls back to
-    // the sequential chain, which measures the norm instead of inferring it.
-    bool blocked = false;
-    if (blockedOrthoOk && blas::multiSupported(*Ap[k], k)) {
-      std::vector<Complex> bk(k > 0 ? k : 1);
-      Complex apr; double apn;
-      blas::multiDot(bk.data(), apr, apn, Ap, k, *Ap[k], rSloppy);
-      double g2 = apn;
-      for (int i = 0; i < k; i++) g2 -= std::norm(bk[i]);
-      if (apn == 0.0) errorQuda("GCR breakdown");
-      if (g2 > 1e-2 * apn) {
-        for (int i = 0; i < k; i++) { beta[i][k] = bk[i]; bk[i] = -bk[i]; }
-        gamma[k] = sqrt(g2);
-        alpha[k] = apr / gamma[k];
-        double y2;
-        blas::multiCaxpyResidual(r2, y2, bk.data(), Ap, k, 1.0 / gamma[k], *Ap[k], alpha[k], rSloppy);   // Ap_k = (Ap_k - sum beta_i Ap_i) / gamma ; r -= alpha Ap_k
-        blocked = true;
-        // y2 is the MEASURED |Ap_k|^2 after the normalisation with the inferred gamma: 1 up to round-off while the old directions are
-        // orthonormal.  Where it is not (single-pass classical Gram-Schmidt in fp32 over up to 20 directions), the direction is put right
-        // with the measured norm — Ap_k, gamma and alpha rescaled consistently, r untouched: alpha Ap_k is invariant under that rescaling
-        // — and the rest of this Krylov cycle goes through the sequential chain, which measures instead of inferring.
-        if (k > 0 && std::fabs(y2 - 1.0) > 1e-3 && y2 > 0.0) {
-          const double s = sqrt(y2);
-          blas::ax(1.0 / s, *Ap[k]);
-          gamma[k] *= s;
-          alpha[k] *= s;
-          blockedOrthoOk = false;
-        }
-      }
-    }
-    if (!blocked) {
-      orthoDir(beta, Ap, k, pipeline);
-      const double3_t Apr = blas::cDotProductNormA(*Ap[k], rSloppy);
-      gamma[k] = sqrt(Apr.z);
-      if (gamma[k] == 0.0) errorQuda("GCR breakdown");
-      alpha[k] = Complex(Apr.x, Apr.y) / gamma[k];
-      r2 = blas::cabxpyAxNorm(1.0 / gamma[k], -alpha[k], *Ap[k], rSloppy);  // Ap /= |Ap| ; r -= alpha Ap
-    }
+    // (the pipelined chain for every value of param.pipeline: 0 and values above 1 have always been read as 1)
+    r2 = gcrKrylovStep(*coeffs, Ap, k, rSloppy, GcrChain::Pipelined, &blockedOrthoOk);
     k++;
     total_iter++;
     PrintStats("GCR", total_iter, r2, b2, 0.0);
     if (k == nKrylov || total_iter == param.maxiter || (r2 < stop && !l2_converge) || sqrt(r2 / r2_old) < param.delta) {
-      updateSolution(xSloppy, alpha, beta, gamma, k, p);
+      gcrUpdateSolution(xSloppy, *coeffs, k, p);
       if (mixed) blas::copy(x, xSloppy);
       blas::xpy(x, y);
       mat(r, y);
@@ -538,7 +524,7 @@ void GCR::operator()(ColorSpinorField &x, ColorSpinorField &b) {
     }
   }
   if (total_iter > 0) blas::copy(x, y);
-  param.secs += now() - t0;
+  param.secs += wallTime() - t0;
   double gf = (blas::flops + mat.flops() + matSloppy.flops() + matPrecon.flops()) * 1e-9;
   if (K) gf += K->flops() * 1e-9;
   if (getVerbosity() >= QUDA_VERBOSE && !param.is_preconditioner) printfQuda("GCR: number of restarts = %d\n", restart);
@@ -555,3 +541,14 @@ void GCR::operator()(ColorSpinorField &x, ColorSpinorField &b) {
 }
 
 }  // namespace quda
+
+// test hook (quda_amd_ext.h): GcrCoeffs::backSubstitute on host-supplied coefficients
+extern "C" void qudaAmdGcrBackSubstitute(int k, int nK, const double *alpha, const double *beta, const double *gamma, double *delta) {
+  if (nK < 1 || k < 0 || k > nK || !alpha || !beta || !gamma || !delta) errorQuda("qudaAmdGcrBackSubstitute: k = %d, nK = %d or a NULL argument", k, nK);
+  quda::GcrCoeffs c(nK);
+  for (int i = 0; i < nK; i++) { c.alpha[i] = quda::Complex(alpha[2 * i], alpha[2 * i + 1]); c.gamma[i] = gamma[i]; }
+  for (int i = 0; i < nK * nK; i++) c.beta[i] = quda::Complex(beta[2 * i], beta[2 * i + 1]);
+  std::vector<quda::Complex> d(k);
+  c.backSubstitute(k, d.data());
+  for (int a = 0; a < k; a++) { delta[2 * a] = d[a].real(); delta[2 * a + 1] = d[a].imag(); }
+}

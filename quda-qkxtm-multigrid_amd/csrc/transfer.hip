@@ -154,7 +154,7 @@ __global__ void __launch_bounds__(256) restrict_stream_kernel(CoarseVec out, Fin
   }
 }
 
-// ---- FOUR SOURCES per pass over V (invertMultiSrcQuda, block_solver.cpp): the restrictor / prolongator of the fine level are pure streams of V
+// ---- FOUR SOURCES per pass over V (invertMultiSrcQuda, block_mg_cycle.cpp): the restrictor / prolongator of the fine level are pure streams of V
 // (2304 B per fine site against 96 B of vector), so a lockstep multi-source cycle that restricts its sources one after the other reads V once per
 // source.  Same structure as restrict_stream_kernel / prolong_kernel — three steps of V requests in flight per thread, fenced — with the V entries
 // of a step meeting the site's components of four sources; the reduce-scatter butterfly that summed four STEPS of one source there sums one step

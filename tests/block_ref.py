@@ -81,7 +81,7 @@ def coefficients(nrhs, k=0, converged=None):
 
 def mr_operands(rng, shape, steps, zero_col=2):
     """x, r, rin, w1 (, w2) of a minimal-residual update as the smoother meets them: w1 = A rin, w2 = A w1 for an A = 0.9 + small, so that no
-    coefficient comes from a cancellation; column zero_col is zero in every field (the padding column of block_solver.cpp)"""
+    coefficient comes from a cancellation; column zero_col is zero in every field (the padding column of block_coarse_cycle.cpp)"""
     f = {n: operand(rng, *shape, k=k, zero_col=zero_col) for k, n in enumerate(["x", "rin", "r"])}
     prev = f["rin"]
     for k, n in enumerate(["w1", "w2"][:steps]):

@@ -6,7 +6,7 @@ values of their summands; epilogue sums to 25 * 2^-24 + 1e-13 of it (the bound o
 bit for bit.  The device images are permuted here by the two formulas of block.h, so a word given to the wrong right-hand side fails.
 
 Operands: normal fp32 reals times 10^u per (site, right-hand side), u uniform in [-3, 3]; right-hand side 2 identically zero in every field
-(for MR the padding column of block_solver.cpp); one zero site per column, another one in each column and field; per-column complex
+(for MR the padding column of block_coarse_cycle.cpp); one zero site per column, another one in each column and field; per-column complex
 coefficients with two nonzero, unequal parts that differ from column to column; column 1 converged (all its coefficients zero).
 
 BLAS shapes (sites, components, right-hand sides), free of any lattice; n4 = 16-byte words, work-groups of 192:

@@ -52,8 +52,9 @@ def test_hooks_call_the_library_code_and_do_not_copy_it():
     body = src[src.index("void qudaAmdMultigridGetCoarseSiteLinks"):]
     for call in (r"applyCoarse\(", r"blockCoarseSchurPiece\(", r"coarseInvertHat\(", r"pc->M\(", r"pc->prepare\(", r"pc->reconstruct\("):
         assert re.search(call, body), call
-    block = open(os.path.join(csrc, "block_solver.cpp")).read()
-    piece = block[block.index("int blockCoarseSchurPiece"):block.index("// the smoother of the fine level for all sources")]
+    block = open(os.path.join(csrc, "block_coarse_cycle.cpp")).read()
+    start = block.index("int blockCoarseSchurPiece")
+    piece = block[start:block.index("\n}\n", start)]   # to the end of that function
     for call in (r"bc\.matpc\(", r"bc\.prepare\(", r"bc\.reconstruct\("):
         assert re.search(call, piece), call
     coarse = open(os.path.join(csrc, "coarse.hip")).read()

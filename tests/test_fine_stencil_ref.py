@@ -3,7 +3,7 @@
   * the reference's own hop sum reproduces oracle.wil_dslash, so the term sums stand on pinned neighbours, daggers and projectors;
   * one launch per parity reproduces the full operators oracle.tm_mat (s0 = 1, a0 = 2 kappa mu, k1 = -kappa, a1 = 0) and, with the direct
     site matrices on `same`, oracle.tmc_mat, to 1e-13; the two-launch Schur compositions of the multi-source smoother
-    (csrc/block_solver.cpp BlockFineSmoother::matpc) reproduce oracle.tmc_matpc and oracle.tm_matpc to 1e-12;
+    (csrc/block_fine_smoother.cpp BlockFineSmoother::matpc) reproduce oracle.tmc_matpc and oracle.tm_matpc to 1e-12;
   * the bound constants: the oracle's fp32 variants (qo_wil_dslash_f, qo_apply_clover_f) and float32 numpy stand in for the device on every
     coefficient case and kind of links of tests/test_fine_stencil_gpu.py; twice the worst |err| / (2^-24 T), rounded up, must not exceed
     K_PLAIN / K_SITE, and those must not exceed the caps 24 / 40.  The ratios are printed (pytest -s);

@@ -1,6 +1,7 @@
 """invertMultiSrcQuda (reference include/quda.h:647; lib/interface_quda.cpp:2546: declared, "cannot work" there): several sources through ONE
 lockstep MG-GCR solve — outer GCR per source with a shared Krylov index, one multigrid cycle for all sources whose coarse levels run on block
-fields through the multi-right-hand-side MFMA coarse operator (csrc/block_solver.cpp).  Every column is a solution in its own right: host
+fields through the multi-right-hand-side MFMA coarse operator (csrc/block_solver.cpp: the lockstep GCR; csrc/block_mg_cycle.cpp,
+block_fine_smoother.cpp, block_coarse_cycle.cpp: its cycle).  Every column is a solution in its own right: host
 residual with the oracle's tm_mat (as tests/multigrid_invert_test.cpp:529-577), agreement with the single-source invertQuda, the same
 iteration count within one."""
 import importlib

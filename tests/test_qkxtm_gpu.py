@@ -148,7 +148,7 @@ def test_propagators_with_up_and_down_hierarchies(qa, oracle):
         print("24 MG-GCR solves: %d outer iterations in total, %.3f s in the solvers, worst true residual %.2e, %s" % (ip.iter, ip.secs, worst, s1))
         assert worst < 5e-10, worst
         assert ip.iter < 24 * 30, ip.iter
-        # the twelve sources of a flavour went through ONE lockstep solve each, smoothed on block fields (csrc/block_solver.cpp)
+        # the twelve sources of a flavour went through ONE lockstep solve each, smoothed on block fields (csrc/block_solver.cpp, block_fine_smoother.cpp)
         assert s1["solves"] - s0["solves"] == 2 and s1["block_smoothed"] > s0["block_smoothed"], (s0, s1)
     finally:
         for h, _, _ in hier.values():
